@@ -16,16 +16,25 @@ run: the top-level `traffic_source` says so; null for any other shape.  `lds_fra
 own bound: every stored entry gathers a 256-byte Q row from LDS (256 B/clk/CU), so a launch
 cannot take less than nnz / (CUs x clock) whatever the HBM does.
 
+A plain run (no --full) sets up, warms up, times the --steps steps, writes --dump-outputs and prints the line: the
+headline figure, ms_per_step and the roofline of the SpMM launches of those steps.
+
+--full adds everything else the line used to carry:
 parity: the CPU leg's f32 ARPACK result on its sample is kept, the GPU path runs tfidf + lsi on the
 same sample, and the largest principal angle between the two top-k right singular subspaces and
 the largest relative difference of the singular values go into the JSON line (`parity`).
 
-secondary: the default run (c3, one GPU) also carries the two other single-GPU configurations of
+secondary: the --full run (c3, one GPU) also carries the two other single-GPU configurations of
 BASELINE.json as complete sub-records (ms, roofline, cpu_baseline, parity): `c2` (configs[0]/[1]) and
 `c4` (configs[3], mu.tl.mofa, f32) + `c4_f64` (the same in the reference's default precision), and
 `ingest` / `mofa_ng` / `mofa_bern` / `wnn`: one measured record with parity per widened row of SURVEY 8f, `c3_api`: the
 API path from a host matrix.
---no-secondary skips them.
+--no-secondary / --no-cpu-baseline skip them in a --full run.
+
+--dump-outputs DIR (LSI workloads: c3, c3shard, c2): after the timed steps, rank 0 writes what the last step returned,
+as .npy: lsi_stdev (f64 [k]), lsi_V (f32 [d, k]), lsi_U (f32, a seeded sample of rows) and tfidf_values (f32, a seeded
+sample of the stored entries), each sample with its positions (<name>_rows / tfidf_positions, f64).  Inputs depend only
+on the arguments, so two builds can be compared output for output.
 
 Workloads (--workload):
   c3 (default)       BASELINE.json configs[2], the shape the metric is quoted on: 1 000 000 cells x
@@ -48,7 +57,7 @@ Workloads (--workload):
                      200 000, a quarter of configs[2]): upload, fingerprints and write-back inside the clock, split
                      into upload / fingerprint / download / kernels
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either run it under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either run it under
 torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env) or
 just call `python bench.py --gpus N`: it then starts its own N ranks (torch.distributed.run on
 127.0.0.1 with a free port).  Prints ONE JSON line on rank 0.
@@ -158,6 +167,35 @@ def cpu_baseline(be, peaks, density, seed, sample_cells, n_comps):
     }, parity
 
 
+DUMP_SEED = 20240611  # fixes which rows / entries --dump-outputs samples
+DUMP_MAX_ROWS = {"lsi_V": 200_000, "lsi_U": 16_384}
+DUMP_TFIDF_ENTRIES = 1 << 19
+
+
+def _sample_positions(n, m):
+    """Sorted, distinct positions in [0, n): all of them if n <= m, else a sample drawn from DUMP_SEED."""
+    if n <= m:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=m, dtype=np.int64))
+
+
+def dump_outputs(path, U, stdev, V, tf_values):
+    """--dump-outputs: what the last timed step returned (U, stdev, V of lsi; the tfidf values it computed), as .npy."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "lsi_stdev.npy"), np.asarray(stdev, dtype=np.float64))
+    for name, t in (("lsi_V", V), ("lsi_U", U)):
+        rows = _sample_positions(t.shape[0], DUMP_MAX_ROWS[name])
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy())
+    pos = _sample_positions(tf_values.numel(), DUMP_TFIDF_ENTRIES)
+    vals = tf_values if pos is None else tf_values[torch.from_numpy(pos).to(tf_values.device)]
+    np.save(os.path.join(path, "tfidf_values.npy"), vals.detach().float().cpu().numpy())
+    if pos is not None:
+        np.save(os.path.join(path, "tfidf_positions.npy"), pos.astype(np.float64))
+
+
 def newest_traffic_profile():
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_spmm_traffic.json")))
     return files[-1] if files else None
@@ -214,8 +252,10 @@ def run_lsi(args, workload, rank, world, local_rank, comm, steps, warmup, cpu_sa
     sync()
     ms0 = torch.cuda.memory_stats(local_rank)
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
+    for i in range(steps):
+        res = step()
+        if i + 1 < steps:  # (only the last step's U / stdev / V outlive their step: --dump-outputs)
+            del res
     sync()
     dt = time.perf_counter() - t0
     be.enabled = False
@@ -231,6 +271,10 @@ def run_lsi(args, workload, rank, world, local_rank, comm, steps, warmup, cpu_sa
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+
+    if args.dump_outputs and rank == 0 and workload == args.workload:
+        dump_outputs(args.dump_outputs, *res, tf_vals)
+    del res
 
     # dominant kernel: the row-stream SpMM (both X*Q and X^T*Y run through it)
     ms = [s.elapsed_time(e) for s, e, _, _, _ in be.events]
@@ -310,7 +354,7 @@ def run_lsi(args, workload, rank, world, local_rank, comm, steps, warmup, cpu_sa
             },
             "traffic_source": traffic_source,
         }
-        if not args.no_cpu_baseline and world == 1:  # (the CPU leg and the sample parity ride on the N = 1 line only)
+        if args.full and not args.no_cpu_baseline and world == 1:  # (the CPU leg and the sample parity ride on the N = 1 line only)
             out["cpu_baseline"], out["parity"] = cpu_baseline(be._be, d, args.density, args.seed,
                                                               min(cpu_sample_cells, n_global), args.n_comps)
     del X, tf_vals, be
@@ -378,7 +422,7 @@ def run_c4(args, steps, warmup, f64=False):
     argv = ["--gpus", str(args.gpus), "--iters", str(steps), "--warmup", str(max(warmup, 3))]
     if args.cells and args.workload == "c4":
         argv += ["--cells", str(args.cells)]
-    if args.no_cpu_baseline or f64:
+    if args.no_cpu_baseline or not args.full or f64:
         argv += ["--no-cpu-baseline"]
     if f64:
         argv += ["--f64"]
@@ -427,11 +471,19 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cpu-sample-cells", type=int, default=12000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline and parity and, for the default workload on one GPU, the secondary records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (LSI workloads)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default workload on one GPU: do not append the c2 / c4 sub-records")
+                    help="with --full, default workload on one GPU: do not append the c2 / c4 sub-records")
     ap.add_argument("--no-pack", action="store_true",
                     help="ablation: run the SpMM on plain CSR (k_spmm_rowwave, one wave per row) instead of the row streams")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and WORKLOADS[args.workload] is None:
+        ap.error(f"--dump-outputs: the LSI workloads only (c3, c3shard, c2), not {args.workload}")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -478,8 +530,8 @@ def main():
     elif args.workload in ("ingest", "mofa_ng", "mofa_bern", "wnn", "c3_api", "c3_rank8", "c5_rank8", "unstructured", "hard"):
         out = run_widened(args.workload) if rank == 0 else None
     else:
-        default_line = (args.workload == "c3" and world == 1 and not (args.cells or args.peaks or args.no_pack
-                                                                       or args.no_secondary))
+        default_line = (args.full and args.workload == "c3" and world == 1
+                        and not (args.cells or args.peaks or args.no_pack or args.no_secondary))
         sec = {}
         if default_line:
             # The 10k x 30k record first: that call is host-bound (a host eigensolve and ~330 launches per call) and

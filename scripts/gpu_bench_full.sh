@@ -1,12 +1,12 @@
 #!/bin/bash
-# the default bench line with every secondary record, timed like the driver runs it
+# the --full bench line with every secondary record
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:-bench_full}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 s=$(date +%s)
-timeout 1500 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$? wall=$(( $(date +%s) - s )) s"; tail -3 "$OUT/bench.err"
 python - "$OUT" <<'PY'
 import json,sys

@@ -13,7 +13,7 @@ timeout 1200 python -m pytest tests -x -q -m gpu > "$OUT/pytest_gpu.txt" 2>&1
 echo "rc=$?" | tee -a "$OUT/steps.txt"; tail -5 "$OUT/pytest_gpu.txt"
 fi
 echo "== bench c3" | tee -a "$OUT/steps.txt"
-timeout 600 python bench.py --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "rc=$?" | tee -a "$OUT/steps.txt"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 echo "== bench c3shard (weak-scaling shard)" | tee -a "$OUT/steps.txt"
 timeout 600 python bench.py --workload c3shard --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_c3shard.json" 2> "$OUT/bench_c3shard.err"

@@ -224,6 +224,40 @@ def test_bench_rccl_branch_runs_on_one_gpu():
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["config"]["lsi"]["converged"]
 
 
+def test_bench_dumps_the_last_steps_outputs_identically(tmp_path):
+    """bench.py --dump-outputs DIR: two runs with the same arguments write the same arrays (f32 / f64 .npy, sampled
+    rows of U with their positions, a sample of the tfidf values), and a plain run carries no CPU baseline."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c3shard",
+                            "--cells", "20000", "--peaks", "9000", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        print(r.stdout[-2000:], r.stderr[-2000:])
+        assert r.returncode == 0
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "parity" not in out
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d)) if f.endswith(".npy")})
+    a, b = dumps
+    assert set(a) == set(b) == {"lsi_stdev", "lsi_V", "lsi_U", "lsi_U_rows", "tfidf_values", "tfidf_positions"}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["lsi_V"].shape == (9000, 50) and a["lsi_stdev"].shape == (50,)
+    assert a["lsi_U"].shape == (len(a["lsi_U_rows"]), 50) and 0 < len(a["lsi_U_rows"]) <= 16384
+    assert len(a["tfidf_values"]) == len(a["tfidf_positions"]) > 0
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
 def test_rank_deficient_input_takes_the_device_flag_and_the_host_redo(hip):
     """min(n, d) >= 8192 selects the device-side Cholesky of CholeskyQR; a matrix of rank 20 asked for 30
     components exhausts the Krylov space, the device flags the pivot that is not safely positive, the call

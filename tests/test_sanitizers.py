@@ -3,7 +3,7 @@
 GPU sanitizers are not available on this pool; what can be checked without a device is everything an entry point does
 before its first launch (argument validation, geometry and work-size arithmetic, the by-value range descriptors, the tune
 table, the error string) and the pure host code (mu_host_hash64 and its threads).  scripts/sanitize_host.py builds the
-library with -fsanitize=address,undefined for the host (cached by source digest: ~80 s cold, seconds warm) and drives it
+library with AddressSanitizer + UBSan on its host code only (cached by source digest: ~80 s cold, seconds warm) and drives it
 in a subprocess under the sanitizer runtime.  Its first run found the null-pointer arithmetic of mu_tpack4_err_offset."""
 import os
 import shutil
