@@ -253,7 +253,8 @@ int mu_spmm_stream_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, con
  * to 2^-48), i.e. two streams and two launches; data that is exact in f32 (counts) needs one. */
 /* r06 - the products of lsi's SUBSAMPLED WARM START (muon_amd/_atac/tools.py; the reference has no counterpart: its
  * ARPACK run, /root/reference/muon/_atac/tools.py:53, starts from a random vector) without operands of their own:
- * mu_spmm_stream_ranges_f32 is mu_spmm_stream_f32 (B = 64) restricted to a list of <= 32 column ranges.  h_ranges5 holds
+ * mu_spmm_stream_ranges_f32 is mu_spmm_stream_f32 (B = 64) restricted to a list of <= 32 column ranges (narrower
+ * blocks, B = 16 / 32, are zero-padded to 64 columns by the callers: HipBackend.spmm_slice / spmm_slice_t).  h_ranges5 holds
  * {col0, col1, q_off, ta, tb} per range: the entries of position p's row in columns [col0, col1)
  * are pairs d_sptr[p] + d_tbl[ta * tbl_stride + row] .. d_sptr[p] + d_tbl[tb * tbl_stride + row] (row = d_perm[p], or p),
  * column c multiplies row c - col0 + q_off of d_Q (q_rows x 64).  Workgroup (x, y) walks ranges [y per_wg, (y + 1) per_wg)

@@ -868,12 +868,18 @@ class HipBackend:
         return dict(sptr=sptr, ent=ent, rel=rel, n_s=n_s, nnz_s=nnz_s, K=K, group=group, d=d, S=S1 - 1)
 
     def spmm_slice(self, S: dict, Q: torch.Tensor) -> torch.Tensor:
-        """Y_S = X_S Q [n_s x 64] on the compact slice stream, column super-slabs split over the chip, partial products
-        summed in fixed order."""
+        """Y_S = X_S Q [n_s x B] on the compact slice stream, column super-slabs split over the chip, partial products
+        summed in fixed order.  B = 16 / 32 / 64; the kernel exists for 64 columns only: a narrower Q is zero-padded to
+        64 and the leading B columns of the product returned (the padded ones are exact zeros)."""
         import ctypes as C
 
         d, n_s = S["d"], S["n_s"]
-        assert Q.shape == (d, 64) and Q.dtype == torch.float32 and Q.is_contiguous()
+        B = Q.shape[1] if Q.dim() == 2 else 0
+        assert Q.shape == (d, B) and B in (16, 32, 64) and Q.dtype == torch.float32 and Q.is_contiguous()
+        if B < 64:
+            Qp = self.zeros((d, 64), torch.float32)
+            Qp[:, :B] = Q
+            return self.spmm_slice(S, Qp)[:, :B].contiguous()
         ns, g = S["S"], S["group"]
         ny = -(-ns // g)
         part = self.empty((ny, n_s, 64), torch.float32)
@@ -886,13 +892,20 @@ class HipBackend:
         return part[0] if ny == 1 else part.sum(dim=0)
 
     def spmm_slice_t(self, Xt: DeviceStream, plan, Ys: torch.Tensor) -> torch.Tensor:
-        """Z = X_S^T Y_S [d x 64] on the row stream of X^T as it is: the slice's cells are <= 16 contiguous pieces of
-        every row, found through the transposition's count prefixes (Xt.t4)."""
+        """Z = X_S^T Y_S [d x B] on the row stream of X^T as it is: the slice's cells are <= 16 contiguous pieces of
+        every row, found through the transposition's count prefixes (Xt.t4).  B = 16 / 32 / 64, a narrower Y_S
+        zero-padded to the kernel's 64 columns like in spmm_slice."""
         import ctypes as C
 
         d, n = Xt.shape
         t4, rg = Xt.t4, plan["ranges"]
-        assert t4 is not None and t4["rpb"] == plan["rpb"] and Ys.shape == (plan["n_s"], 64) and Ys.is_contiguous()
+        B = Ys.shape[1] if Ys.dim() == 2 else 0
+        assert t4 is not None and t4["rpb"] == plan["rpb"] and Ys.shape == (plan["n_s"], B) and B in (16, 32, 64) \
+            and Ys.dtype == torch.float32 and Ys.is_contiguous()
+        if B < 64:
+            Yp = self.zeros((plan["n_s"], 64), torch.float32)
+            Yp[:, :B] = Ys
+            return self.spmm_slice_t(Xt, plan, Yp)[:, :B].contiguous()
         Z = self.empty((d, 64), torch.float32)
         h = (C.c_int32 * (5 * len(rg)))()
         q_off = 0

@@ -60,6 +60,16 @@ angw = float(torch.linalg.matrix_norm(qb - qa @ (qa.T @ qb), ord=2))
 assert angw < 5e-5 and float(np.max(np.abs(sdw - sd) / sd)) < 1e-6, (angw, infow["bounds"])
 if rank == 0:
     print(f"warm start ({infow['warm_start']}): {infow['iterations']} expansions against {info['iterations']}, angle to the cold run {angw:.2e}")
+# the same at a narrow block: n_comps = 10 is B = 32, the ranged slice products zero-padded to their kernel's 64 columns,
+# the partial X_S^T Y_S of the ranks summed at width 32; on 10 planted topics (n_comps at a spectral gap: with 50, the
+# 10th value sits inside the planted cluster), against the single-process run below
+k10 = 10
+T10 = tfidf_device(be, be.synth_counts(r0, r1 - r0, d, k10, 0.03, 0), n, 3, 1e4, comm=comm)
+os.environ["MUON_AMD_LSI_WARM"] = "8:2"
+U10, sd10, V10, info10 = lsi_device(be, T10, n_comps=k10, n_obs=n, comm=comm, return_info=True)
+os.environ.pop("MUON_AMD_LSI_WARM")
+assert info10["block"] == 32 and info10["warm_start"] is not None and info10["warm_start"]["slice"] == "ranges" \
+    and info10["converged"], (info10["warm_start"], info10["bounds"])
 # f64 arithmetic for f64 input (r06, tools._refine_f64) on the row streams of the shards: the f32 process continued in f64
 # blocks, Z = X^T Y summed over the ranks in f64, the stop decisions rank 0's; against the same on one rank below
 U6, sd6, V6, info6 = lsi_device(be, T, n_comps=k, n_obs=n, comm=comm, return_info=True, refine_f64=True)
@@ -78,6 +88,15 @@ if rank == 0:
     print(f"ranks {world}: tfidf max rel diff {dv:.2e}, subspace angle vs single process {ang:.2e}, stdev rel diff {ds:.2e}, "
           f"|U| max diff {du:.2e}, iterations {info['iterations']} / {inff['iterations']}")
     assert dv < 1e-6 and ang < 1e-4 and ds < 1e-5
+    Tf10 = tfidf_device(be, be.synth_counts(0, n, d, k10, 0.03, 0), n, 3, 1e4)
+    _, sd10f, V10f, inf10 = lsi_device(be, Tf10, n_comps=k10, return_info=True)
+    qa, _ = torch.linalg.qr(V10.double())
+    qb, _ = torch.linalg.qr(V10f.double())
+    ang10 = float(torch.linalg.matrix_norm(qb - qa @ (qa.T @ qb), ord=2))
+    ds10 = float(np.max(np.abs(sd10 - sd10f) / sd10f))
+    print(f"warm start at n_comps = {k10} (B = {info10['block']}, {info10['warm_start']}), ranks {world}: subspace angle vs "
+          f"single process {ang10:.2e}, stdev rel diff {ds10:.2e}, iterations {info10['iterations']} / {inf10['iterations']}")
+    assert inf10["warm_start"] is None and inf10["converged"] and ang10 < 1e-4 and ds10 < 1e-5
     U6f, sd6f, V6f, inf6 = lsi_device(be, Tf, n_comps=k, return_info=True, refine_f64=True)
     qa, _ = torch.linalg.qr(V6)
     qb, _ = torch.linalg.qr(V6f)

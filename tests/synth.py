@@ -54,3 +54,13 @@ def unstructured_csr(n, d, density=0.03, seed=0, dtype=np.float32):
     X.indices = X.indices.astype(np.int32)
     X.indptr = X.indptr.astype(np.int64)
     return X
+
+
+def rank20_f64_csr(n=9000, d=9000, seed=0):
+    """Rank 20 with f64 values: 20 sparse base rows (2 % density), every cell a copy of one scaled by 1 + U(0, 1)."""
+    rng = np.random.default_rng(seed)
+    base = sp.random(20, d, density=0.02, random_state=rng, format="csr", dtype=np.float64)
+    idx = rng.integers(0, 20, n)
+    X = (sp.diags(1 + rng.random(n)) @ base[idx]).tocsr()
+    X.sort_indices()
+    return X

@@ -11,7 +11,7 @@ from muon_amd import AnnData
 from muon_amd import atac as ac
 from muon_amd._atac.tools import lsi_device
 from oracle import lsi_oracle
-from tests.synth import planted_topics_csr
+from tests.synth import planted_topics_csr, rank20_f64_csr
 
 pytestmark = pytest.mark.gpu
 ANGLE = 1e-4
@@ -288,6 +288,37 @@ def test_rank_deficient_input_takes_the_device_flag_and_the_host_redo(hip):
     assert np.all(s[20:] < 1e-3 * s[0]) and np.all(np.isfinite(hip.to_host(U))) and np.all(np.isfinite(hip.to_host(V)))
 
 
+def test_rank_deficient_f64_input_takes_the_host_redo_and_the_f64_continuation(hip, monkeypatch):
+    """The f64 counterpart of the test above, through ac.tl.lsi on an f64 AnnData: the device Cholesky flags the
+    exhausted Krylov space, the call is redone on the host path, and tools._refine_f64 continues the result in f64 from
+    a start block with more columns than the matrix has rank (deflation; s = 0 would divide U).  The 20 singular
+    values and right vectors that exist to f64 accuracy, everything finite, the other 10 values at the level of
+    rounding."""
+    from scipy.sparse.linalg import svds
+
+    from muon_amd._atac import tools
+
+    X = rank20_f64_csr()
+    n = X.shape[0]
+    calls = []
+    orig = tools._lsi_device
+    monkeypatch.setattr(tools, "_lsi_device", lambda *a, **k: (calls.append(k.get("device_qr")), orig(*a, **k))[1])
+    ad = AnnData(X.copy())
+    ac.tl.lsi(ad, n_comps=30, backend=hip)
+    assert calls == [None, False], calls  # (device QR first, then the redo on the host path)
+    U, V, sd = ad.obsm["X_lsi"], ad.varm["LSI"], ad.uns["lsi"]["stdev"]
+    assert U.dtype == V.dtype == sd.dtype == np.float64 and U.shape == (n, 30) and V.shape == (X.shape[1], 30)
+    assert np.all(np.isfinite(U)) and np.all(np.isfinite(V)) and np.all(np.isfinite(sd))
+    _, want, vt = svds(X, k=20)
+    o = np.argsort(want)[::-1]
+    s = sd * np.sqrt(n - 1)
+    rel = np.max(np.abs(s[:20] / want[o] - 1))
+    angle = lsi_oracle.max_subspace_angle(V[:, :20], vt[o].T)
+    print(f"rank 20 of 30, f64: singular values rel {rel:.1e}, angle {angle:.1e}, tail {np.max(sd[20:]) / sd[0]:.1e}")
+    assert rel < 1e-8 and angle < 1e-6
+    assert np.all(sd[20:] < 1e-6 * sd[0])
+
+
 def test_widened_bench_records_run_small_and_hold_parity(hip):
     """scripts/bench_widened.py (the `secondary` records of SURVEY 8f.2 - 8f.4 in the bench line) at toy
     sizes: every record carries a value and its parity against the oracle / the scipy route."""
@@ -364,12 +395,19 @@ def test_warm_start_saves_an_expansion_and_gives_the_same_subspace(hip, monkeypa
         assert np.max(np.abs(sd - ref["stdev"]) / ref["stdev"]) < 1e-5
 
 
-@pytest.mark.parametrize("n,d,n_s,dens", [(40000, 12000, 5000, 0.03), (6000, 30000, 1500, 0.02), (3000, 700, 640, 0.1),
-                                          (70000, 9000, 2200, 0.01)])
-def test_slice_products_without_operands_of_their_own(hip, n, d, n_s, dens):
+_SLICE_SHAPES = [(40000, 12000, 5000, 0.03), (6000, 30000, 1500, 0.02), (3000, 700, 640, 0.1), (70000, 9000, 2200, 0.01)]
+
+
+# (the 64-wide cases keep their ids of before the width parameter)
+@pytest.mark.parametrize("n,d,n_s,dens,B", [(*sh, B) for sh in _SLICE_SHAPES for B in (64, 32, 16)],
+                         ids=[f"{n}-{d}-{n_s}-{dens}" + ("" if B == 64 else f"-B{B}")
+                              for n, d, n_s, dens in _SLICE_SHAPES for B in (64, 32, 16)])
+def test_slice_products_without_operands_of_their_own(hip, n, d, n_s, dens, B):
     """r06: the warm start's products on a cell slice.  X_S Q on the compact slice stream with the column super-slabs
     split over blockIdx.y (mu_csr_slice_stream, mu_spmm_stream_ranges_f32), X_S^T Y_S on the row stream of X^T as it
-    is, the slice's cells found through the transposition's count prefixes - against scipy on the same rows."""
+    is, the slice's cells found through the transposition's count prefixes - against scipy on the same rows.  At every
+    block width lsi uses (n_comps + oversample <= 16 / 32 / 64): the narrow blocks go through the 64-column kernel
+    zero-padded, and come back as wide as they went in."""
     import scipy.sparse as sp
 
     rng = np.random.default_rng(n + d)
@@ -388,16 +426,20 @@ def test_slice_products_without_operands_of_their_own(hip, n, d, n_s, dens):
     ms = m[rows].astype(np.float64)
     assert plan["nnz_s"] == ms.nnz
     S = hip.slice_stream(X, plan)
-    Q = rng.standard_normal((d, 64)).astype(np.float32)
+    Q = rng.standard_normal((d, B)).astype(np.float32)
     Ys = hip.spmm_slice(S, hip.to_device(Q))
+    assert Ys.shape == (plan["n_s"], B)
     want = ms @ Q.astype(np.float64)
     got = hip.to_host(Ys)
     assert np.max(np.abs(got - want)) <= 2e-5 * np.max(np.abs(want))
-    Z = hip.to_host(hip.spmm_slice_t(Xt, plan, Ys))
+    Zd = hip.spmm_slice_t(Xt, plan, Ys)
+    assert Zd.shape == (d, B)
+    Z = hip.to_host(Zd)
     wantz = ms.T @ got.astype(np.float64)
     assert np.max(np.abs(Z - wantz)) <= 2e-5 * np.max(np.abs(wantz))
     # the same bytes run to run (fixed-order sums)
     assert np.array_equal(hip.to_host(hip.spmm_slice(S, hip.to_device(Q))), got)
+    assert np.array_equal(hip.to_host(hip.spmm_slice_t(Xt, plan, Ys)), Z)
 
 
 def test_warm_start_on_ranges_matches_the_slice_operands(hip, monkeypatch):
@@ -422,6 +464,97 @@ def test_warm_start_on_ranges_matches_the_slice_operands(hip, monkeypatch):
         assert np.max(np.abs(sd - ref["stdev"]) / ref["stdev"]) < 1e-5
         out[how] = info
     assert out["ranges"]["iterations"] == out["operands"]["iterations"]
+
+
+def _narrow_topics_csr(n, d, n_topics, seed):
+    """Counts of n cells over d < 64 features, n_topics topics of 4 features each over a background, unequal topic
+    sizes: a TF-IDF matrix with n_topics separated singular values (planted_topics_csr up-weights 5 % of the features -
+    one of 20 - and leaves no gap at that width)."""
+    rng = np.random.default_rng(seed)
+    p = 0.3 * rng.gamma(2.0, 1.0, size=(n_topics, d)) / d
+    for t in range(n_topics):
+        p[t, 4 * t:4 * t + 4] += 0.7 * rng.gamma(2.0, 1.0, size=4) / 4
+    p /= p.sum(axis=1, keepdims=True)
+    topic = rng.choice(n_topics, size=n, p=np.arange(1, n_topics + 1) / (n_topics * (n_topics + 1) / 2))
+    c = rng.poisson(rng.lognormal(np.log(8), 0.3, size=n)[:, None] * p[topic])
+    c[c.sum(axis=1) == 0, 0] = 1
+    X = sp.csr_matrix(c.astype(np.float32))
+    X.sort_indices()
+    return X
+
+
+# n_comps -> (cells, features, planted topics, seed, block width): both sides of every width boundary of
+# pick_block(n_comps + 14), each at a spectral gap (n_topics = n_comps), and a matrix with fewer features than the
+# block is wide (target 19 -> B = 32, w = 20: the warm start's `Zs[:, w:] = 0`)
+_WARM_WIDTH_CASES = {"k1": (1, 40000, 2000, 1, 21, 16), "k2": (2, 40000, 2000, 2, 22, 16),
+                     "k5": (5, 40000, 2000, 5, 25, 32), "k18": (18, 40000, 2000, 18, 38, 32),
+                     "k19": (19, 40000, 2000, 19, 39, 64), "k50": (50, 40000, 3000, 50, 70, 64),
+                     "k5_d20": (5, 40000, 20, 5, 0, 32)}
+
+
+@pytest.fixture(scope="module")
+def warm_width_operands(hip):
+    """TF-IDF operands made by tfidf_device (their slab pointers are what the ranged slice needs) and the f64 ARPACK
+    oracle of each at n_comps + 1 components (the extra one: sigma_k+1 for the gap), one per case, built once."""
+    from muon_amd._atac.preproc import tfidf_device
+
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            k, n, d, topics, seed, _ = _WARM_WIDTH_CASES[case]
+            if d < 64:
+                X = _narrow_topics_csr(n, d, topics, seed)
+            else:
+                X = planted_topics_csr(n, d, n_topics=topics, density=0.03, seed=seed, dtype=np.float32)
+            Xd = hip.upload_csr(X.indptr, X.indices, X.data, X.shape)
+            T = tfidf_device(hip, Xd, n, 3, 1e4)
+            Th = sp.csr_matrix((hip.to_host(T.values).astype(np.float64), hip.to_host(T.indices),
+                                hip.to_host(T.indptr)), shape=T.shape)
+            cache[case] = (T, lsi_oracle.lsi(Th, n_comps=k + 1))
+        return cache[case]
+
+    return get
+
+
+@pytest.mark.parametrize("case", list(_WARM_WIDTH_CASES))
+def test_warm_start_at_every_block_width_against_the_f64_oracle(hip, monkeypatch, warm_width_operands, case):
+    """The warm start (MUON_AMD_LSI_WARM) is the one part of lsi that depends on the block width, the slice path and
+    the rank count together; the other warm-start tests run n_comps = 20 (B = 64) only.  Here n_comps = 1, 2 (B = 16),
+    5, 18 (B = 32), 19, 50 (B = 64) and a 20-feature matrix (B = 32 with 20 active columns), each cold, warm on the
+    ranged slice products (the 64-column kernel, narrower blocks zero-padded) and warm on the slice's own operands:
+    against f64 ARPACK of the same operand, and the two slice paths taking the same number of expansions."""
+    k, n, d, _, _, B = _WARM_WIDTH_CASES[case]
+    T, ref = warm_width_operands(case)
+    sv = ref["svalues"]
+    assert sv[k - 1] / sv[k] - 1 > 0.01, sv[:k + 1]  # (n_comps at a spectral gap: the subspace is well posed)
+    assert sv[0] / sv[1] - 1 > 0.01, sv[:2]  # (the leading component is isolated: compared vector-wise)
+    want_V, want_U, want_sd = ref["LSI"][:, :k], ref["X_lsi"][:, :k], ref["stdev"][:k]
+    runs = {}
+    for how in ("off", "ranges", "operands"):
+        monkeypatch.setenv("MUON_AMD_LSI_WARM", "0" if how == "off" else "8:2")
+        monkeypatch.setenv("MUON_AMD_LSI_WARM_SLICE", "ranges" if how == "off" else how)
+        U, sd, V, info = lsi_device(hip, T, n_comps=k, n_obs=n, return_info=True)
+        assert info["block"] == B and info["width"] == min(B, d), (how, info["block"], info["width"])
+        if how == "off":
+            assert info["warm_start"] is None
+        else:
+            ws = info["warm_start"]
+            assert ws is not None and ws["slice"] == how and ws["power_steps"] == 2 and ws["cells"] >= 8192, (how, ws)
+        assert info["converged"], (how, info["bounds"])
+        assert U.shape == (n, k) and V.shape == (d, k)
+        angle = lsi_oracle.max_subspace_angle(hip.to_host(V), want_V)
+        rel = np.max(np.abs(sd - want_sd) / want_sd)
+        print(f"{case} {how}: B {info['block']}, {info['iterations']} expansions, angle {angle:.2e}, stdev rel {rel:.1e}")
+        assert angle < ANGLE, (how, angle)
+        assert rel < 1e-5, (how, rel)
+        Uh = hip.to_host(U)
+        u = lsi_oracle.sign_align(Uh[:, :1], want_U[:, :1])
+        np.testing.assert_allclose(u, want_U[:, :1], atol=2e-3, err_msg=how)
+        np.testing.assert_allclose(Uh.mean(axis=0), 0, atol=1e-3, err_msg=how)
+        np.testing.assert_allclose(Uh.std(axis=0), 1, rtol=1e-3, err_msg=how)
+        runs[how] = info
+    assert runs["ranges"]["iterations"] == runs["operands"]["iterations"], (runs["ranges"]["bounds"], runs["operands"]["bounds"])
 
 
 def test_f64_input_is_answered_in_f64_arithmetic(hip):

@@ -609,6 +609,36 @@ def test_f64_continuation_with_wide_starts_and_an_exhausted_krylov_space(k):
     assert np.abs(V.numpy().T @ V.numpy() - np.eye(k)).max() < 1e-10
 
 
+def test_f64_input_of_rank_below_n_comps():
+    """The rank-20 f64 case of tests/test_gpu_lsi.py on the CPU operator set: the device-side Cholesky flags the exhausted
+    Krylov space, the call is redone on the host path, and the f64 continuation starts from more columns than the
+    matrix has rank: the 20 values and vectors that exist to f64 accuracy, the other 10 finite and at rounding level."""
+    from scipy.sparse.linalg import svds
+
+    from muon_amd._atac import tools
+    from tests.synth import rank20_f64_csr
+
+    X = rank20_f64_csr()
+    n = X.shape[0]
+    calls = []
+    orig = tools._lsi_device
+    try:
+        tools._lsi_device = lambda *a, **k: (calls.append(k.get("device_qr")), orig(*a, **k))[1]
+        ad = AnnData(X.copy())
+        ac.tl.lsi(ad, n_comps=30, backend=BE)
+    finally:
+        tools._lsi_device = orig
+    assert calls == [None, False], calls
+    U, V, sd = ad.obsm["X_lsi"], ad.varm["LSI"], ad.uns["lsi"]["stdev"]
+    assert U.dtype == V.dtype == sd.dtype == np.float64
+    assert np.all(np.isfinite(U)) and np.all(np.isfinite(V)) and np.all(np.isfinite(sd))
+    _, want, vt = svds(X, k=20)
+    o = np.argsort(want)[::-1]
+    np.testing.assert_allclose(sd[:20] * np.sqrt(n - 1), want[o], rtol=1e-8)
+    assert lsi_oracle.max_subspace_angle(V[:, :20], vt[o].T) < 1e-6
+    assert np.all(sd[20:] < 1e-6 * sd[0])
+
+
 def test_bench_line_is_flattened_for_the_driver():
     """bench.py:flatten_for_driver: the driver keeps scalar keys of `config` and a 2 000-character
     tail of the line - parity, the LSI figures, one value per secondary record (and the hard spectrum's f64 continuation)
