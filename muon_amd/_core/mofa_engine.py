@@ -59,6 +59,22 @@ def _can_ell16(be, X, wide: bool) -> bool:
     return max(X.shape) * row < (1 << 32)
 
 
+LDS_TILE_BYTES = 60000  # the Grams' LDS tile of csrc/mofa.hip and csrc/mofa_elbo.hip
+
+
+def two_pass_fits(M: int, G: int, K: int) -> bool:
+    """True iff the two-pass engine's kernels take M views, G groups and K factors: the argument checks of
+    mu_mofa_update_w and mu_mofa_tau_elbo (every group's K x K Gram and its diagonal moments in LDS) and of
+    mu_mofa_update_z (every (view, group) Gram, its moments and its centring term).  The tiles are sized at
+    8 bytes per entry for f32 as well."""
+    M, G, K = int(M), int(G), int(K)
+    if not (1 <= K <= 32 and M >= 1 and G >= 1):
+        return False
+    w_ok = G * (K * K + K) * 8 <= LDS_TILE_BYTES  # update_w, tau_elbo
+    z_ok = M * G * (K * K + 2 * K) * 8 <= LDS_TILE_BYTES  # update_z
+    return w_ok and z_ok
+
+
 class _View:
     pass
 
@@ -83,6 +99,10 @@ class MofaEngine:
                          spikeslab_weights=spikeslab_weights)
         groups = np.asarray(groups, dtype=np.int64)
         self.N = N = len(groups)
+        self.G = G = self._global_max(groups) + 1
+        if not two_pass_fits(len(views), G, self.K):
+            raise NotImplementedError(f"{len(views)} views x {G} groups x {self.K} factors do not fit the sweeps' LDS "
+                                      "tile (two_pass_fits): GeneralMofaEngine fits this model")
         # the seeded host draw of the factors' initial expectations (8 ns per normal, the GIL released): on a host
         # thread while the device works through the views
         import threading
@@ -93,7 +113,6 @@ class MofaEngine:
                               daemon=True)
         th.start()
         self._z0 = (th, z0)
-        self.G = G = self._global_max(groups) + 1
         # samples sorted by group (stable) so that every group is a contiguous row range
         self.perm = np.argsort(groups, kind="stable")
         gs = groups[self.perm]

@@ -133,6 +133,45 @@ def _has_elementwise_nan(v) -> bool:
     return bool((a.any(axis=1) & ~a.all(axis=1)).any())
 
 
+def _needs_general_engine(backend, views, lik, groups, n_factors, spikeslab_factors, comm=None) -> bool:
+    """True iff the fit goes to GeneralMofaEngine rather than the two-pass MofaEngine: pseudo-data likelihoods or
+    element-wise missing values (element-wise precisions, walked in row chunks; the sparse modalities stay CSR on the
+    device), and the model options the two-pass engine's kernels are not instantiated for - more than 32 factors
+    (tools.py:298 takes any int), more than 64 stacked (group, factor) columns against a sparse view,
+    spikeslab_factors=True (tools.py:305,486), more views x groups x factors than the sweeps' LDS tile holds
+    (two_pass_fits) - the same model on the general engine's chunk passes (slower: those are rare settings).
+    One decision of all ranks: the group count is the maximum over ``comm`` and a shard that needs the general engine
+    decides for every rank (an engine per rank would issue different collectives and hang the fit)."""
+    from .._comm import default_comm
+    from .mofa_engine import two_pass_fits
+
+    comm = default_comm(comm)
+    K = int(n_factors)
+    n_groups = int(np.max(groups)) + 1 if len(groups) else 1
+    local = (any(l != "gaussian" for l in lik) or any(_has_elementwise_nan(v) for v in views)
+             or bool(spikeslab_factors))
+    if comm.world_size > 1:
+        t = torch.tensor([n_groups, int(local)], dtype=torch.int64)
+        if getattr(backend, "name", "") == "hip":
+            t = t.to(backend.device)
+        n_groups, local = (int(x) for x in comm.all_reduce_max(t).tolist())
+    wide = n_groups * K > 64 and any(issparse(v) for v in views)
+    return bool(local) or wide or not two_pass_fits(len(views), n_groups, K)
+
+
+def _mofa_engine(backend, views, lik, groups, n_factors, spikeslab_factors, **kw):
+    """The engine of a Gaussian or pseudo-data fit (_needs_general_engine decides which); ``kw`` goes to its
+    constructor (``comm``, ``row_offset``, ``n_total`` among them)."""
+    if _needs_general_engine(backend, views, lik, groups, n_factors, spikeslab_factors, kw.get("comm")):
+        from .mofa_general import GeneralMofaEngine
+
+        return GeneralMofaEngine(backend, views, list(lik), groups, n_factors, spikeslab_factors=bool(spikeslab_factors),
+                                 **kw)
+    from .mofa_engine import MofaEngine
+
+    return MofaEngine(backend, views, groups, n_factors, **kw)
+
+
 def mofa(
     data,
     groups_label: bool = None,
@@ -234,26 +273,13 @@ def mofa(
         from .._backend import get_backend
 
         backend = get_backend()  # raises without a GPU: no CPU fallback
-    from .mofa_engine import MofaEngine
 
     logger.info("Building the model...")
     kw = dict(dtype=torch.float32 if use_float32 else torch.float64,
               center_groups=center_groups, scale_views=scale_views, scale_groups=scale_groups,
               ard_weights=ard_weights, ard_factors=ard_factors, spikeslab_weights=spikeslab_weights,
               seed=seed, comm=comm)
-    n_groups = int(np.max(groups)) + 1 if len(groups) else 1
-    wide = int(n_factors) > 32 or (n_groups * int(n_factors) > 64 and any(issparse(v) for v in views))
-    if any(l != "gaussian" for l in lik) or any(_has_elementwise_nan(v) for v in views) or spikeslab_factors or wide:
-        # pseudo-data likelihoods / element-wise missing values: element-wise precisions, walked in
-        # row chunks (the sparse modalities stay CSR on the device).  r06: also the model options the two-pass engine's
-        # kernels are not instantiated for - more than 32 factors (tools.py:298 takes any int), more than 64 stacked
-        # (group, factor) columns against a sparse view, spikeslab_factors=True (tools.py:305,486) - the same model on
-        # the general engine's chunk passes (slower: those are rare settings; n_factors defaults to 10)
-        from .mofa_general import GeneralMofaEngine
-
-        eng = GeneralMofaEngine(backend, views, list(lik), groups, n_factors, spikeslab_factors=bool(spikeslab_factors), **kw)
-    else:
-        eng = MofaEngine(backend, views, groups, n_factors, **kw)
+    eng = _mofa_engine(backend, views, lik, groups, n_factors, spikeslab_factors, **kw)
     logger.info("Running the model...")
     eng.run(n_iterations=n_iterations, convergence_mode=convergence_mode)
     res = eng.results(sort_factors=True)

@@ -206,3 +206,92 @@ def test_world_size_2_matches_single_process():
     for a, b in zip(got["g_W"], ref["W"]):
         np.testing.assert_allclose(a, b, atol=1e-8)
     np.testing.assert_allclose(got["g_r2"], ref["r2"], atol=1e-6)
+
+
+def _dispatch_case(case):
+    """Two dense views, sharded 0..95 | 96..191; the shard property that decides the engine is rank 0's or rank 1's only.
+    groups: rank 1 holds no sample of group 31 (32 groups x 10 factors x 2 views do not fit the two-pass engine's tile,
+    31 groups do); nan: only rank 1's shard has element-wise missing values."""
+    rng = np.random.default_rng(3)
+    N = 192
+    Z = rng.standard_normal((N, 3))
+    y1 = Z @ rng.standard_normal((3, 20)) + 0.5 * rng.standard_normal((N, 20))
+    y2 = Z @ rng.standard_normal((3, 15)) + 0.5 * rng.standard_normal((N, 15))
+    if case == "groups":
+        groups, K = np.arange(N) % 31, 10
+        groups[:6] = 31
+    else:
+        groups, K = np.arange(N) % 2, 5
+        y2[150, 3] = np.nan
+    return [y1, y2], groups, K
+
+
+def _dispatch_worker(rank, world, port, case, q):
+    sys.path.insert(0, ROOT)
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from muon_amd._comm import TorchDistComm
+        from muon_amd._core import tools
+        from tests.cpu_backend import CpuTestBackend
+
+        be = CpuTestBackend()
+        comm = TorchDistComm()
+        views, groups, K = _dispatch_case(case)
+        a, b = (0, 96) if rank == 0 else (96, len(groups))
+        shard = [v[a:b] for v in views]
+        lik = ["gaussian"] * len(views)
+        general = tools._needs_general_engine(be, shard, lik, groups[a:b], K, False, comm)
+        both = [None, None]
+        dist.all_gather_object(both, general)
+        out = {"general": both}
+        if both[0] == both[1]:  # (different engines issue different collectives: the fit would hang)
+            eng = tools._mofa_engine(be, shard, lik, groups[a:b], K, False, seed=1, comm=comm, row_offset=a,
+                                     n_total=len(groups))
+            eng.run(5, "slow", min_iterations=100)
+            res = eng.results(sort_factors=False)
+            out.update(kind=type(eng).__name__, elbo=res["elbo"],
+                       Z=comm.all_gather_rows(torch.from_numpy(np.ascontiguousarray(res["Z"]))).numpy(), W=res["W"])
+        if rank == 0:
+            q.put(out)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("case", ["groups", "nan"])
+def test_world_size_2_one_engine_choice_for_all_ranks(case):
+    """The engine is chosen from the GLOBAL group count and from every rank's shard (an OR over the ranks): a rank
+    without the highest group, or a rank whose shard alone has element-wise NaN, must not end on another engine than
+    its peers.  Both ranks on the general engine, and the fit equals the single-process one."""
+    sys.path.insert(0, ROOT)
+    from muon_amd._core import tools
+    from tests.cpu_backend import CpuTestBackend
+
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_dispatch_worker, args=(r, 2, port, case, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = q.get(timeout=240)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert got["general"] == [True, True], got["general"]
+    assert got["kind"] == "GeneralMofaEngine"
+
+    be = CpuTestBackend()
+    views, groups, K = _dispatch_case(case)
+    eng = tools._mofa_engine(be, views, ["gaussian"] * 2, groups, K, False, seed=1)
+    assert type(eng).__name__ == "GeneralMofaEngine"
+    eng.run(5, "slow", min_iterations=100)
+    res = eng.results(sort_factors=False)
+    assert len(got["elbo"]) == len(res["elbo"]) == 5
+    np.testing.assert_allclose(got["elbo"], res["elbo"], rtol=1e-9)
+    np.testing.assert_allclose(got["Z"], res["Z"], atol=1e-8)
+    for a, b in zip(got["W"], res["W"]):
+        np.testing.assert_allclose(a, b, atol=1e-8)

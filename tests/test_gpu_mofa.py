@@ -151,7 +151,8 @@ class TestWrapperOnGpu:
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
-@pytest.mark.parametrize("K,G,ard,ss", [(10, 1, True, True), (10, 2, True, False), (20, 2, False, True), (3, 3, False, False)])
+@pytest.mark.parametrize("K,G,ard,ss", [(10, 1, True, True), (10, 2, True, False), (20, 2, False, True), (3, 3, False, False),
+                                         (1, 1, True, True), (16, 2, True, False), (17, 5, False, True), (32, 7, True, True)])
 def test_fused_small_nodes_match_tensor_formulas(hip, dtype, K, G, ard, ss):
     """csrc/mofa_elbo.hip against the same equations as tensor operations (tests/cpu_backend.py):
     tau / <ln tau>, alpha_w, theta, alpha_z and every ELBO term."""
@@ -829,6 +830,36 @@ def test_wrapper_fits_48_factors_and_90_stacked_columns_on_the_gpu():
     for m in md.mod.values():
         m.obs["grp"] = md.obs["grp"].values
     mu.tl.mofa(md, n_factors=10, groups_label="grp", n_iterations=4, convergence_mode="slow", quiet=True)
+    np.testing.assert_allclose(md.uns["mofa"]["elbo"][:4], ref["elbo"][:4], rtol=1e-8)
+
+
+@pytest.mark.parametrize("M,G,K,general", [(2, 32, 10, True), (1, 8, 32, True), (3, 3, 30, True),
+                                           (2, 31, 10, False), (1, 6, 32, False)])
+def test_wrapper_fits_views_x_groups_x_factors_past_the_lds_tile(monkeypatch, M, G, K, general):
+    """Dense fits whose Grams do not fit the two-pass sweeps' LDS tile (two_pass_fits: 2 views x 32 groups at 10
+    factors, 8 groups at 32, 3 views x 3 groups at 30) go to the general engine; the last fitting neighbours (31 groups
+    at 10 factors, 6 groups at 32 - the Z sweep's tile refuses 7) stay on the two-pass engine.  Either way the ELBO
+    follows the gaussian oracle iteration by iteration."""
+    import pandas as pd
+
+    from muon_amd._core import tools
+
+    chosen = []
+    spy = tools._needs_general_engine
+    monkeypatch.setattr(tools, "_needs_general_engine", lambda *a, **k: chosen.append(spy(*a, **k)) or chosen[-1])
+    rng = np.random.default_rng(9)
+    n = 600
+    Z = rng.standard_normal((n, 4))
+    ys = [Z @ rng.standard_normal((4, D)) + 0.5 * rng.standard_normal((n, D)) for D in (300, 100, 200)[:M]]
+    grp = rng.permutation(np.arange(n) % G)
+    ref = mofa_oracle.run(ys, groups=grp, n_factors=K, n_iterations=4, convergence_mode="slow", min_iterations=100)
+    md = MuData({f"v{m}": AnnData(y) for m, y in enumerate(ys)})
+    md.obs["grp"] = pd.Categorical([f"g{i:02d}" for i in grp])
+    for m in md.mod.values():
+        m.obs["grp"] = md.obs["grp"].values
+    mu.tl.mofa(md, n_factors=K, groups_label="grp", n_iterations=4, convergence_mode="slow", quiet=True)
+    assert chosen == [general]
+    assert md.obsm["X_mofa"].shape == (n, K)
     np.testing.assert_allclose(md.uns["mofa"]["elbo"][:4], ref["elbo"][:4], rtol=1e-8)
 
 

@@ -597,3 +597,72 @@ def test_intersection_write_back_by_name_or_by_the_reference_mask(monkeypatch):
     assert np.array_equal(np.isnan(x0).all(axis=1), ~mask) and np.array_equal(np.isnan(x1).all(axis=1), ~mask)
     np.testing.assert_allclose(x1[mask], np.stack([rows[c] for c in common]), atol=1e-12)  # sorted-order rows through the mask
     assert not np.allclose(x0[mask], x1[mask])                          # ... which is another placement here
+
+
+# ---- the two-pass engine's LDS tile: one predicate, the C checks, the dispatch -------------------------------------------
+def _boundary_grid():
+    """(M, G, K) for K = 1..32, M = 1..4 and G on both sides of the largest G every check accepts."""
+    from muon_amd._core.mofa_engine import LDS_TILE_BYTES
+
+    out = set()
+    for K in range(1, 33):
+        gw = LDS_TILE_BYTES // (8 * (K * K + K))
+        for M in (1, 2, 3, 4):
+            gz = LDS_TILE_BYTES // (8 * M * (K * K + 2 * K))
+            for g0 in (gw, gz):
+                out.update((M, G, K) for G in range(max(1, g0 - 1), g0 + 3))
+            out.add((M, 1, K))
+    return sorted(out)
+
+
+def test_two_pass_fits_is_the_kernels_argument_checks():
+    """two_pass_fits against the real argument checks of mu_mofa_update_w, mu_mofa_update_z and mu_mofa_tau_elbo (all
+    run before any HIP call: D = N = 0, null pointers), for both value types, around every boundary."""
+    from muon_amd import _ffi
+    from muon_amd._core.mofa_engine import two_pass_fits
+
+    lib = _ffi.lib()
+    n = None
+    grid = _boundary_grid()
+    assert sum(two_pass_fits(*c) for c in grid) and sum(not two_pass_fits(*c) for c in grid)
+    for M, G, K in grid:
+        for dt in (0, 1):  # f32, f64: the tiles are sized at 8 bytes per entry for both
+            rw = lib.mu_mofa_update_w(dt, 0, K, G, n, n, n, n, n, n, n, 1, n, n, n, n, n, n)
+            rt = lib.mu_mofa_tau_elbo(dt, 0, K, G, n, n, n, n, n, n, n, 1e-14, 1e-14, n, n, n, n, n)
+            rz = lib.mu_mofa_update_z(dt, 0, K, M, G, n, n, n, n, n, n, n, n, n, n, n)
+            assert rw in (0, -1) and rt in (0, -1) and rz in (0, -1)
+            assert rw == rt, (M, G, K)
+            assert (rw == 0) == (G * (K * K + K) * 8 <= 60000), (M, G, K)
+            assert two_pass_fits(M, G, K) == (rw == 0 and rt == 0 and rz == 0), (M, G, K, dt, rw, rt, rz)
+    # the corners of the issue's table
+    assert two_pass_fits(2, 31, 10) and not two_pass_fits(2, 32, 10)
+    assert two_pass_fits(1, 6, 32) and not two_pass_fits(1, 7, 32)  # (update_w alone would take 7 groups)
+    assert two_pass_fits(1, 3, 32) and not two_pass_fits(2, 4, 32)
+    assert not two_pass_fits(3, 3, 30) and not two_pass_fits(2, 1, 33) and not two_pass_fits(1, 1, 0)
+
+
+def test_two_pass_engine_refuses_a_model_past_the_tile_up_front():
+    rng = np.random.default_rng(0)
+    views = [rng.standard_normal((40, 6)), rng.standard_normal((40, 5))]
+    with pytest.raises(NotImplementedError, match="two_pass_fits"):
+        MofaEngine(BE, views, np.arange(40) % 32, 10)
+    MofaEngine(BE, views, np.arange(40) % 31, 10)
+
+
+@pytest.mark.parametrize("M,G,K,sparse,nan,general", [
+    (2, 31, 10, False, False, False), (2, 32, 10, False, False, True),
+    (1, 6, 32, False, False, False), (1, 7, 32, False, False, True), (1, 8, 32, False, False, True),
+    (3, 3, 30, False, False, True), (1, 1, 33, False, False, True),
+    (1, 6, 10, True, False, False), (1, 7, 10, True, False, True),  # 64 stacked columns against a sparse view
+    (1, 1, 10, False, True, True), (2, 1, 10, False, False, False)])
+def test_engine_choice(M, G, K, sparse, nan, general):
+    from muon_amd._core import tools
+
+    rng = np.random.default_rng(1)
+    views = [rng.standard_normal((70, 9)) for _ in range(M)]
+    if nan:
+        views[0][3, 2] = np.nan
+    if sparse:
+        views[0] = sp.csr_matrix(np.where(views[0] > 1, views[0], 0.0))
+    groups = np.arange(70) % G
+    assert tools._needs_general_engine(BE, views, ["gaussian"] * M, groups, K, False) == general
