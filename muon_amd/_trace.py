@@ -1,9 +1,10 @@
 """roctx ranges around the phases of the hot path (tracing / profiling).
 
 ``MUON_AMD_TRACE=1`` loads ``libroctx64.so`` (ROCm's marker library) and brackets the phases of ``tfidf_device`` and
-``lsi_device`` - and the iterations of the MOFA engines - with ``roctxRangePushA`` / ``roctxRangePop``, so that a
-``rocprofv3 --marker-trace --kernel-trace`` run shows which kernels belong to which phase.  Off (the default) it costs
-one attribute lookup per phase; a missing library turns it off with a warning instead of failing the call.
+``lsi_device`` with ``roctxRangePushA`` / ``roctxRangePop``, so that a ``rocprofv3 --marker-trace --kernel-trace`` run
+shows which kernels belong to which phase.  Every range is a ``with phase(...)`` block: it is closed however the block
+is left, an exception included.  Off (the default) it costs one attribute lookup per phase; a missing library turns it
+off with a warning instead of failing the call.
 """
 from __future__ import annotations
 
@@ -48,16 +49,3 @@ def phase(name: str):
     finally:
         _lib.roctxRangePop()
 
-
-def mark(name: str) -> None:
-    """Close the innermost open range of this module's stack and open ``name`` (phases that follow each other)."""
-    if _enabled():
-        if _depth[0] > 0:
-            _lib.roctxRangePop()
-            _depth[0] -= 1
-        if name:
-            _lib.roctxRangePushA(name.encode())
-            _depth[0] += 1
-
-
-_depth = [0]

@@ -508,11 +508,21 @@ def test_restarts_keep_more_when_k_sits_inside_a_cluster(monkeypatch):
     assert cnt[0] == cnt[1]
 
 
-def test_roctx_ranges_are_balanced_and_off_by_default(monkeypatch):
+def _rank20_small():
+    """300 cells, rank 20 (every cell a scaled copy of one of 20 base rows)."""
+    rng = np.random.default_rng(0)
+    base = sp.random(20, 200, density=0.2, random_state=rng, format="csr", dtype=np.float32)
+    X = (sp.diags((1 + rng.random(300)).astype(np.float32)) @ base[rng.integers(0, 20, 300)]).tocsr()
+    X.sort_indices()
+    return X
+
+
+def test_roctx_ranges_close_on_every_exit_and_are_off_by_default(monkeypatch):
     """MUON_AMD_TRACE=1 brackets the phases of tfidf / lsi with roctx ranges (muon_amd/_trace.py).  Off by
-    default; when on, every push has its pop - also when lsi leaves through its redo-on-host path - and the result is
-    the same."""
+    default; when on, every push has its pop - also when lsi leaves through its redo-on-host path and when it raises -
+    and the result is the same."""
     from muon_amd import _trace
+    from muon_amd._atac import tools
     from muon_amd._atac.tools import lsi_device
 
     X = planted_topics_csr(600, 400, n_topics=8, density=0.08, seed=11, dtype=np.float32)
@@ -533,14 +543,118 @@ def test_roctx_ranges_are_balanced_and_off_by_default(monkeypatch):
             calls.append(("pop", None))
             return 0
 
+    def balanced():
+        depth = 0
+        for kind, _ in calls:
+            depth += 1 if kind == "push" else -1
+            assert depth >= 0
+        return depth == 0
+
     monkeypatch.setattr(_trace, "_state", True)
     monkeypatch.setattr(_trace, "_lib", Fake())
-    monkeypatch.setattr(_trace, "_depth", [0])
     _, sd1, _, _ = lsi_device(BE, Xd, n_comps=8, return_info=True)
     names = [n for k, n in calls if k == "push"]
     assert names == ["lsi/operands", "lsi/warm_start", "lsi/krylov", "lsi/ritz_vectors"]
-    assert sum(k == "push" for k, _ in calls) == sum(k == "pop" for k, _ in calls) and _trace._depth[0] == 0
+    assert balanced()
     np.testing.assert_array_equal(sd0, sd1)
+
+    # the device-side Cholesky flags the exhausted Krylov space of a rank-20 matrix: the call is redone on the host path
+    R = _rank20_small()
+    Rd = BE.upload_csr(R.indptr, R.indices, R.data, R.shape)
+    redo = []
+    orig = tools._lsi_device
+    monkeypatch.setattr(tools, "_lsi_device", lambda *a, **k: (redo.append(k.get("device_qr")), orig(*a, **k))[1])
+    calls.clear()
+    lsi_device(BE, Rd, n_comps=30, device_qr=True)
+    assert redo == [True, False]
+    names = [n for k, n in calls if k == "push"]
+    assert names == ["lsi/operands", "lsi/warm_start", "lsi/krylov"] * 2 + ["lsi/ritz_vectors"]
+    assert balanced()
+    monkeypatch.setattr(tools, "_lsi_device", orig)
+
+    # an error out of the Krylov loop (here: the device -> host copy of the Grams) closes the open ranges as it leaves
+    class Failing(CpuTestBackend):
+        def fetch_async(self, tensors):
+            class _Lost:
+                def wait(self):
+                    raise RuntimeError("copy failed")
+
+            return _Lost()
+
+    calls.clear()
+    with pytest.raises(RuntimeError, match="copy failed"):
+        lsi_device(Failing(), Xd, n_comps=8)
+    assert [n for k, n in calls if k == "push"] == ["lsi/operands", "lsi/warm_start", "lsi/krylov"]
+    assert balanced()
+
+
+def test_lsi_stop_rule():
+    """tools._stop_rule, branch by branch: (stop, expect_final) from the Ritz values, this step's bound and the history."""
+    from muon_amd._atac.tools import _stop_rule
+
+    k = 3
+    lam_all = np.array([10.0, 8.0, 5.0, 1.0, 0.5])  # theta_k = 5, theta_out = 0.5: Chebyshev rate ~0.03
+    inf = np.inf
+
+    def rule(bound, bounds, gap=4.0, prev_sv=None, it=3, big=False):
+        return _stop_rule(lam_all, k, bound, list(bounds) + [bound], gap, prev_sv, it, 3e-5, 1e-7, big)
+
+    # the bound under angle_tol
+    assert rule(2e-5, [inf, 1e-2, 1e-3]) == (True, True)
+    assert rule(4e-5, [inf, 1e-2, 1e-3])[0] is False
+    # four expansions that bought < 30 %, below 1e-2: the f32 floor
+    assert rule(9e-4, [inf, 1e-3, 1e-3, 1e-3, 1e-3]) == (True, True)
+    assert rule(6e-4, [inf, 1e-3, 1e-3, 1e-3, 1e-3])[0] is False       # 40 % bought
+    assert rule(9e-4, [inf, 1e-3, 1e-3, 1e-3])[0] is False              # only three expansions
+    assert rule(2e-2, [inf, 2e-2, 2e-2, 2e-2, 2e-2])[0] is False        # a stall above 1e-2 goes on
+    # expect_final: the next step is predicted to pass (bound x rate < 100 angle_tol)
+    assert rule(1e-4, [inf, 1e-3]) == (False, True)                      # rate 0.1
+    assert rule(1e-2, [inf, 2e-2]) == (False, False)                     # rate 0.5
+    assert rule(1e-2, [inf]) == (False, False)                           # no rate yet: 0.5
+    # big products: stop speculating once the bound is under 1, whatever the rate
+    assert rule(0.5, [inf, 0.9], big=True) == (False, True)
+    assert rule(0.5, [inf, 0.9], big=False) == (False, False)
+    assert rule(1.5, [inf, 2.0], big=True) == (False, False)
+    assert rule(inf, [inf], big=True) == (False, False)
+    # no gap behind sigma_k: stop once the Ritz values have settled to tol (relative to theta_1)
+    settled = np.sqrt(lam_all[:k] * (1 + 1e-9))
+    moved = np.sqrt(lam_all[:k] * (1 + 1e-5))
+    assert rule(inf, [inf, inf], gap=0.0, prev_sv=settled) == (True, False)
+    assert rule(inf, [inf, inf], gap=0.0, prev_sv=moved) == (False, False)
+    assert rule(inf, [inf, inf], gap=0.0, prev_sv=settled, it=1)[0] is False   # too early
+    assert rule(inf, [inf], gap=0.0, prev_sv=None)[0] is False                 # nothing to compare with
+    assert rule(inf, [inf, inf], gap=1.0, prev_sv=settled)[0] is False          # a gap, just no bound yet
+
+
+def test_lsi_restart_growth_and_bound_rules():
+    """tools._restart_grows: the restarts keep one block more when the restart is due and the gap behind sigma_k is under
+    3 %; tools._ritz_bound: gap, Lanczos bound and f32 floor of a Ritz step."""
+    from muon_amd._atac.tools import _F32_EPS, _restart_grows, _ritz_bound
+
+    k, w = 50, 64
+    cluster = np.linspace(2.0, 1.0, 130)
+    cluster[k:] -= 0.001                          # theta_k - theta_k+1 ~ 0.8 % of theta_k
+    gapped = cluster.copy()
+    gapped[k:] -= 0.2                             # ~ 20 %
+    # m = 2 blocks of 64 with max_blocks 3: due with the early cap (restart after every block), not without it
+    assert _restart_grows(cluster, k, 2, w, 3, None)
+    assert not _restart_grows(cluster, k, 2, w, 3, 2)
+    assert _restart_grows(cluster, k, 3, w, 3, 2)
+    assert not _restart_grows(gapped, k, 2, w, 3, None)
+    assert not _restart_grows(cluster, k, 1, w, 3, None)        # not due yet
+    assert not _restart_grows(cluster, 70, 1, w, 2, None)       # one block of 64 cannot hold 71 vectors
+    assert not _restart_grows(np.zeros(130), k, 2, w, 3, None)  # nothing to grow for
+
+    rng = np.random.default_rng(0)
+    k, w = 3, 4
+    lam_all = np.array([9.0, 4.0, 2.0, 1.5, 0.5])
+    C = rng.standard_normal((2 * w, k))
+    gap, bound, floor = _ritz_bound(lam_all, C, k, w, 0.1)
+    want = np.sqrt(np.sum((0.1 * np.linalg.norm(C[w:], axis=0) / (lam_all[:k] - 1.5)) ** 2))
+    assert gap == 0.5 and bound == pytest.approx(want, rel=1e-15) and floor == pytest.approx(_F32_EPS * 9.0 / 0.5)
+    assert _ritz_bound(lam_all, C, k, w, 0.0) == (0.5, np.inf, floor)           # no expansion measured yet
+    assert _ritz_bound(np.array([9.0, 4.0, 2.0, 2.0]), C, k, w, 0.1)[:2] == (0.0, np.inf)   # no gap
+    assert _ritz_bound(lam_all, C[:3], k, w, 0.1) == (0.0, np.inf, np.inf)      # 3 basis vectors for k = 3
 
 
 def test_f64_input_is_answered_in_f64_arithmetic():
