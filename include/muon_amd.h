@@ -234,6 +234,25 @@ size_t mu_tpack4_err_offset(int64_t n_rows, int64_t n_cols, int64_t nnz);
  * inside every row of X^T - the table of mu_spmm_stream_ranges_f32 for the warm start's X_S^T Y_S */
 size_t mu_tpack4_cnt_offset(int64_t n_rows, int64_t n_cols, int64_t nnz);
 int mu_tpack4_phase_cycles(unsigned long long* h_out6, int reset);
+/* The table-driven fill of lsi's hot path (csrc/tperm.hip): X^T's row stream from the row stream of X, the same bytes as
+ * mu_tpack4_fill_stream writes, with every entry's staging slot and every row block's tile schedule taken from a plan
+ * that depends on the index arrays alone (tune "tperm_off" = 1 in the Python layer: the old fill).
+ *   The CSR must be canonical: column indices strictly increasing inside every row (mu_tpack4_* assume the same).
+ *   mu_tperm_plan, count pass (d_tile_off = NULL): d_ntile[n_blocks] <- tiles of every row block (n_blocks from
+ *     mu_tpack4_geometry; tile_cols = widest tile, 16 .. 512).  The caller scans them: d_tile_off[n_blocks + 1], [0] = 0.
+ *   mu_tperm_plan, record pass (d_tile_off given, same tile_cols): d_tiles[T + n_blocks] (T = d_tile_off[n_blocks]; block
+ *     g's tile boundaries at d_tile_off[g] + g, closed by n_cols), d_cont[16 T] (per tile and wave: the rows with a
+ *     continuation window), d_slots[nnz] (per pair of X's row stream - d_x_row_dst[r] = first pair of row r - its
+ *     slot in the staging buffer of its tile, < mu_tperm_stage_pairs()).
+ *   mu_tperm_fill: d_cdst[c] = first pair of column c's row in the target stream, d_cnt = the count pass' prefix table
+ *     (mu_tpack4_cnt_offset inside the work buffer of mu_tpack4_count); d_x_ent 256-byte aligned. */
+int mu_tperm_stage_pairs(void);
+int mu_tperm_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int32_t* d_indices,
+                  const int64_t* d_x_row_dst, int tile_cols, const int64_t* d_tile_off, int32_t* d_ntile,
+                  int32_t* d_tiles, uint32_t* d_cont, uint16_t* d_slots, void* stream);
+int mu_tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
+                  const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
+                  const int32_t* d_tiles, const uint32_t* d_cont, const uint16_t* d_slots, void* d_ent, void* stream);
 int mu_csr_stream_len(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr, int64_t* d_len,
                       void* stream);
 int mu_csr_stream_fill(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr,

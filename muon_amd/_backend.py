@@ -751,10 +751,18 @@ class HipBackend:
             if before_fill is not None:
                 before_fill()
             xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
+            tp = self._tperm_of(X, plan, xs_ent, xs_dst) if src is not None else None
             with self._dev_ctx():
-                check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                     _p(xs_dst), _p(xs_ent), _p(plan["sptr"]), _p(plan["inv"]), _p(ent),
-                                                     _p(plan["work"]), plan["wb"], self._stream()))
+                if tp is not None:
+                    # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
+                    cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
+                    check(self.lib.mu_tperm_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
+                                                 _p(tp["toff"]), _p(tp["tiles"]), _p(tp["cont"]), _p(tp["slots"]), _p(ent),
+                                                 self._stream()))
+                else:
+                    check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
+                                                         _p(xs_dst), _p(xs_ent), _p(plan["sptr"]), _p(plan["inv"]), _p(ent),
+                                                         _p(plan["work"]), plan["wb"], self._stream()))
             self._note_tpack4(plan["work"], n, d, X.nnz)
             return DeviceStream(plan["sptr"], ent, (d, n), X.nnz, plan["perm"], plan["K"], self._t4_prefix(plan["work"], n, d, X.nnz))
         if self._use_tpack4(X):
@@ -787,6 +795,51 @@ class HipBackend:
         if before_fill is not None:
             before_fill()
         return self.stream(self.transpose(X), sort_rows=sort_rows, K=K)
+
+    def _tperm_of(self, X: DeviceCSR, plan, xs_ent, xs_dst):
+        """The slot table of the table-driven fill (csrc/tperm.hip) for X's row stream as `xplan` lays it out, or None
+        (tune tperm_off = 1, a stream laid out otherwise, phase accounting asked for, no memory for the table: the fill of
+        csrc/tpack4.hip).  Made with the FIRST fill that can use it and kept on the transposition plan: it costs 2 bytes
+        per stored entry, which only lsi's operand building gets back - a TF-IDF-only caller never pays for it."""
+        import ctypes as C
+
+        lib = self.lib
+        if plan.get("tperm") is False:  # (no memory for the table when it was tried: the old fill from then on)
+            return None
+        xplan = self._plan_of(X, "xplan")
+        if (lib.mu_tune_get(b"tperm_off") == 1 or lib.mu_tune_get(b"tpack_dbg") > 0 or xplan is None
+                or xs_dst is not xplan["row_dst"] or xs_ent.data_ptr() % 256 != 0):
+            return None
+        n, d = X.shape
+        got = plan.get("tperm")
+        # (the widest tile follows the tune keys of t4_geometry: a table recorded under other keys is made again)
+        keys = (lib.mu_tune_get(b"tpack4_c"), lib.mu_tune_get(b"tpack4_m"))
+        if got is not None and got["keys"] == keys:
+            return got
+        rpb, G, Ct = C.c_int64(0), C.c_int(0), C.c_int(0)
+        check(lib.mu_tpack4_geometry(n, d, X.nnz, C.byref(rpb), C.byref(G), C.byref(Ct)))
+        G, Ct = int(G.value), min(int(Ct.value), 512)
+        try:
+            with self._dev_ctx():
+                st = self._stream()
+                ntile = self.empty((G,), torch.int32)
+                check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
+                                        None, st))
+                toff = torch.zeros((G + 1,), dtype=torch.int64, device=self.device)
+                toff[1:] = torch.cumsum(ntile.long(), 0)
+                T = int(toff[-1].item())
+                tiles = self.empty((T + G,), torch.int32)
+                cont = self.empty((16 * T,), torch.int32)
+                slots = self.empty((X.nnz,), torch.int16)
+                check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
+                                        _p(tiles), _p(cont), _p(slots), st))
+                inv = plan["inv"]
+                cdst = (plan["sptr"][inv.long()] if inv is not None else plan["sptr"][:d]).contiguous()
+        except (RuntimeError, MemoryError):  # (torch's out-of-memory errors and a refused launch are RuntimeErrors)
+            plan["tperm"] = False
+            return None
+        plan["tperm"] = dict(keys=keys, tile_cols=Ct, toff=toff, tiles=tiles, cont=cont, slots=slots, cdst=cdst, n_tiles=T)
+        return plan["tperm"]
 
     def _t4_geometry(self, n, d, nnz):
         import ctypes as C

@@ -81,6 +81,9 @@ SIGNATURES = {
     "mu_csr_slice_stream": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_spmm_stream_ranges_f32": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp]),
     "mu_tpack4_cnt_offset": (_sz, [_i64, _i64, _i64]),
+    "mu_tperm_stage_pairs": (C.c_int, []),
+    "mu_tperm_plan": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mu_tperm_fill": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_spmm_ell16_waves": (C.c_int, [_i64]),
     "mu_dense_col_moments_chunks": (C.c_int, [_i64, _i64]),
     "mu_dense_col_moments": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),

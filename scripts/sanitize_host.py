@@ -106,10 +106,20 @@ def drive(path):
         lib.mu_csr_slice_stream(40, P, P, P, P, i64(10), P, P, P, P, P, P, P, None),                     # 40 ranges
         lib.mu_tpack4_count(i64(0), i64(10), i64(5), P, P, P, P, sz(0), None, None),                     # unsupported shape
         lib.mu_tpack4_fill_stream(i64(100), i64(10), i64(50), P, None, None, None, None, P, None, P, P, sz(1), None),  # no source
+        lib.mu_tperm_plan(i64(0), i64(10), i64(5), P, P, None, 64, None, P, None, None, None, None),     # unsupported shape
+        lib.mu_tperm_plan(i64(100), i64(10), i64(50), P, None, None, 64, None, P, None, None, None, None),  # no index array
+        lib.mu_tperm_plan(i64(100), i64(10), i64(50), P, P, None, 8, None, P, None, None, None, None),   # tile_cols < 16
+        lib.mu_tperm_plan(i64(100), i64(10), i64(50), P, P, None, 513, None, P, None, None, None, None), # tile_cols > 512
+        lib.mu_tperm_plan(i64(100), i64(10), i64(50), P, P, None, 64, None, None, None, None, None, None),  # count pass without d_ntile
+        lib.mu_tperm_plan(i64(100), i64(10), i64(50), P, P, None, 64, P, None, P, P, P, None),           # record pass without row_dst
+        lib.mu_tperm_fill(i64(0), i64(10), i64(5), P, P, P, P, P, P, P, P, P, P, None),                  # unsupported shape
+        lib.mu_tperm_fill(i64(100), i64(10), i64(50), P, P, P, P, P, P, P, P, None, P, None),            # no slot table
+        lib.mu_tperm_fill(i64(100), i64(10), i64(50), P, P, C.c_void_p(C.addressof(one) | 8), P, P, P, P, P, P, P, None),  # stream not 256-byte aligned
         lib.mu_mofa_update_w(0, i64(10), 40, 1, P, P, P, P, P, P, P, 1, P, P, P, P, P, None),           # K > 32
         lib.mu_mofa_update_w(7, i64(10), 4, 1, P, P, P, P, P, P, P, 1, P, P, P, P, P, None),            # bad dtype
     ]
     assert all(rc != 0 for rc in bad), bad
+    assert 0 < lib.mu_tperm_stage_pairs() < (1 << 16)  # (a staging slot is 16 bits of the table)
     # one descending range: h[1] < h[0]
     h = (C.c_int32 * 5)(512, 256, 0, 0, 1)
     assert lib.mu_spmm_stream_ranges_f32(i64(10), P, P, None, 4, P, i64(10), P, i64(0), P, i64(10), 1, h, 1, None) != 0
