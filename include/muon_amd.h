@@ -602,6 +602,33 @@ int mu_mofa_z_sums(int dtype, int64_t n0, int64_t n1, int K, const void* d_EZ2, 
 int mu_mofa_z_elbo(int dtype, int K, int G, int ard, const double* d_zs, const double* d_Ng, double a0,
                    double b0, void* d_alpha_z, void* d_lalpha_z, double* d_elbo, void* stream);
 
+/* ---- muon.prot.pp.dsb (/root/reference/muon/_prot/preproc.py:161-198; csrc/prot.hip, C-ABI v700) ---------------------
+ * mu_prot_max_proteins(): the widest panel the CSR moments kernel and the fit kernel take (1024: 16 values per lane).
+ *
+ * Log-moments of the empty droplets: d_mean[j], d_std[j] (ddof = 1) of log(x + pseudocount) over the n rows, f64, from
+ * the CSR as it is (canonical rows: sorted, no duplicates) or from a dense row-major matrix.  Zeros are accounted for in
+ * closed form, the sums are centred on log(pseudocount) (> 0 required; 0 is the caller's dense two-pass expression).
+ * dtype f32: the logarithm is rounded to f32 first, as numpy does for a float32 matrix.  d_work: mu_prot_moments_worksize
+ * bytes (partial sums of fixed row ranges, added in order: two runs agree bit for bit). */
+int mu_prot_max_proteins(void);
+size_t mu_prot_moments_worksize(int64_t n, int64_t d);
+int mu_prot_log_moments_csr(int dtype, int64_t n, int64_t d, const int64_t* d_indptr, const int32_t* d_indices,
+                            const void* d_values, double pseudocount, double* d_mean, double* d_std, void* d_work,
+                            size_t work_bytes, void* stream);
+int mu_prot_log_moments_dense(int dtype, int64_t n, int64_t d, const void* d_X, double pseudocount, double* d_mean,
+                              double* d_std, void* d_work, size_t work_bytes, void* stream);
+/* The per-cell fit, one wave per cell: the row (d_X dense [n x d], or d_X = NULL and a CSR) becomes
+ * (log(x + pseudocount) - mean_j) / std_j (d_std NULL: no division; dtype f32: rounded to f32 where numpy does), is
+ * written to d_scaled [n x d] f64, and gets scikit-learn's 2-component GaussianMixture EM (init_params "random", tol 1e-3,
+ * reg_covar 1e-6, max_iter 100) for covariance_type "tied" and "full" in f64.  d_resp: the uniform draws [d x 2] of the
+ * initial responsibilities of cell c and model m (0 tied, 1 full) at d_resp + c * resp_cell_stride + m * resp_model_stride
+ * (doubles; both 0: one matrix for every fit, what an integer random_state means).  Out: d_bgmean [n] = the smaller
+ * component mean of the model with the lower BIC, d_bic [n x 2], d_niter [n x 2] (n_iter_).  1 <= d <= 1024. */
+int mu_prot_dsb_fit(int dtype, int64_t n, int64_t d, const void* d_X, const int64_t* d_indptr, const int32_t* d_indices,
+                    const void* d_values, double pseudocount, const double* d_mean, const double* d_std,
+                    const double* d_resp, int64_t resp_cell_stride, int64_t resp_model_stride, double* d_scaled,
+                    double* d_bgmean, double* d_bic, int32_t* d_niter, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

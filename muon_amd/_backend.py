@@ -1392,6 +1392,57 @@ class HipBackend:
                                                _p(X.indices), _p(X.values), _p(out), self._stream()))
         return out
 
+    # -- muon.prot.pp.dsb (csrc/prot.hip; muon_amd/_prot/preproc.py tests for these with hasattr) ---------------------
+    def prot_max_proteins(self) -> int:
+        """The widest protein panel the two kernels below take (wider panels: the tensor formulation)."""
+        return int(self.lib.mu_prot_max_proteins())
+
+    def prot_log_moments(self, X, pseudocount: float):
+        """(mean, std with ddof = 1) per column of log(X + pseudocount), f64 (include/muon_amd.h).  X: a DeviceCSR as it
+        is (no densifying) or a dense [n, d] tensor, f32 / f64; pseudocount > 0."""
+        n, d = (int(s) for s in X.shape)
+        mean, std = self.empty((d,), torch.float64), self.empty((d,), torch.float64)
+        wb = int(self.lib.mu_prot_moments_worksize(n, d))
+        work = self.empty((max(wb, 8),), torch.uint8)
+        with self._dev_ctx():
+            if isinstance(X, DeviceCSR):
+                check(self.lib.mu_prot_log_moments_csr(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values),
+                                                       float(pseudocount), _p(mean), _p(std), _p(work), wb, self._stream()))
+            else:
+                assert X.is_contiguous()
+                check(self.lib.mu_prot_log_moments_dense(_dt(X), n, d, _p(X), float(pseudocount), _p(mean), _p(std),
+                                                         _p(work), wb, self._stream()))
+        return mean, std
+
+    def prot_dsb_fit(self, X, pseudocount: float, mean, std, resp):
+        """Scaled rows and the two Gaussian-mixture fits of every cell, a wave per cell (include/muon_amd.h).
+        ``resp``: uniform draws, [d, 2] (one matrix for every fit) or [n, 2, d, 2] (cell, tied | full); ``std`` None =
+        mean_subtract.  Returns (scaled [n, d] f64, bgmean [n], bic [n, 2], n_iter [n, 2] int32)."""
+        n, d = (int(s) for s in X.shape)
+        assert mean.dtype == torch.float64 and mean.numel() == d and resp.dtype == torch.float64 and resp.is_contiguous()
+        assert std is None or (std.dtype == torch.float64 and std.numel() == d)
+        if resp.dim() == 2:
+            assert tuple(resp.shape) == (d, 2)
+            cs = ms = 0
+        else:
+            assert tuple(resp.shape) == (n, 2, d, 2)
+            cs, ms = 4 * d, 2 * d
+        scaled = self.empty((n, d), torch.float64)
+        bg = self.empty((n,), torch.float64)
+        bic = self.empty((n, 2), torch.float64)
+        niter = self.empty((n, 2), torch.int32)
+        with self._dev_ctx():
+            if isinstance(X, DeviceCSR):
+                check(self.lib.mu_prot_dsb_fit(_dt(X.values), n, d, None, _p(X.indptr), _p(X.indices), _p(X.values),
+                                               float(pseudocount), _p(mean), _p(std), _p(resp), cs, ms, _p(scaled), _p(bg),
+                                               _p(bic), _p(niter), self._stream()))
+            else:
+                assert X.is_contiguous()
+                check(self.lib.mu_prot_dsb_fit(_dt(X), n, d, _p(X), None, None, None, float(pseudocount), _p(mean),
+                                               _p(std), _p(resp), cs, ms, _p(scaled), _p(bg), _p(bic), _p(niter),
+                                               self._stream()))
+        return scaled, bg, bic, niter
+
     def mofa_jaakkola(self, zeta, a, b):
         """Bernoulli pseudo-data precision 2 lambda(xi), xi^2 = zeta^2 + a - b, written over ``a``."""
         assert zeta.is_contiguous() and a.is_contiguous() and b.is_contiguous() and a.shape == zeta.shape == b.shape

@@ -249,6 +249,11 @@ class MuData:
     def __getitem__(self, key):
         if isinstance(key, str) and key in self.mod:
             return self.mod[key]
+        if isinstance(key, tuple):
+            # mdata[obs_names, :] (muon.prot.pp.dsb, /root/reference/muon/_prot/preproc.py:92): all variables only
+            if len(key) != 2 or not (isinstance(key[1], slice) and key[1] == slice(None)):
+                raise NotImplementedError("MuData(duck)[obs, var]: only `:` is supported for the variables")
+            key = key[0]
         names = pd.Index(np.asarray(key).reshape(-1))
         sub = {}
         for m, a in self.mod.items():

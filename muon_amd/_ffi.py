@@ -138,6 +138,12 @@ SIGNATURES = {
     "mu_mofa_w_elbo": (C.c_int, [_i32, _i64, _i32, _i32, _i32] + [_vp] * 3 + [_dbl] * 5 + [_vp] * 7),
     "mu_mofa_z_sums": (C.c_int, [_i32, _i64, _i64, _i32] + [_vp] * 5),
     "mu_mofa_z_elbo": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _dbl, _dbl] + [_vp] * 4),
+    "mu_prot_max_proteins": (C.c_int, []),
+    "mu_prot_moments_worksize": (_sz, [_i64, _i64]),
+    "mu_prot_log_moments_csr": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "mu_prot_log_moments_dense": (C.c_int, [_i32, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "mu_prot_dsb_fit": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                  _vp, _vp]),
     "mu_synth_row_nnz": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp]),
     "mu_synth_fill": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp, _vp, _vp]),
 }
