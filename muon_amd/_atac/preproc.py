@@ -351,7 +351,7 @@ def upload_canonical(backend, counts, values_dtype=None):
 
         X = backend.upload_csr(host.indptr, host.indices, host.data, host.shape, values_dtype=values_dtype,
                                slab_ptr=False)
-        if getattr(canonicalize(backend, X), "canonical_as_given", False):
+        if canonicalize(backend, X).canonical_as_given:
             host.has_canonical_format = True  # (verified entry by entry on the device: scipy need not scan it again)
             return host, backend.with_slab_ptr(X)
         del X  # unsorted rows or duplicates: the host route (it copies, sorts and sums like scipy)
@@ -390,35 +390,44 @@ def tfidf_device(backend, X, n_obs, flags: int, scale: float, comm=None, out=Non
     from .._trace import phase
 
     comm = default_comm(comm)
+    # HipBackend's sweeps hand the slab pointers they search from the sum pass to the scale pass and on to the result
+    # (`keep_work`, `work`); other operator sets (CPU tests) have the plain forms only
+    hands_on = hasattr(backend, "slab_ptr_from_work")
+    work = None
     with phase("tfidf/sums"):
-        rowsum, colsum = backend.row_col_sums(X)
+        if hands_on:
+            rowsum, colsum, work = backend.row_col_sums(X, keep_work=True)  # (work None: X came with its table)
+        else:
+            rowsum, colsum = backend.row_col_sums(X)
         comm.all_reduce_sum(colsum)
         idf = backend.idf(colsum, float(n_obs), flags, X.values.dtype)
     # r05: the scale sweep also writes the ROW STREAM of the result - the operand layout of lsi's products - while it has
     # every entry in registers (the layout needs the row lengths only); lsi then skips its streaming copy of X and
     # transposes from the stream.  Operator sets without the kernel (CPU tests) simply do not offer it.
-    emit = None
+    emit = sp = None
+    kw = {} if work is None else {"work": work}
     can = getattr(backend, "can_emit_stream", None)
     with phase("tfidf/scale"):
         if emit_stream and can is not None and can(X):
-            emit = backend.stream_layout(X)
-            vals, zero_count = backend.tfidf_scale(X, rowsum, idf, scale, flags, out=out, emit=emit)
-        else:
-            vals, zero_count = backend.tfidf_scale(X, rowsum, idf, scale, flags, out=out)
+            emit = kw["emit"] = backend.stream_layout(X)
+        vals, zero_count = backend.tfidf_scale(X, rowsum, idf, scale, flags, out=out, **kw)
+        if work is not None:
+            sp = backend.slab_ptr_from_work(X, work)
+        del work, kw  # (the work buffer dies with the scale sweep)
     res = X.with_values(vals)
-    take = getattr(backend, "take_slab_ptr", None)  # (a method: wrappers of the backend forward it)
-    sp = take() if take is not None else None
     if int(zero_count.item()) != 0:
         # scipy's SpGEMM drops entries whose product is exactly 0
         res = backend.compact_nonzero(res)
     else:
-        # the result shares X's index arrays: the slab pointers the sweeps searched go with it, lsi's transposition
-        # cuts the same 8192-column slabs (csrc/tpack4.hip) and does not search them again
-        if sp is not None and getattr(res, "slab_ptr", None) is None:  # (else: X came with its table, `with_values` kept it)
-            res.slab_ptr = (sp, (res.indptr.data_ptr(), res.indices.data_ptr(), res.shape[0], res.shape[1]))
-        if emit is not None:  # (keyed by the arrays it mirrors: a result whose zeros were compacted has no stream)
-            res.xstream = (emit[0], emit[1], (res.indptr.data_ptr(), res.indices.data_ptr(), res.values.data_ptr(),
-                                              res.shape[0], res.shape[1], res.nnz))
+        # the result shares X's index arrays: the slab pointers the sweeps searched go with it (with the result only: X
+        # keeps searching), lsi's transposition cuts the same 8192-column slabs (csrc/tpack4.hip) and does not search
+        # them again.  (sp None: X came with its table, `with_values` handed it on.)
+        if sp is not None:
+            from .._backend import CsrPlans
+
+            res.plans = CsrPlans(CsrPlans.key_of(res), slab_ptr=sp)
+        if emit is not None:  # (mirrors these arrays: a result whose zeros were compacted has no stream)
+            res.xstream = (emit[0], emit[1], res.values.data_ptr())
     return res
 
 

@@ -467,8 +467,7 @@ def _warm_start(backend, comm, Xcsr, Xt, B, w, seed, start, adaptive, n_obs, nnz
         Ss = backend.slice_stream(Xcsr, wplan)
     elif n_s > 0:
         Ss, St, n_s = _operands_slice(backend, Xcsr, n_s)
-        take = getattr(backend, "take_tpack4_err", None)
-        e2 = take() if (Ss is not None and take is not None) else None  # (the slice's transposition is checked with the shard's)
+        e2 = getattr(St, "t4_err", None)  # (the slice's transposition is checked with the shard's)
         if e2 is not None:
             t4_err = e2 if t4_err is None else (t4_err | e2)
     for _ in range(qsteps):
@@ -843,8 +842,7 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
     with phase("lsi/operands"):
         if pack:
             X, Xt = backend.stream_both(X)
-            take = getattr(backend, "take_tpack4_err", None)
-            t4_err = take() if take is not None else None  # (read with the first Gram fetch: no synchronisation of its own)
+            t4_err = getattr(Xt, "t4_err", None)  # (read with the first Gram fetch: no synchronisation of its own)
         elif Xt is None:
             Xt = backend.transpose(X)
 

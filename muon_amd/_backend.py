@@ -22,7 +22,33 @@ from . import _ffi
 from ._ffi import F32, F64, check
 
 
-@dataclass
+@dataclass(slots=True)
+class CsrPlans:
+    """What the backend derives from the INDEX ARRAYS of a device CSR alone, keyed once by the arrays it describes.
+    Every CSR that shares those arrays (``with_values``) shares this object; a CSR with other arrays (compacted zeros,
+    a transposition) has none of it."""
+
+    key: tuple                                # key_of() of the arrays described
+    slab_ptr: Optional[torch.Tensor] = None   # include/muon_amd.h mu_csr_slab_ptr
+    xplan: Optional[dict] = None              # where the rows go in the row stream of X (HipBackend._make_xplan)
+    # the transposition's count phase and the layout of X^T's stream (_make_tplan); its "tperm" entry, once a fill has
+    # asked for it (_tperm_of): the slot table of the table-driven fill, or False = tried, no memory
+    tplan: Optional[dict] = None
+    wplan: Optional[tuple] = None             # (the warm start's slice plan, (n_s, max_ranges))
+
+    @staticmethod
+    def key_of(X: "DeviceCSR") -> tuple:
+        n, d = X.shape
+        return (X.indptr.data_ptr(), X.indices.data_ptr(), n, d, X.nnz)
+
+    @staticmethod
+    def of(X: "DeviceCSR") -> Optional["CsrPlans"]:
+        """X's plans if they describe X's index arrays as they are (the one validity rule)."""
+        plans = X.plans
+        return plans if plans is not None and plans.key == CsrPlans.key_of(X) else None
+
+
+@dataclass(slots=True)
 class DeviceCSR:
     """CSR resident in HBM: indptr int64[n+1], indices int32[nnz], values f32|f64[nnz]."""
 
@@ -30,6 +56,11 @@ class DeviceCSR:
     indices: torch.Tensor
     values: torch.Tensor
     shape: Tuple[int, int]
+    plans: Optional[CsrPlans] = None
+    # (row stream of this CSR, row_dst, values.data_ptr()) as the TF-IDF scale sweep wrote it: apart from `plans`
+    # because it mirrors the values too
+    xstream: Optional[tuple] = None
+    canonical_as_given: bool = False  # _core.io.canonicalize: the arrays were canonical as they came
 
     @property
     def nnz(self) -> int:
@@ -40,12 +71,9 @@ class DeviceCSR:
         return self.values.dtype
 
     def with_values(self, values: torch.Tensor) -> "DeviceCSR":
-        out = DeviceCSR(self.indptr, self.indices, values, self.shape)
-        for name in ("slab_ptr", "xplan", "tplan", "wplan"):  # (they describe the index arrays, which the new object shares)
-            got = getattr(self, name, None)
-            if got is not None:
-                setattr(out, name, got)
-        return out
+        # (the plans describe the index arrays, which the new object shares: by reference, so that a plan made through
+        #  either object serves both)
+        return DeviceCSR(self.indptr, self.indices, values, self.shape, plans=self.plans)
 
 
 @dataclass
@@ -64,6 +92,8 @@ class DeviceStream:
     # fourth-generation transposition only: the count pass' prefix table (uint32 [(blocks + 1), rows of this stream]: entries
     # of a row in the source's row blocks before g) and the rows per block - what a ranged product on this stream reads
     t4: Optional[dict] = None
+    # ... and the device int32[1] copy of the fill's error word, queued behind the fill (HipBackend.raise_tpack4)
+    t4_err: Optional[torch.Tensor] = None
 
     @property
     def n_pos(self) -> int:
@@ -129,6 +159,10 @@ def _dt(t: torch.Tensor) -> int:
 
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def _n_slab_ptr(n: int, d: int) -> int:
+    return n * (-(-d // 8192) + 1)
 
 
 def pick_block(width: int) -> int:
@@ -409,10 +443,10 @@ class HipBackend:
         n, d = X.shape
         if n == 0 or d == 0 or X.nnz == 0 or self._slab_ptr_of(X) is not None:
             return X
-        sp = self.empty((n * (-(-d // 8192) + 1),), torch.int64)
+        sp = self.empty((_n_slab_ptr(n, d),), torch.int64)
         with self._dev_ctx():
             check(self.lib.mu_csr_slab_ptr(n, d, _p(X.indptr), _p(X.indices), _p(sp), self._stream()))
-        X.slab_ptr = (sp, (X.indptr.data_ptr(), X.indices.data_ptr(), n, d))
+        X.plans = CsrPlans(CsrPlans.key_of(X), slab_ptr=sp)
         return self.with_plans(X)
 
     def with_plans(self, X: DeviceCSR) -> DeviceCSR:
@@ -425,48 +459,57 @@ class HipBackend:
         n, d = X.shape
         if n == 0 or d == 0 or X.nnz == 0:
             return X
-        if getattr(X, "xplan", None) is None:
-            lens = X.indptr[1:] - X.indptr[:-1]
-            perm, inv, K = self.launch_layout(lens, None)
-            plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
-            plens[inv.long()] = lens
-            with self._dev_ctx():
-                try:
-                    sptr = self._stream_sptr(plens, K)
-                except NotImplementedError:
-                    return X
-            X.xplan = (dict(perm=perm, inv=inv, K=K, sptr=sptr, row_dst=sptr[inv.long()].contiguous()),
-                       (X.indptr.data_ptr(), n, d))
-        if getattr(X, "tplan", None) is None and self._use_tpack4(X):
-            col_nnz = self.empty((d,), torch.int64)
-            wb = int(self.lib.mu_tpack4_worksize(n, d, X.nnz))
-            work = self.empty((wb,), torch.uint8)
-            with self._dev_ctx():
-                check(self.lib.mu_tpack4_count(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(col_nnz), _p(work), wb,
-                                               _p(self._slab_ptr_of(X)), self._stream()))
-                perm, inv, K = self.launch_layout(col_nnz, None)
-                plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
-                plens[inv.long()] = col_nnz
-                try:
-                    sptr = self._stream_sptr(plens, K)
-                except NotImplementedError:
-                    return X
-            X.tplan = (dict(work=work, wb=wb, perm=perm, inv=inv, K=K, sptr=sptr),
-                       (X.indptr.data_ptr(), X.indices.data_ptr(), n, d, X.nnz))
+        plans = CsrPlans.of(X)
+        if plans is None:
+            plans = X.plans = CsrPlans(CsrPlans.key_of(X))
+        try:
+            if plans.xplan is None:
+                plans.xplan = self._make_xplan(X, None)
+            if plans.tplan is None and self._use_tpack4(X):
+                plans.tplan = self._make_tplan(X, None, True)
+        except NotImplementedError:  # (_stream_sptr: a layout the stream SpMM does not take - X goes without the plan)
+            pass
         return X
+
+    def _make_xplan(self, X: DeviceCSR, K: Optional[int]) -> dict:
+        """Where the rows of X go in its row stream: launch_layout of the row lengths, scanned."""
+        lens = X.indptr[1:] - X.indptr[:-1]
+        perm, inv, K = self.launch_layout(lens, K)
+        plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
+        plens[inv.long()] = lens
+        sptr = self._stream_sptr(plens, K)
+        return dict(perm=perm, inv=inv, K=K, sptr=sptr, row_dst=sptr[inv.long()].contiguous())
+
+    def _make_tplan(self, X: DeviceCSR, K: Optional[int], sort_rows: bool) -> dict:
+        """The count phase of the tile-staged transposition of X (csrc/tpack4.hip) and the layout of X^T's row stream."""
+        n, d = X.shape
+        col_nnz = self.empty((max(d, 1),), torch.int64)
+        wb = int(self.lib.mu_tpack4_worksize(n, d, X.nnz))
+        work = self.empty((wb,), torch.uint8)
+        with self._dev_ctx():
+            check(self.lib.mu_tpack4_count(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(col_nnz), _p(work), wb,
+                                           _p(self._slab_ptr_of(X)), self._stream()))
+            lens = col_nnz[:d]
+            if sort_rows and d > 0:
+                perm, inv, K = self.launch_layout(lens, K)
+                plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
+                plens[inv.long()] = lens
+            else:
+                perm, inv, K, plens = None, None, max(1, int(K or self.lib.mu_spmm_stream_k(d))), lens
+            sptr = self._stream_sptr(plens, K)
+        return dict(work=work, wb=wb, perm=perm, inv=inv, K=K, sptr=sptr)
 
     @staticmethod
     def _plan_of(X: DeviceCSR, name: str):
-        got = getattr(X, name, None)
-        if got is None:
-            return None
-        plan, key = got
-        n, d = X.shape
-        want = (X.indptr.data_ptr(), n, d) if name == "xplan" else (X.indptr.data_ptr(), X.indices.data_ptr(), n, d, X.nnz)
-        return plan if key == want else None
+        """Field ``name`` of X's plans (None: not made, or the plans describe other arrays)."""
+        plans = CsrPlans.of(X)
+        return None if plans is None else getattr(plans, name)
 
     # -- TF-IDF (reference preproc.py:92-117) -----------------------------------------
-    def row_col_sums(self, X: DeviceCSR):
+    def row_col_sums(self, X: DeviceCSR, keep_work: bool = False):
+        """(row sums, column sums), f64.  ``keep_work``: also the sweep's work buffer, whose head holds the slab pointers
+        the sweep searched - what ``tfidf_scale(work=)`` of the SAME matrix then does not search again (None when X
+        brought its own table: nothing was searched)."""
         n, d = X.shape
         rowsum = self.empty((n,), torch.float64)
         colsum = self.empty((d,), torch.float64)
@@ -477,9 +520,8 @@ class HipBackend:
             check(self.lib.mu_csr_row_col_sums_sp(_dt(X.values), n, d, _p(X.indptr), _p(X.indices),
                                                   _p(X.values), _p(rowsum), _p(colsum), _p(work), wb, _p(sp),
                                                   self._stream()))
-        if sp is None:
-            # the slab pointers at the head of `work` serve the scale pass of the same matrix
-            self._sweep_work = (work, wb, (X.indptr.data_ptr(), X.indices.data_ptr(), n, d))
+        if keep_work:
+            return rowsum, colsum, (work if sp is None else None)
         return rowsum, colsum
 
     def idf(self, colsum: torch.Tensor, n_obs: float, flags: int, dtype) -> torch.Tensor:
@@ -500,88 +542,68 @@ class HipBackend:
         the values exist) and an empty stream to fill: (DeviceStream, row_dst) with row_dst[r] = pair index of row r's
         first pair."""
         n, d = X.shape
-        plan = self._plan_of(X, "xplan") if K is None else None
-        if plan is not None:  # (made with the device CSR: with_plans)
-            ent = self.empty((max(X.nnz, 1),), torch.int64)
-            return DeviceStream(plan["sptr"], ent, (n, d), X.nnz, plan["perm"], plan["K"]), plan["row_dst"]
-        lens = X.indptr[1:] - X.indptr[:-1]
-        perm, inv, K = self.launch_layout(lens, K)
-        n_pos = int(perm.numel())
-        plens = torch.zeros((n_pos,), dtype=torch.int64, device=self.device)
-        plens[inv.long()] = lens
-        with self._dev_ctx():
-            sptr = self._stream_sptr(plens, K)
+        plan = (self._plan_of(X, "xplan") if K is None else None) or self._make_xplan(X, K)
         ent = self.empty((max(X.nnz, 1),), torch.int64)
-        row_dst = sptr[inv.long()].contiguous()
-        return DeviceStream(sptr, ent, (n, d), X.nnz, perm, K), row_dst
+        return DeviceStream(plan["sptr"], ent, (n, d), X.nnz, plan["perm"], plan["K"]), plan["row_dst"]
 
     @staticmethod
     def _xstream_of(X: DeviceCSR):
         """(row stream, row_dst) the TF-IDF scale sweep left with X, if they describe X's arrays as they are."""
-        got = getattr(X, "xstream", None)
-        if got is None:
+        got = X.xstream
+        if got is None or CsrPlans.of(X) is None or got[2] != X.values.data_ptr():
             return None
-        xs, row_dst, key = got
-        n, d = X.shape
-        if key != (X.indptr.data_ptr(), X.indices.data_ptr(), X.values.data_ptr(), n, d, X.nnz):
-            return None
-        return xs, row_dst
+        return got[0], got[1]
 
-    def tfidf_scale(self, X: DeviceCSR, rowsum, idf, scale: float, flags: int, out=None, emit=None):
-        """``emit`` = (DeviceStream, row_dst) from stream_layout: the sweep also writes the result's row stream."""
+    def tfidf_scale(self, X: DeviceCSR, rowsum, idf, scale: float, flags: int, out=None, emit=None, work=None,
+                    gather: bool = False):
+        """``emit`` = (DeviceStream, row_dst) from stream_layout: the sweep also writes the result's row stream.
+        ``work``: what ``row_col_sums(X, keep_work=True)`` of the same X returned - the slab pointers at its head are
+        read instead of searched again.  ``gather``: the per-lane gather kernel (comparison / tests)."""
         if out is None:
             out = torch.empty_like(X.values)
         zc = self.zeros((1,), torch.int64)
         n, d = X.shape
-        kept = self.__dict__.pop("_sweep_work", None)
-        key = (X.indptr.data_ptr(), X.indices.data_ptr(), n, d)
         sp = self._slab_ptr_of(X)
-        if emit is not None:
-            assert X.values.dtype == torch.float32
-            have = kept is not None and kept[2] == key
-            work, wb = None, 0
-            if sp is None:
-                if have:
-                    work, wb = kept[0], kept[1]
-                else:
-                    wb = int(self.lib.mu_csr_row_col_sums_worksize(n, d))
-                    work = self.empty((wb,), torch.uint8)
+        if emit is None and (gather or sp is not None):
             with self._dev_ctx():
+                if gather:
+                    check(self.lib.mu_tfidf_scale(_dt(X.values), n, _p(X.indptr), _p(X.indices),
+                                                  _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
+                                                  _p(out), _p(zc), self._stream()))
+                else:
+                    check(self.lib.mu_tfidf_scale_sweep_sp(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values),
+                                                           _p(rowsum), _p(idf), float(scale), flags, _p(out), _p(zc), _p(sp),
+                                                           self._stream()))
+            return out, zc
+        # the sweeps that search the slab pointers into the head of a work buffer, or find them there (`have`)
+        have, wb = False, 0
+        if sp is not None:
+            work = None
+        else:
+            have, wb = work is not None, int(self.lib.mu_csr_row_col_sums_worksize(n, d))
+            if not have:
+                work = self.empty((wb,), torch.uint8)
+            elif work.numel() != wb:
+                raise ValueError("tfidf_scale(work=): not the work buffer of a sum sweep of this matrix")
+        with self._dev_ctx():
+            if emit is not None:
+                assert X.values.dtype == torch.float32
                 check(self.lib.mu_tfidf_scale_sweep_stream(n, d, _p(X.indptr), _p(X.indices), _p(X.values), _p(rowsum),
                                                            _p(idf), float(scale), flags, _p(out), _p(zc), _p(work), wb,
                                                            int(have), _p(sp), _p(emit[1]), _p(emit[0].ent),
                                                            self._stream()))
-            if sp is None:
-                n_sp = n * (-(-d // 8192) + 1)
-                self._last_slab_ptr = work[:8 * n_sp].view(torch.int64).clone()
-            return out, zc
-        if sp is not None and not self.__dict__.get("_scale_gather"):
-            with self._dev_ctx():
-                check(self.lib.mu_tfidf_scale_sweep_sp(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                       _p(rowsum), _p(idf), float(scale), flags, _p(out), _p(zc), _p(sp),
-                                                       self._stream()))
-            return out, zc
-        with self._dev_ctx():
-            if self.__dict__.get("_scale_gather"):  # comparison / tests: the per-lane gather kernel
-                check(self.lib.mu_tfidf_scale(_dt(X.values), n, _p(X.indptr), _p(X.indices),
-                                              _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
-                                              _p(out), _p(zc), self._stream()))
-                return out, zc
-            have = kept is not None and kept[2] == key
-            if have:
-                work, wb = kept[0], kept[1]
             else:
-                wb = int(self.lib.mu_csr_row_col_sums_worksize(n, d))
-                work = self.empty((wb,), torch.uint8)
-            check(self.lib.mu_tfidf_scale_sweep(_dt(X.values), n, d, _p(X.indptr), _p(X.indices),
-                                                _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
-                                                _p(out), _p(zc), _p(work), wb, int(have),
-                                                self._stream()))
-            # the slab pointers (head of the work buffer) also serve the transposition of the same index arrays
-            # one call later (transpose_stream): kept apart from the column partials that follow them
-            n_sp = n * (-(-d // 8192) + 1)
-            self._last_slab_ptr = work[:8 * n_sp].view(torch.int64).clone()
+                check(self.lib.mu_tfidf_scale_sweep(_dt(X.values), n, d, _p(X.indptr), _p(X.indices),
+                                                    _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
+                                                    _p(out), _p(zc), _p(work), wb, int(have),
+                                                    self._stream()))
         return out, zc
+
+    def slab_ptr_from_work(self, X: DeviceCSR, work: torch.Tensor) -> torch.Tensor:
+        """The slab pointers of a table-less X after its scale sweep: a copy of the head of the sweep's work buffer,
+        apart from the column partials that follow them.  They also serve the transposition of the same index arrays
+        (transpose_stream cuts the same 8192-column slabs)."""
+        return work[:8 * _n_slab_ptr(*X.shape)].view(torch.int64).clone()
 
     def compact_nonzero(self, X: DeviceCSR) -> DeviceCSR:
         n = X.shape[0]
@@ -606,21 +628,11 @@ class HipBackend:
                                               self._stream()))
 
     # -- LSI building blocks (reference tools.py:53 -> scipy svds) ---------------------
-    def take_slab_ptr(self):
-        """The slab pointers the last TF-IDF scale sweep left behind (once; None if there are none)."""
-        return self.__dict__.pop("_last_slab_ptr", None)
-
     @staticmethod
     def _slab_ptr_of(X: DeviceCSR):
-        """The slab pointers the TF-IDF sweeps left with X (``tfidf_device``), if they describe X's index arrays."""
-        got = getattr(X, "slab_ptr", None)
-        if got is None:
-            return None
-        sp, key = got
-        n, d = X.shape
-        if key != (X.indptr.data_ptr(), X.indices.data_ptr(), n, d) or sp.numel() != n * (-(-d // 8192) + 1):
-            return None
-        return sp
+        """The slab pointers that came with X (``with_slab_ptr``, ``tfidf_device``), if they describe X's index arrays."""
+        sp = HipBackend._plan_of(X, "slab_ptr")
+        return sp if sp is not None and sp.numel() == _n_slab_ptr(*X.shape) else None
 
     def transpose(self, X: DeviceCSR) -> DeviceCSR:
         n, d = X.shape
@@ -655,8 +667,7 @@ class HipBackend:
                 check(self.lib.mu_exclusive_scan_i64(d, _p(col_nnz), _p(t_indptr), st))
                 check(self.lib.mu_tpack4_fill_csr(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values), None, None,
                                                   _p(t_indptr), _p(t_indices), _p(t_values), _p(work), wb, st))
-            self._note_tpack4(work, n, d, X.nnz)
-            self.raise_tpack4(self.take_tpack4_err().item())  # (set-up / ingest paths: a synchronisation is affordable)
+            self.raise_tpack4(self._note_tpack4(work, n, d, X.nnz).item())  # (set-up / ingest paths: a synchronisation is affordable)
             return DeviceCSR(t_indptr, t_indices, t_values, (d, n))
         # (2^31 rows, a row block of 2^29 entries: the general stable transposition, csrc/transpose.hip)
         return self.transpose(X)
@@ -704,19 +715,17 @@ class HipBackend:
 
     keep_tpack4_work = False  # tests / probes: keep the last fill's work buffer so that tpack4_status() can read its error word
 
-    def _note_tpack4(self, work, n, d, nnz) -> None:
+    def _note_tpack4(self, work, n, d, nnz) -> torch.Tensor:
+        """After a fourth-generation fill: the device int32[1] copy of its error word."""
         # (never by default: a work buffer kept across calls is a second 1.8 GB block at 1e6 x 200k - the next call's
         #  allocation then misses the caching allocator's pool: a hipMalloc inside every step, measured at 300 ms)
         self._tpack4_work = (work, (n, d, nnz)) if self.keep_tpack4_work else None
         # ADVICE r05: the fill's error word (1: bitmap and count pass disagree, 2: a tile could not be narrowed - a
-        # silently wrong X^T) was read by tests only.  A 4-byte copy of it, queued behind the fill, is picked up by the
-        # consumer at its next synchronisation (lsi: with the first Gram fetch; transpose_csr: right away).
+        # silently wrong X^T) was read by tests only.  A 4-byte copy of it, queued behind the fill, goes with the stream
+        # (DeviceStream.t4_err) to the consumer's next synchronisation (lsi: with the first Gram fetch; transpose_csr:
+        # right away).
         off = int(self.lib.mu_tpack4_err_offset(n, d, nnz))
-        self._tpack4_err = work[off:off + 4].view(torch.int32).clone()
-
-    def take_tpack4_err(self):
-        """Device int32[1] error word of the last fourth-generation fill (once; None if there was none)."""
-        return self.__dict__.pop("_tpack4_err", None)
+        return work[off:off + 4].view(torch.int32).clone()
 
     @staticmethod
     def raise_tpack4(err: int) -> None:
@@ -743,64 +752,40 @@ class HipBackend:
         the CSR arrays (r05).  ``before_fill``: called once the count phase is done and before the fill is queued."""
         n, d = X.shape
         assert X.values.dtype == torch.float32
-        col_nnz = self.empty((max(d, 1),), torch.int64)
-        plan = self._plan_of(X, "tplan") if (sort_rows and K is None and self._use_tpack4(X)) else None
-        if plan is not None:
-            # count phase and layout were made with the device CSR (with_plans): the fill is all that is left
-            ent = self.empty((max(X.nnz, 1),), torch.int64)
+        if not self._use_tpack4(X):
+            # (shapes the tile-staged transposition refuses: the CSR of X^T from the general kernel, then a streaming copy)
             if before_fill is not None:
                 before_fill()
-            xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
-            tp = self._tperm_of(X, plan, xs_ent, xs_dst) if src is not None else None
-            with self._dev_ctx():
-                if tp is not None:
-                    # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
-                    cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
-                    check(self.lib.mu_tperm_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
-                                                 _p(tp["toff"]), _p(tp["tiles"]), _p(tp["cont"]), _p(tp["slots"]), _p(ent),
-                                                 self._stream()))
-                else:
-                    check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                         _p(xs_dst), _p(xs_ent), _p(plan["sptr"]), _p(plan["inv"]), _p(ent),
-                                                         _p(plan["work"]), plan["wb"], self._stream()))
-            self._note_tpack4(plan["work"], n, d, X.nnz)
-            return DeviceStream(plan["sptr"], ent, (d, n), X.nnz, plan["perm"], plan["K"], self._t4_prefix(plan["work"], n, d, X.nnz))
-        if self._use_tpack4(X):
-            wb = int(self.lib.mu_tpack4_worksize(n, d, X.nnz))
-            work = self.empty((wb,), torch.uint8)
-            with self._dev_ctx():
-                st = self._stream()
-                check(self.lib.mu_tpack4_count(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(col_nnz), _p(work), wb,
-                                               _p(self._slab_ptr_of(X)), st))
-                want_k = K
-                perm, inv, K, n_pos = None, None, max(1, int(want_k or self.lib.mu_spmm_stream_k(d))), d
-                lens = col_nnz[:d]
-                if sort_rows and d > 0:
-                    perm, inv, K = self.launch_layout(lens, want_k)
-                    n_pos = int(perm.numel())
-                    plens = torch.zeros((n_pos,), dtype=torch.int64, device=self.device)
-                    plens[inv.long()] = lens
-                else:
-                    plens = lens.contiguous()
-                sptr = self._stream_sptr(plens, K)
-                ent = self.empty((max(X.nnz, 1),), torch.int64)
-                if before_fill is not None:
-                    before_fill()
-                xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
-                check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                     _p(xs_dst), _p(xs_ent), _p(sptr), _p(inv), _p(ent), _p(work), wb, st))
-            self._note_tpack4(work, n, d, X.nnz)
-            return DeviceStream(sptr, ent, (d, n), X.nnz, perm, K, self._t4_prefix(work, n, d, X.nnz))
-        # (shapes the tile-staged transposition refuses: the CSR of X^T from the general kernel, then a streaming copy)
+            return self.stream(self.transpose(X), sort_rows=sort_rows, K=K)
+        # count phase and layout: made with the device CSR (with_plans: the fill is all that is left) or here
+        cached = self._plan_of(X, "tplan") if (sort_rows and K is None) else None
+        plan = cached or self._make_tplan(X, K, sort_rows)
+        ent = self.empty((max(X.nnz, 1),), torch.int64)
         if before_fill is not None:
             before_fill()
-        return self.stream(self.transpose(X), sort_rows=sort_rows, K=K)
+        xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
+        tp = self._tperm_of(X, cached, xs_ent, xs_dst) if (cached is not None and src is not None) else None
+        with self._dev_ctx():
+            if tp is not None:
+                # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
+                cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
+                check(self.lib.mu_tperm_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
+                                             _p(tp["toff"]), _p(tp["tiles"]), _p(tp["cont"]), _p(tp["slots"]), _p(ent),
+                                             self._stream()))
+            else:
+                check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
+                                                     _p(xs_dst), _p(xs_ent), _p(plan["sptr"]), _p(plan["inv"]), _p(ent),
+                                                     _p(plan["work"]), plan["wb"], self._stream()))
+        err = self._note_tpack4(plan["work"], n, d, X.nnz)
+        return DeviceStream(plan["sptr"], ent, (d, n), X.nnz, plan["perm"], plan["K"],
+                            self._t4_prefix(plan["work"], n, d, X.nnz), err)
 
     def _tperm_of(self, X: DeviceCSR, plan, xs_ent, xs_dst):
         """The slot table of the table-driven fill (csrc/tperm.hip) for X's row stream as `xplan` lays it out, or None
         (tune tperm_off = 1, a stream laid out otherwise, phase accounting asked for, no memory for the table: the fill of
-        csrc/tpack4.hip).  Made with the FIRST fill that can use it and kept on the transposition plan: it costs 2 bytes
-        per stored entry, which only lsi's operand building gets back - a TF-IDF-only caller never pays for it."""
+        csrc/tpack4.hip).  ``plan``: X's cached `tplan`.  Made with the FIRST fill that can use it and kept on the
+        transposition plan: it costs 2 bytes per stored entry, which only lsi's operand building gets back - a TF-IDF-only
+        caller never pays for it."""
         import ctypes as C
 
         lib = self.lib
@@ -867,13 +852,11 @@ class HipBackend:
         n, d = X.shape
         if n_s <= 0 or X.values.dtype != torch.float32 or not self._use_tpack4(X) or self._slab_ptr_of(X) is None:
             return None
-        key = (X.indptr.data_ptr(), X.indices.data_ptr(), n, d, X.nnz, int(n_s), int(max_ranges))
-        # (kept in the transposition plan's dict when there is one: `with_values` hands that dict - by reference - from
-        #  the counts to every TF-IDF result, so the plan made in the first call serves the later ones)
-        shared = self._plan_of(X, "tplan")
-        got = shared.get("wplan") if shared is not None else getattr(X, "wplan", None)
-        if got is not None and got[1] == key:
-            return got[0]
+        # (cached with the plans: `with_values` hands them - by reference - from the counts to every TF-IDF result, so
+        #  the plan made in the first call serves the later ones)
+        plans, key = CsrPlans.of(X), (int(n_s), int(max_ranges))
+        if plans.wplan is not None and plans.wplan[1] == key:
+            return plans.wplan[0]
         rpb, G = self._t4_geometry(n, d, X.nnz)
         if G < 1:
             return None
@@ -887,10 +870,7 @@ class HipBackend:
                                      for i, (g0, (a, b)) in enumerate(zip(g0s, rows))])
         plan["n_s"] = sum(r["row1"] - r["row0"] for r in plan["ranges"])
         plan["nnz_s"] = sum(r["hi"] - r["lo"] for r in plan["ranges"])
-        if shared is not None:
-            shared["wplan"] = (plan, key)
-        else:
-            X.wplan = (plan, key)
+        plans.wplan = (plan, key)
         return plan
 
     def slice_stream(self, X: DeviceCSR, plan) -> dict:

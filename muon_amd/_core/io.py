@@ -84,10 +84,7 @@ def device_csr_from_10x(matrix: Mapping, comm=None, backend=None, atac_only: boo
     X = canonicalize(backend, X)
     if hasattr(backend, "with_slab_ptr"):
         # ingest is where the slab pointers of the final index arrays are searched, once (tfidf and lsi read them)
-        flag = getattr(X, "canonical_as_given", None)
         X = backend.with_slab_ptr(X)
-        if flag is not None:
-            X.canonical_as_given = flag
     return X, keep, (r0, r1)
 
 
@@ -215,7 +212,7 @@ def read_10x_arrays(matrix: Mapping, atac_only: bool = True, feature_types=None,
         backend = get_backend()
     X, keep, _ = device_csr_from_10x(matrix, None, backend, atac_only, feature_types)
     shape = np.asarray(_get(matrix, "shape")).astype(np.int64)
-    if keep is None and np.asarray(matrix["data"]).dtype == np.float32 and getattr(X, "canonical_as_given", False):
+    if keep is None and np.asarray(matrix["data"]).dtype == np.float32 and X.canonical_as_given:
         # the caller's arrays ARE the canonical CSR: the host view shares them (the flags below used to be
         # set on this branch also when only the device copy had been sorted)
         host = csr_matrix((np.asarray(matrix["data"]), np.asarray(matrix["indices"]),

@@ -299,9 +299,7 @@ class MofaEngine:
                 sub = DeviceCSR((V.X.indptr[a:b + 1] - lo).contiguous(), V.X.indices[lo:hi], V.X.values[lo:hi], (b - a, D))
                 if b > a and hi > lo:
                     s1[g] = be.row_col_sums(sub)[1].to(T)
-                    be.__dict__.pop("_sweep_work", None)
                     s2[g] = be.row_col_sums(sub.with_values(V.X.values[lo:hi] ** 2))[1].to(T)
-                    be.__dict__.pop("_sweep_work", None)
             else:
                 lo, hi = int(V.X.indptr[a].item()), int(V.X.indptr[b].item())
                 idx = V.X.indices[lo:hi].long()

@@ -57,7 +57,7 @@ def run_unstructured(be, n=1_000_000, d=200_000, sample=12_000):
     out = torch.empty_like(X.values)
     tfidf_ms, T = _timed(lambda: tfidf_device(be, X, n, 3, 1e4, out=out))
     fill_ms, (Xs, Xt) = _timed(lambda: be.stream_both(T))
-    be.raise_tpack4(be.take_tpack4_err().item())
+    be.raise_tpack4(Xt.t4_err.item())
     # retried tiles of the fill (tune tpack_dbg: the phase-accounting instance counts them; its time is not the figure)
     retried = None
     try:

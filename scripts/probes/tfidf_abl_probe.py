@@ -37,14 +37,8 @@ for abl in (0, 1, 2, 0):
     print(f"abl {abl}: sum sweep (+ pointers) {t:.2f} ms")
 for abl in (0, 3, 4, 0):
     be.tune("tfidf_abl", abl)
-    be.row_col_sums(X)
-    kept = be.__dict__.get("_sweep_work")
-
-    def scale_only():
-        be._sweep_work = kept
-        be.tfidf_scale(X, rs, idf, 1e4, 3, out=out)
-
-    t = timeit(scale_only)
+    work = be.row_col_sums(X, keep_work=True)[2]  # (None: X came with its slab pointers, nothing to hand on)
+    t = timeit(lambda: be.tfidf_scale(X, rs, idf, 1e4, 3, out=out, work=work))
     print(f"abl {abl}: scale sweep alone {t:.2f} ms")
 be.tune("tfidf_abl", 0)
 rs0, cs0 = be.row_col_sums(X)

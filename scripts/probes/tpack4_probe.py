@@ -51,16 +51,10 @@ def checksum(t, n):
 
 def scale_only(emit):
     """the scale sweep alone (sums and idf once outside)"""
-    rowsum, colsum = be.row_col_sums(X)
+    rowsum, colsum, work = be.row_col_sums(X, keep_work=True)
     idf = be.idf(colsum, float(cells), 3, X.values.dtype)
     lay = be.stream_layout(X) if emit else None
-    keep = be.__dict__.pop("_sweep_work", None)
-
-    def run():
-        be._sweep_work = keep
-        return be.tfidf_scale(X, rowsum, idf, 1e4, 3, out=out, emit=lay)
-
-    ms, _ = timed(run)
+    ms, _ = timed(lambda: be.tfidf_scale(X, rowsum, idf, 1e4, 3, out=out, emit=lay, work=work))
     return ms
 
 

@@ -33,10 +33,8 @@ idf = be.idf(cs, cells, 3, torch.float32)
 out = torch.empty_like(X.values)
 t = timeit(lambda: be.row_col_sums(X))
 print(f"sum sweep (with slab pointers): {t:.2f} ms  {8 * nnz / t / 1e9:.2f} TB/s")
-be._scale_gather = True
-t = timeit(lambda: be.tfidf_scale(X, rs, idf, 1e4, 3, out=out))
+t = timeit(lambda: be.tfidf_scale(X, rs, idf, 1e4, 3, out=out, gather=True))
 print(f"scale, per-lane idf gather:     {t:.2f} ms  {12 * nnz / t / 1e9:.2f} TB/s")
-be._scale_gather = False
 t = timeit(lambda: be.tfidf_scale(X, rs, idf, 1e4, 3, out=out))
 print(f"scale, slab sweep (+ pointers): {t:.2f} ms  {12 * nnz / t / 1e9:.2f} TB/s")
 
@@ -58,14 +56,8 @@ for wide in (1, 0):
     be.row_col_sums(X)
     got, _ = be.tfidf_scale(X, rs, idf, 1e4, 3)
     same = bool(torch.equal(got, ref))
-    be.row_col_sums(X)
-    kept = be.__dict__.get("_sweep_work")
-
-    def scale_only():
-        be._sweep_work = kept
-        be.tfidf_scale(X, rs, idf, 1e4, 3, out=out)
-
-    t = timeit(scale_only) if kept is not None else float("nan")
+    work = be.row_col_sums(X, keep_work=True)[2]  # (None: X came with its slab pointers, nothing to hand on)
+    t = timeit(lambda: be.tfidf_scale(X, rs, idf, 1e4, 3, out=out, work=work))
     t2 = timeit(both)
     print(f"tfidf_wide {wide}: scale sweep alone {t:.2f} ms ({12 * nnz / t / 1e9:.2f} TB/s), sum + scale {t2:.2f} ms, bit-identical {same}")
 be.tune("tfidf_wide", 0)

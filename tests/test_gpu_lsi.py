@@ -356,8 +356,8 @@ def test_transposition_takes_the_slab_pointers_tfidf_searched(hip):
     X = hip.synth_counts(0, 3000, 20000, 20, 0.03, 0)
     for be in (hip, Wrapped(hip)):
         T = tfidf_device(be, X, 3000, 3, 1e4)
-        sp_, key = T.slab_ptr
-        assert sp_.numel() == 3000 * (3 + 1) and key == (T.indptr.data_ptr(), T.indices.data_ptr(), 3000, 20000)
+        sp_, key = T.plans.slab_ptr, T.plans.key
+        assert sp_.numel() == 3000 * (3 + 1) and key == (T.indptr.data_ptr(), T.indices.data_ptr(), 3000, 20000, T.nnz)
         assert hip._slab_ptr_of(T) is sp_
         plain = DeviceCSR(T.indptr, T.indices, T.values, T.shape)
         assert hip._slab_ptr_of(plain) is None
@@ -367,7 +367,7 @@ def test_transposition_takes_the_slab_pointers_tfidf_searched(hip):
         assert torch.equal(sa.sptr, sb.sptr) and torch.equal(sa.ent, sb.ent)
     # pointers of other index arrays are not taken
     other = DeviceCSR(T.indptr.clone(), T.indices.clone(), T.values, T.shape)
-    other.slab_ptr = T.slab_ptr
+    other.plans = T.plans
     assert hip._slab_ptr_of(other) is None
 
 

@@ -164,15 +164,11 @@ def test_scale_sweep_equals_gather_kernel(hip, dt, flags):
     m = m.tocsr().astype(dt)
     m.sort_indices()
     X = hip.upload_csr(m.indptr, m.indices, m.data, m.shape)
-    rs, cs = hip.row_col_sums(X)
+    rs, cs, work = hip.row_col_sums(X, keep_work=True)
     idf = hip.idf(cs, n, flags, X.values.dtype)
-    a, za = hip.tfidf_scale(X, rs, idf, 1e4, flags)            # slab pointers reused
+    a, za = hip.tfidf_scale(X, rs, idf, 1e4, flags, work=work)  # slab pointers reused
     b, zb = hip.tfidf_scale(X, rs, idf, 1e4, flags)            # searched again
-    hip._scale_gather = True
-    try:
-        c, zc = hip.tfidf_scale(X, rs, idf, 1e4, flags)
-    finally:
-        hip._scale_gather = False
+    c, zc = hip.tfidf_scale(X, rs, idf, 1e4, flags, gather=True)
     assert torch.equal(a.view(torch.uint8), c.view(torch.uint8))
     assert torch.equal(b.view(torch.uint8), c.view(torch.uint8))
     assert int(za.item()) == int(zc.item()) == int(zb.item())
@@ -204,10 +200,10 @@ def test_sum_sweep_variants_agree(hip, shape):
         for name, keys in (("r03", {"tfidf_pipe": 1}), ("pipe", {"tfidf_sum_m": 1}), ("wide", {"tfidf_sum_m": 2})):
             for k in ("tfidf_pipe", "tfidf_sum_m"):
                 hip.tune(k, keys.get(k, 0))
-            rs, cs = hip.row_col_sums(X)
-            table = hip._sweep_work[0][:8 * n_sp].view(torch.int64).clone()
+            rs, cs, work = hip.row_col_sums(X, keep_work=True)
+            table = work[:8 * n_sp].view(torch.int64).clone()
             idf = hip.idf(cs, n, 3, torch.float32)
-            vals, _ = hip.tfidf_scale(X, rs, idf, 1e4, 3)
+            vals, _ = hip.tfidf_scale(X, rs, idf, 1e4, 3, work=work)
             got[name] = (rs, cs, table, vals)
     finally:
         hip.tune("tfidf_pipe", 0)

@@ -785,3 +785,37 @@ def test_bench_line_is_flattened_for_the_driver():
     assert "mofa_ng_parity_oracle" not in cfg  # (strings stay in the sub-record)
     assert list(out)[-1] == "summary" and out["summary"]["hard_f64_continuation_converged"] is True
     assert len(json.dumps(out["summary"], separators=(",", ":"))) < 1900
+
+
+def _tiny_device_csr():
+    from muon_amd._backend import DeviceCSR
+
+    return DeviceCSR(torch.tensor([0, 1, 2]), torch.tensor([0, 1], dtype=torch.int32), torch.tensor([1.0, 2.0]), (2, 2))
+
+
+def test_device_csr_refuses_undeclared_attributes():
+    """What travels with a device CSR is declared (plans, xstream, canonical_as_given): anything else raises instead of
+    becoming one more field that only some code knows about."""
+    X = _tiny_device_csr()
+    assert X.plans is None and X.xstream is None and X.canonical_as_given is False
+    with pytest.raises(AttributeError):
+        X.slab_ptr = object()
+    with pytest.raises(AttributeError):
+        X.plans_of_mine = 1
+
+
+def test_with_values_shares_the_plans_and_drops_the_stream():
+    from muon_amd._backend import CsrPlans
+
+    X = _tiny_device_csr()
+    X.plans = CsrPlans(CsrPlans.key_of(X))
+    X.xstream = (object(), object(), X.values.data_ptr())
+    X.canonical_as_given = True
+    Y = X.with_values(X.values * 2)
+    assert Y.plans is X.plans and CsrPlans.of(Y) is X.plans  # (one object: a plan made through either serves both)
+    assert Y.xstream is None and Y.indptr is X.indptr and Y.indices is X.indices and Y.shape == X.shape
+    with pytest.raises(AttributeError):
+        X.plans.another_plan = {}
+    # plans of other index arrays are not taken
+    Z = type(X)(X.indptr.clone(), X.indices.clone(), X.values, X.shape, plans=X.plans)
+    assert CsrPlans.of(Z) is None
