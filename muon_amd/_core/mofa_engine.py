@@ -12,9 +12,11 @@ Sparse views go through the CSR SpMM kernel in both directions (X and its device
 group blocks stacked along the dense dimension so that one pass serves all groups; centring is
 applied implicitly as a rank-one correction ((Y - 1 mu^T) W = Y W - 1 (mu^T W)), so the view
 stays CSR.  Dense views go through the tall-skinny MFMA kernels mu_skinny_nn / mu_skinny_tn
-(n_factors <= 16; PyTorch-ROCm GEMMs otherwise and for the K x K blocks).  The Gauss-Seidel
-sweeps over factors are the fused HIP kernels mu_mofa_update_w / mu_mofa_update_z; the
-remaining O(D K + G K^2) node updates (tau, alpha, theta, ELBO) are torch element-wise ops.
+(n_factors <= 16; PyTorch-ROCm GEMMs otherwise).  The K x K statistics of the factor and weight
+blocks come from one pass per block (mu_mofa_rowstats), the Gauss-Seidel sweeps over factors are
+the HIP kernels mu_mofa_update_w / mu_mofa_update_z, and the node updates (tau, alpha, theta) with
+their ELBO terms are the kernels of csrc/mofa_elbo.hip.  An operator set without one of these
+(REQUIRED_OPS) is refused at construction: there is no tensor-operation twin of the iteration.
 When samples are sharded over ranks, the statistics B, <Z>^T<Z>, sum <z^2> and the sample
 part of the ELBO are all-reduced (RCCL) and the W / tau / alpha / theta updates are replicated.
 
@@ -23,23 +25,20 @@ compared iteration by iteration).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
+import threading
 import time
 import warnings
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import Any, List, Optional
 
 import numpy as np
 import torch
 from scipy.sparse import issparse
 
-from .._comm import default_comm
-
-A0 = 1e-14
-B0 = 1e-14
-TH_A0 = 1.0
-TH_B0 = 1.0
-TOL = {"fast": 5e-4, "medium": 5e-5, "slow": 5e-6}
+from .mofa_common import A0, B0, TH_A0, TH_B0, TOL, MofaDriver, _can_ell16  # noqa: F401  (the constants: importable from here)
 
 
 def _pad_block(w: int) -> int:
@@ -47,16 +46,6 @@ def _pad_block(w: int) -> int:
         if w <= b:
             return b
     raise NotImplementedError("n_groups * n_factors must be <= 64 for sparse views")
-
-
-def _can_ell16(be, X, wide: bool) -> bool:
-    """The sliced-ELL kernels address both dense operands with 32-bit byte offsets (64-byte rows of an f32 block, 128-byte
-    rows of an f64 one): X and X^T must both stay under 4 GiB of dense rows, else the row-stream path is taken."""
-    fn = getattr(be, "can_ell16", None)
-    if fn is not None:
-        return bool(fn(X, wide))
-    row = 128 if wide else 64
-    return max(X.shape) * row < (1 << 32)
 
 
 LDS_TILE_BYTES = 60000  # the Grams' LDS tile of csrc/mofa.hip and csrc/mofa_elbo.hip
@@ -75,123 +64,94 @@ def two_pass_fits(M: int, G: int, K: int) -> bool:
     return w_ok and z_ok
 
 
-class _View:
-    pass
+# what every operator set behind a MofaEngine provides (capabilities that differ between operator sets are asked where
+# they are used)
+REQUIRED_OPS = ("mofa_rowstats_work", "mofa_rowstats", "mofa_update_w", "mofa_update_z", "mofa_elbo_work",
+                "mofa_tau_elbo", "mofa_w_elbo", "mofa_z_sums", "mofa_z_elbo")
 
 
-class MofaEngine:
+@dataclass(slots=True)
+class GaussianView:
+    """One view of a MofaEngine: its operands, masks and moments, and the fixed operand blocks of its products."""
+    D: int
+    kind: Optional[str] = None        # "dense" | "sparse"
+    X: Any = None                     # sparse: the CSR view, rows in group order
+    Xs: Any = None                    # ... and the layouts both products read (sliced ELL, row streams or X itself)
+    Xt: Any = None
+    Y: Optional[torch.Tensor] = None  # dense: the block (centred, unless `implicit`)
+    implicit: bool = False            # dense, f32-stored in an f64 fit: centred inside the products (_f32_storage_ok)
+    alias: bool = False               # Y is still the caller's tensor (until _layout_view writes the centred copy)
+    pres: Optional[torch.Tensor] = None  # [N] 1 / 0: sample observed in this view
+    full: bool = False                   # every local sample observed
+    Ngm: Optional[torch.Tensor] = None   # [G] observed samples per group over all ranks (host, f64)
+    Ngm_d: Optional[torch.Tensor] = None
+    mu: Optional[torch.Tensor] = None    # [G, D] what centring subtracts
+    yy: Optional[torch.Tensor] = None    # [G, D] sum (y - mu)^2
+    intercepts: Optional[torch.Tensor] = None
+    ld: int = 0                          # columns of the padded operand blocks (0: plain GEMMs)
+    TWs: Optional[torch.Tensor] = None   # tau o W, D x ld, the groups side by side (sparse)
+    T16: Optional[list] = None           # tau o W per group, D x 16 (mu_skinny_nn)
+    TWt: Optional[list] = None           # tau o W per group, K x D (library GEMM)
+
+
+class MofaEngine(MofaDriver):
     def __init__(self, backend, views: List, groups: np.ndarray, n_factors: int, *,
                  dtype=torch.float64, center_groups=True, scale_views=False, scale_groups=False,
                  ard_weights=True, ard_factors=True, spikeslab_weights=True, seed=1, comm=None,
                  row_offset: int = 0, n_total: Optional[int] = None):
         """``views``: list of (N x D_m) scipy CSR or ndarray; rows that are entirely NaN (dense)
         or flagged in ``present`` are samples missing from that view.  ``groups``: int [N]."""
-        self.be = backend
-        self.comm = default_comm(comm)
         self.T = dtype
         # MUON_AMD_MOFA_PROFILE=1: wall time of the set-up's stages (synchronising between them) in `setup_profile`
         self.setup_profile = [] if os.environ.get("MUON_AMD_MOFA_PROFILE", "0") == "1" else None
         self._t_last = time.perf_counter()
-        self.K = int(n_factors)
-        if not (1 <= self.K <= 32):
+        if not (1 <= int(n_factors) <= 32):
             raise NotImplementedError("1 <= n_factors <= 32")
+        for op in REQUIRED_OPS:
+            if not hasattr(backend, op):
+                raise NotImplementedError(f"MofaEngine needs the operator `{op}`, which {type(backend).__name__} lacks")
         self.opts = dict(ard_weights=ard_weights, ard_factors=ard_factors,
                          spikeslab_weights=spikeslab_weights)
-        groups = np.asarray(groups, dtype=np.int64)
-        self.N = N = len(groups)
-        self.G = G = self._global_max(groups) + 1
-        if not two_pass_fits(len(views), G, self.K):
-            raise NotImplementedError(f"{len(views)} views x {G} groups x {self.K} factors do not fit the sweeps' LDS "
+        # (one iteration is ~150 short launches: the single-process one is replayed as a HIP graph)
+        graph = os.environ.get("MUON_AMD_MOFA_GRAPH", "1") != "0"
+        super().__init__(backend, groups, len(views), n_factors, comm, graph)
+        if not two_pass_fits(len(views), self.G, self.K):
+            raise NotImplementedError(f"{len(views)} views x {self.G} groups x {self.K} factors do not fit the sweeps' LDS "
                                       "tile (two_pass_fits): GeneralMofaEngine fits this model")
         # the seeded host draw of the factors' initial expectations (8 ns per normal, the GIL released): on a host
         # thread while the device works through the views
-        import threading
-
-        z0 = {}
-        nt = N if n_total is None else int(n_total)
-        th = threading.Thread(target=lambda: z0.setdefault("z", np.random.default_rng(seed).standard_normal((nt, self.K))),
-                              daemon=True)
+        z0 = []
+        th = threading.Thread(target=lambda: z0.append(self._draw_z0(seed, row_offset, n_total)), daemon=True)
         th.start()
-        self._z0 = (th, z0)
-        # samples sorted by group (stable) so that every group is a contiguous row range
-        self.perm = np.argsort(groups, kind="stable")
-        gs = groups[self.perm]
-        self.gslice = [(int(np.searchsorted(gs, g, "left")), int(np.searchsorted(gs, g, "right")))
-                       for g in range(G)]
-        self.grp = backend.to_device(gs.astype(np.int32))
-        self.Ng = self._allreduce(torch.tensor([b - a for a, b in self.gslice], dtype=torch.float64))
-        self.M = len(views)
+        self.grp = backend.to_device(np.asarray(groups, dtype=np.int64)[self.perm].astype(np.int32))
         self._mark("groups")
         self.views = [self._prepare_view(v, center_groups, scale_views, scale_groups) for v in views]
         self.Ds = [v.D for v in self.views]
-        self._init_state(seed, row_offset, n_total)
-        self._mark("state")
+        # statistics of the current factors: per view (Gz, Z2, B) and their fixed buffers, per presence mask (Gz, Z2, Zs)
         self._stats = {}
         self._stat_buf = {}
-        self.elbo = []
-        # one iteration is ~150 short launches (the K x K algebra of the tau / alpha / theta / ELBO
-        # terms): on a GPU, and without collectives inside the step, it is captured once into a HIP
-        # graph and replayed, so the host only launches the graph and reads the ELBO back
-        self._graph = None
-        self._graph_elbo = None
-        self._graph_ok = (getattr(backend, "name", "") == "hip" and self.comm.world_size == 1
-                          and os.environ.get("MUON_AMD_MOFA_GRAPH", "1") != "0")
-        self._eager_steps = 0
+        self._zmom = {}
+        th.join()
+        self._init_state(z0[0])
+        self._mark("state")
         # several ranks: the iteration as two captured segments around one packed all-reduce (see _seg_a); on operator
         # sets without graphs (CPU tests) the segments run eagerly - same schedule, one collective per iteration
-        self._loc = {}
         self._seg_graphs = None
-        self._seg = bool(self.comm.world_size > 1 and getattr(self, "_fused", False)
-                         and os.environ.get("MUON_AMD_MOFA_SEGMENTS", "1") != "0")
-        self._seg_ok = (self._seg and getattr(backend, "name", "") == "hip"
-                        and os.environ.get("MUON_AMD_MOFA_GRAPH", "1") != "0")
+        self._seg = bool(self.comm.world_size > 1 and os.environ.get("MUON_AMD_MOFA_SEGMENTS", "1") != "0")
+        self._seg_ok = self._seg and self._hip and graph
+        self._loc_flat = None  # the segments' fixed buffers (_seg_alloc, at the first segmented iteration)
+        self._locB = []
+        self._statB = []
+        self._zmom_out = {}
 
     # -- helpers -------------------------------------------------------------------------
     def _mark(self, label):
         if self.setup_profile is not None:
-            if getattr(self.be, "name", "") == "hip":
+            if self._hip:
                 torch.cuda.synchronize(self.be.device)
             now = time.perf_counter()
             self.setup_profile.append((label, (now - self._t_last) * 1e3))
             self._t_last = now
-
-    def _global_max(self, groups):
-        m = int(groups.max()) if groups.size else 0
-        if self.comm.world_size > 1:
-            t = torch.tensor([m], dtype=torch.int64)
-            if getattr(self.be, "name", "") == "hip":
-                t = t.to(self.be.device)
-            m = int(self.comm.all_reduce_max(t).item())
-        return m
-
-    def _allreduce(self, t: torch.Tensor) -> torch.Tensor:
-        if self.comm.world_size > 1:
-            dev = t.device
-            if getattr(self.be, "name", "") == "hip" and not t.is_cuda:
-                t = t.to(self.be.device)
-            self.comm.all_reduce_sum(t)
-            t = t.to(dev)
-        return t
-
-    def _all_ranks(self, flag: bool) -> bool:
-        """True iff ``flag`` holds on EVERY rank (a per-shard property that selects a code path with collectives)."""
-        if self.comm.world_size == 1:
-            return bool(flag)
-        bad = self._allreduce(torch.tensor([0.0 if flag else 1.0], dtype=torch.float64))
-        return float(bad.item()) == 0.0
-
-    def _pad16(self, A: torch.Tensor) -> torch.Tensor:
-        out = torch.zeros((A.shape[0], 16), dtype=A.dtype, device=A.device)
-        out[:, : A.shape[1]] = A
-        return out
-
-    def _tn(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
-        """A^T B for tall blocks with <= 16 columns (K x K Grams of the factor / weight blocks).
-        rocBLAS' f64 GEMM takes 4-11 ms for these 10 x 10 outputs with a 1e5-long inner dimension
-        (Tensile 128x128 macro tiles); the tall-skinny MFMA kernel streams the blocks once."""
-        if A.shape[1] <= 16 and B.shape[1] <= 16 and A.shape[0] >= 1024 and hasattr(self.be, "skinny_tn"):
-            return self.be.skinny_tn(self._pad16(A), self._pad16(B))[: A.shape[1], : B.shape[1]]
-        return A.T @ B
 
     def _dev(self, arr, dtype=None):
         t = self.be.to_device(np.ascontiguousarray(arr))
@@ -207,14 +167,14 @@ class MofaEngine:
         view / group scaling (the scaled values are not exact in f32 either)."""
         be = self.be
         return (self.T == torch.float64 and not scale_views and not scale_groups and self.K <= 16
-                and getattr(be, "skinny_mixed", False) and hasattr(be, "skinny_nn") and hasattr(be, "mofa_rowstats")
+                and getattr(be, "skinny_mixed", False) and hasattr(be, "skinny_nn")
                 and os.environ.get("MUON_AMD_MOFA_F32_STORAGE", "1") != "0")
 
     def _prepare_view(self, v, center_groups, scale_views, scale_groups):
         be, T, G = self.be, self.T, self.G
-        V = _View()
         N = self.N
-        V.D = D = v.shape[1]
+        D = v.shape[1]
+        V = GaussianView(D=D)
         from .._backend import DeviceCSR
 
         if isinstance(v, (DeviceCSR, torch.Tensor)):
@@ -271,8 +231,7 @@ class MofaEngine:
                 V.Y = self._dev(a)
         self._mark(f"{V.kind}: values")
         V.pres = self._dev(pres.astype(np.float64))
-        V.Ngm = self._allreduce(torch.tensor([float(pres[a:b].sum()) for a, b in self.gslice],
-                                             dtype=torch.float64))
+        V.Ngm = self._allreduce(torch.tensor([float(pres[a:b].sum()) for a, b in self.gslice], dtype=torch.float64))
         # per (group, feature) first and second moments over the observed samples
         s1 = torch.zeros((G, D), dtype=T, device=V.pres.device)
         s2 = torch.zeros((G, D), dtype=T, device=V.pres.device)
@@ -282,7 +241,7 @@ class MofaEngine:
                 if b > a:
                     m1, m2 = be.col_moments(V.Y, a, b)
                     s1[g], s2[g] = m1.to(T), m2.to(T)
-            elif V.kind == "dense" and getattr(V, "implicit", False):
+            elif V.kind == "dense" and V.implicit:
                 for c0 in range(a, b, 16384):  # (f64 moments of the f32-stored block, a slab of rows at a time)
                     blk = V.Y[c0:min(b, c0 + 16384)].to(T)
                     s1[g] += blk.sum(dim=0)
@@ -353,18 +312,17 @@ class MofaEngine:
 
     def _layout_view(self, V):
         be, mu = self.be, V.mu
-        if V.kind == "dense" and getattr(V, "implicit", False):
-            V.Yt = None  # centred in the products, like the sparse views: Y stays what it was (exact in f32)
+        if V.kind == "dense" and V.implicit:
+            pass  # centred in the products, like the sparse views: Y stays what it was (exact in f32)
         elif V.kind == "dense":
             # explicit centring of the dense block, one pass: y - pres mu (pres is 0 / 1: the product is exact)
             src = V.Y
-            if getattr(V, "alias", False):
+            if V.alias:
                 V.Y = torch.empty_like(src)
                 V.alias = False
             for g, (a, b) in enumerate(self.gslice):
                 if b > a:
                     torch.addcmul(src[a:b], V.pres[a:b, None], mu[g][None, :], value=-1.0, out=V.Y[a:b])
-            V.Yt = None
         elif (self.T == torch.float32 and hasattr(be, "ell16") and _pad_block(self.G * self.K) == 16
               and V.X.shape[0] > 0 and V.X.shape[1] > 0 and _can_ell16(be, V.X, wide=False)):
             # f32, factor blocks of <= 16 columns: the operand of both directions never changes during a fit - laid
@@ -396,35 +354,10 @@ class MofaEngine:
             V.Xs = V.X
         return V
 
-    def _init_state(self, seed, row_offset, n_total):
+    def _init_state(self, z0):
         K, G, T = self.K, self.G, self.T
-        n_total = self.N if n_total is None else int(n_total)
-        th, box = self._z0
-        th.join()
-        del self._z0
-        z0 = box["z"][row_offset:row_offset + self.N]
-        self.EZ = self._dev(z0[self.perm])
-        self.EZ2 = self.EZ ** 2 + 1.0
-        self.sig2z = torch.ones_like(self.EZ)
+        self._init_nodes(z0, T, T)
         dev = self.EZ.device
-        c = float(torch.digamma(torch.tensor(1.0, dtype=torch.float64)) - torch.digamma(torch.tensor(2.0, dtype=torch.float64)))
-        self.W = []
-        for D in self.Ds:
-            w = _View()
-            w.EW = torch.zeros((D, K), dtype=T, device=dev)
-            w.EW2 = torch.ones((D, K), dtype=T, device=dev)
-            w.gamma = torch.ones((D, K), dtype=T, device=dev)
-            w.EWh2 = torch.ones((D, K), dtype=T, device=dev)
-            w.sig2 = torch.ones((D, K), dtype=T, device=dev)
-            w.tau = torch.ones((G, D), dtype=T, device=dev)
-            w.ltau = torch.zeros((G, D), dtype=T, device=dev)
-            w.alpha = torch.ones((K,), dtype=T, device=dev)
-            w.lalpha = torch.zeros((K,), dtype=T, device=dev)
-            w.lth = torch.full((K,), c, dtype=T, device=dev)
-            w.l1mth = torch.full((K,), c, dtype=T, device=dev)
-            self.W.append(w)
-        self.alpha_z = torch.ones((G, K), dtype=T, device=dev)
-        self.lalpha_z = torch.zeros((G, K), dtype=T, device=dev)
         # constants of the Gamma updates, resident so that an iteration has no host -> device copies
         self.Ng_d = self.Ng.to(dev).to(T)
         self._Ng64 = self.Ng.to(dev).to(torch.float64).contiguous()
@@ -434,52 +367,48 @@ class MofaEngine:
             V.Ngm_d = V.Ngm.to(dev).to(T).contiguous()
             V.yy = V.yy.contiguous()
             w.a_alpha = torch.tensor(A0 + 0.5 * V.D, dtype=T, device=dev)
-        # fused statistics (csrc/mofa_stats.hip): operands and moments at fixed addresses, the zero
-        # padding of the operand blocks written once
-        self._fused = hasattr(self.be, "mofa_rowstats")
-        if self._fused:
-            M = self.M
-            self._rs_work = self.be.mofa_rowstats_work(K)
-            self._A = torch.zeros((M, self.N, K), dtype=T, device=dev)
-            self._Gw = torch.zeros((M, G, K, K), dtype=T, device=dev)
-            self._dw2 = torch.zeros((M, G, K), dtype=T, device=dev)
-            self._corr = torch.zeros((M, G, K), dtype=T, device=dev)
-            self._pres = torch.stack([v.pres for v in self.views]).contiguous()
-            self._zpad = {}
-            for V in self.views:
-                V.full = bool((V.pres == 1).all().item())
-                if V.kind == "sparse":
-                    V.ld = _pad_block(G * K)
-                    V.TWs = torch.zeros((V.D, V.ld), dtype=T, device=dev)
-                elif K <= 16 and hasattr(self.be, "skinny_tn"):
-                    V.ld = 16
-                    # f32: the library GEMM for A = Y (tau o W) had been 3 % ahead of mu_skinny_nn; with the branch-free,
-                    # asm-prefetching build of r04 (views of whole 128-byte tiles) the kernel is 2 % ahead of it
-                    # (c4: 0.465 against 0.475 s with the library GEMM)
-                    own_f32 = V.D % 32 == 0
-                    if (T == torch.float64 or own_f32) and hasattr(self.be, "skinny_nn"):
-                        V.T16 = [torch.zeros((V.D, 16), dtype=T, device=dev) for _ in range(G)]
-                    else:
-                        V.TWt = [torch.zeros((K, V.D), dtype=T, device=dev) for _ in range(G)]
+        # the statistics' operands and moments at fixed addresses (csrc/mofa_stats.hip), the zero padding of the operand
+        # blocks written once
+        M = self.M
+        self._rs_work = self.be.mofa_rowstats_work(K)
+        self._A = torch.zeros((M, self.N, K), dtype=T, device=dev)
+        self._Gw = torch.zeros((M, G, K, K), dtype=T, device=dev)
+        self._dw2 = torch.zeros((M, G, K), dtype=T, device=dev)
+        self._corr = torch.zeros((M, G, K), dtype=T, device=dev)
+        self._pres = torch.stack([v.pres for v in self.views]).contiguous()
+        self._zpad = {}
+        for V in self.views:
+            V.full = bool((V.pres == 1).all().item())
+            if V.kind == "sparse":
+                V.ld = _pad_block(G * K)
+                V.TWs = torch.zeros((V.D, V.ld), dtype=T, device=dev)
+            elif K <= 16 and hasattr(self.be, "skinny_tn"):
+                V.ld = 16
+                # f32: the library GEMM for A = Y (tau o W) had been 3 % ahead of mu_skinny_nn; with the branch-free,
+                # asm-prefetching build of r04 (views of whole 128-byte tiles) the kernel is 2 % ahead of it
+                # (c4: 0.465 against 0.475 s with the library GEMM)
+                own_f32 = V.D % 32 == 0
+                if (T == torch.float64 or own_f32) and hasattr(self.be, "skinny_nn"):
+                    V.T16 = [torch.zeros((V.D, 16), dtype=T, device=dev) for _ in range(G)]
                 else:
-                    V.ld = 0
                     V.TWt = [torch.zeros((K, V.D), dtype=T, device=dev) for _ in range(G)]
-                if V.ld and (V.ld, V.kind == "sparse") not in self._zpad:
-                    self._zpad[(V.ld, V.kind == "sparse")] = torch.zeros((self.N, V.ld), dtype=T, device=dev)
-            self._zmom = {}
+            else:
+                V.ld = 0
+                V.TWt = [torch.zeros((K, V.D), dtype=T, device=dev) for _ in range(G)]
+            if V.ld and (V.ld, V.kind == "sparse") not in self._zpad:
+                self._zpad[(V.ld, V.kind == "sparse")] = torch.zeros((self.N, V.ld), dtype=T, device=dev)
         # r05: the views' shares of an iteration are independent between the joins W updates | products A | Z update |
         # statistics, tau, alpha / theta per view | factor node - each view's share runs on its own stream (fork / join by
         # events; captured into the HIP graph as parallel branches), so the ~25 small kernels of one view hide under the
         # other view's product and the HBM-bound dense product overlaps the sliced-ELL one.  Same kernels, same operands:
         # the same numbers; the ELBO adds the views' terms at the end (per-view scalars: the kernels add to a scalar in
-        # place).  One process, fused path only.
+        # place).
         # (several ranks: the first, eager iteration has collectives inside the views' shares and stays on one stream;
         #  the segmented iterations that follow - _seg_a / _seg_b, no collective inside - take the views' streams too)
-        self._par_ok = bool(self._fused and self.M > 1 and getattr(self.be, "name", "") == "hip")
+        self._par_ok = bool(self.M > 1 and self._hip)
         self._par = self._par_ok and self.comm.world_size == 1
         self._side = [torch.cuda.Stream(self.be.device) for _ in range(self.M - 1)] if self._par_ok else []
-        if self._fused:
-            self._rs_work_v = [self._rs_work] + [self.be.mofa_rowstats_work(K) for _ in range(self.M - 1)]
+        self._rs_work_v = [self._rs_work] + [self.be.mofa_rowstats_work(K) for _ in range(self.M - 1)]
         self._elbo_work_v = [self._elbo_work] + [self.be.mofa_elbo_work(K) for _ in range(self.M - 1)]
 
     # -- the views' streams -------------------------------------------------------------------
@@ -491,8 +420,6 @@ class MofaEngine:
 
     def _on(self, m):
         """Context in which view m's share of a phase is issued (view 0: the current stream)."""
-        import contextlib
-
         if self._par and m > 0:
             return torch.cuda.stream(self._side[m - 1])
         return contextlib.nullcontext()
@@ -533,7 +460,7 @@ class MofaEngine:
         key = "all" if V.full else m
         got = self._zmom.get(key)
         if got is None:
-            fixed = self.__dict__.get("_zmom_out", {}).get(key)  # (segmented iterations: views of one flat block)
+            fixed = self._zmom_out.get(key)  # (segmented iterations: views of one flat block)
             if fixed is not None:
                 Gz, Z2, Zs = fixed
             else:
@@ -566,49 +493,14 @@ class MofaEngine:
             B = torch.stack([V.Y[a:b].T @ self.EZ[a:b] for a, b in self.gslice])
         return Gz, Z2, Zs, B
 
-    def _zstats_fused(self, m):
+    def _zstats_fresh(self, m):
         V = self.views[m]
         Gz, Z2, Zs, B = self._stats_local(m)
         if self.comm.world_size > 1:
             B = B.contiguous()
             Gz, Z2, Zs = Gz.clone(), Z2.clone(), Zs.clone()  # (shared between views: reduce copies)
-            self.comm.all_reduce_sum(Gz, Z2, Zs, B)
-        if V.kind == "sparse" or getattr(V, "implicit", False):
-            B = B - V.mu[:, :, None] * Zs[:, None, :]  # implicit centring
-        return Gz, Z2, B.contiguous()
-
-    def _zstats_fresh(self, m):
-        if getattr(self, "_fused", False):
-            return self._zstats_fused(m)
-        V, K, G = self.views[m], self.K, self.G
-        Gz = torch.zeros((G, K, K), dtype=self.T, device=self.EZ.device)
-        Z2 = torch.zeros((G, K), dtype=self.T, device=self.EZ.device)
-        Zs = torch.zeros((G, K), dtype=self.T, device=self.EZ.device)
-        for g, (a, b) in enumerate(self.gslice):
-            zp = self.EZ[a:b] * V.pres[a:b, None]
-            Gz[g] = self._tn(zp, zp)
-            Z2[g] = (self.EZ2[a:b] * V.pres[a:b, None]).sum(dim=0)
-            Zs[g] = zp.sum(dim=0)
-        if V.kind == "dense" and K <= 16 and hasattr(self.be, "skinny_tn"):
-            # B_g = Y_g^T <Z_g> on the matrix cores, one pass over Y (csrc/skinny.hip)
-            Bl = []
-            for a, b in self.gslice:
-                Z16 = torch.zeros((b - a, 16), dtype=self.T, device=self.EZ.device)
-                Z16[:, :K] = self.EZ[a:b]
-                Bl.append(self.be.skinny_tn(V.Y[a:b], Z16)[:, :K])
-            B = torch.stack(Bl)
-        elif V.kind == "dense":
-            B = torch.stack([V.Y[a:b].T @ self.EZ[a:b] for a, b in self.gslice])
-        else:
-            Bp = _pad_block(G * K)
-            Zst = torch.zeros((self.N, Bp), dtype=self.T, device=self.EZ.device)
-            for g, (a, b) in enumerate(self.gslice):
-                Zst[a:b, g * K:(g + 1) * K] = self.EZ[a:b]
-            out = self.be.spmm(V.Xt, Zst)  # D x (G K): X_g^T <Z_g> for every group in one pass
-            B = torch.stack([out[:, g * K:(g + 1) * K] for g in range(G)]).contiguous()
-        if self.comm.world_size > 1:
-            self.comm.all_reduce_sum(Gz, Z2, Zs, B)
-        if V.kind == "sparse":
+            self._allreduce(Gz, Z2, Zs, B)
+        if V.kind == "sparse" or V.implicit:
             B = B - V.mu[:, :, None] * Zs[:, None, :]  # implicit centring
         return Gz, Z2, B.contiguous()
 
@@ -630,11 +522,11 @@ class MofaEngine:
             if V.kind == "sparse":
                 be.mofa_rowstats(Wm.EW, Wm.EW2, 0, V.D, rs_work, aux=V.mu[g], out_pad=V.TWs, col0=g * K,
                                  s1=self._corr[m, g], **kw)
-            elif hasattr(V, "T16") and getattr(V, "implicit", False):
+            elif V.T16 is not None and V.implicit:
                 be.mofa_rowstats(Wm.EW, Wm.EW2, 0, V.D, rs_work, aux=V.mu[g], out_pad=V.T16[g],
                                  s1=self._corr[m, g], **kw)  # (the centring term goes into the sweep: corr)
                 A[m, a:b] = be.skinny_nn(V.Y[a:b], V.T16[g])[:, :K]
-            elif hasattr(V, "T16"):
+            elif V.T16 is not None:
                 be.mofa_rowstats(Wm.EW, Wm.EW2, 0, V.D, rs_work, out_pad=V.T16[g], **kw)
                 A[m, a:b] = be.skinny_nn(V.Y[a:b], V.T16[g])[:, :K]
             else:
@@ -650,7 +542,7 @@ class MofaEngine:
                 for g, (a, b) in enumerate(self.gslice):
                     A[m, a:b] = out[a:b, g * K:(g + 1) * K]
 
-    def _update_z_fused(self):
+    def _update_z(self):
         """W-side statistics in one pass per (view, group) over the weight block (mu_mofa_rowstats: tau o W
         as the dense operand, Gw, dw2 and the centring correction), the products A = Y (tau o W), the
         sample sweep."""
@@ -667,86 +559,63 @@ class MofaEngine:
         self._stats = {}  # <Z> changed: statistics are stale
         self._zmom = {}
 
-    def _update_z(self):
-        if getattr(self, "_fused", False):
-            return self._update_z_fused()
-        K, G, M, N = self.K, self.G, self.M, self.N
-        dev = self.EZ.device
-        A = torch.zeros((M, N, K), dtype=self.T, device=dev)
-        Gw = torch.zeros((M, G, K, K), dtype=self.T, device=dev)
-        dw2 = torch.zeros((M, G, K), dtype=self.T, device=dev)
-        pres = torch.stack([v.pres for v in self.views]).contiguous()
-        for m, (V, Wm) in enumerate(zip(self.views, self.W)):
-            TW = Wm.tau[:, :, None] * Wm.EW[None, :, :]  # G x D x K
-            for g in range(G):
-                Gw[m, g] = self._tn(Wm.EW, TW[g])
-                dw2[m, g] = (Wm.tau[g][:, None] * Wm.EW2).sum(dim=0)
-            # (f32: hipBLASLt streams Y at 5.1 TB/s when the K x D operand is the transposed one -
-            #  1.57 ms at 1e5 x 2e4 against 2.27 ms with tau o W stored D x K and 3.1 ms for
-            #  mu_skinny_nn, scripts/probes/skinny_nn_probe.py; f64: rocBLAS needs 26 ms, mu_skinny_nn 4.6)
-            if V.kind == "dense" and K <= 16 and self.T == torch.float64 and hasattr(self.be, "skinny_nn"):
-                for g, (a, b) in enumerate(self.gslice):
-                    T16 = torch.zeros((V.D, 16), dtype=self.T, device=dev)
-                    T16[:, :K] = TW[g]
-                    A[m, a:b] = self.be.skinny_nn(V.Y[a:b], T16)[:, :K]
-            elif V.kind == "dense":
-                for g, (a, b) in enumerate(self.gslice):
-                    A[m, a:b] = V.Y[a:b] @ TW[g].T.contiguous().T
-            else:
-                Bp = _pad_block(G * K)
-                TWs = torch.zeros((V.D, Bp), dtype=self.T, device=dev)
-                for g in range(G):
-                    TWs[:, g * K:(g + 1) * K] = TW[g]
-                out = self.be.spmm(V.Xs, TWs)  # N x (G K)
-                for g, (a, b) in enumerate(self.gslice):
-                    # K: mu^T (tau o W), implicit centring (as a reduction: rocBLAS' f64 path takes
-                    # 10.7 ms for this 1 x 1e5 by 1e5 x 10 product)
-                    corr = (V.mu[g][:, None] * TW[g]).sum(dim=0)
-                    A[m, a:b] = out[a:b, g * K:(g + 1) * K] - V.pres[a:b, None] * corr[None, :]
-        az = self.alpha_z if self.opts["ard_factors"] else torch.ones_like(self.alpha_z)
-        self.be.mofa_update_z(A.contiguous(), pres, self.grp, Gw.contiguous(), dw2.contiguous(),
-                              az.contiguous(), self.EZ, self.EZ2, self.sig2z)
-        self._stats = {}  # <Z> changed: statistics are stale
+    def _moments_before_fork(self):
+        """ The factors' moments and the padded <Z> operands are SHARED by the views: where a view's share would
+        make them after the fork (no statistics cached: the first eager iteration, the one after a refused capture)
+        another view's share would read them on its own stream - made here, before the views part."""
+        if self._par:
+            for m in range(self.M):
+                if self._stats.get(m) is None:
+                    self._z_moments(m)
 
-    def _update_rest_and_elbo(self):
-        """tau, alpha_w, theta, alpha_z and the ELBO: csrc/mofa_elbo.hip (one pass per array and a
-        one-workgroup finish per node; the same equations as tensor operations - ~250 launches per
-        iteration - are tests/cpu_backend.py's versions of these entry points)."""
+    def _update_w_all(self):
+        self._fork()
+        for m in range(self.M):
+            with self._on(m):
+                self._update_w(m)
+        self._join()
+
+    def _z_sums_local(self):
+        """Per-group column sums of <z^2> and ln sig2 over this rank's samples."""
+        for g, (a, b) in enumerate(self.gslice):
+            self.be.mofa_z_sums(self.EZ2, self.sig2z, a, b, self._zs[g], self._elbo_work)
+
+    def _nodes_and_elbo(self, stats_of, factor_sums=None) -> torch.Tensor:
+        """tau, alpha_w and theta of every view - ``stats_of(m)``: its (Gz, Z2, B), asked on the view's stream - then
+        alpha_z, with the ELBO: csrc/mofa_elbo.hip (one pass per array and a one-workgroup finish per node; the same
+        equations as tensor operations - ~250 launches per iteration - are tests/cpu_backend.py's versions of these
+        entry points).  ``factor_sums`` fills ``_zs`` between the views' share and the factor node, where ``_zs`` does not
+        hold the sums over all ranks already."""
         o, be = self.opts, self.be
         elbo = torch.zeros((), dtype=torch.float64, device=self.EZ.device)
-        work = self._elbo_work
-        if self._par:
-            # the factors' moments are shared between the views that observe every sample (and refresh the padded <Z>
-            # operands of every product): made once, before the views part
-            if getattr(self, "_fused", False):
-                for m in range(self.M):
-                    if self._stats.get(m) is None:
-                        self._z_moments(m)
+        parts = [elbo] * self.M
+        if self._par:  # (per-view scalars: the kernels add to a scalar in place)
             parts = [elbo] + [torch.zeros((), dtype=torch.float64, device=self.EZ.device) for _ in range(self.M - 1)]
-        else:
-            parts = [elbo] * self.M
         self._fork()
         for m, (V, Wm) in enumerate(zip(self.views, self.W)):
             with self._on(m):
-                wk = self._elbo_work_v[m] if self._par else work
-                Gz, Z2, B = self._zstats(m)
+                wk = self._elbo_work_v[m] if self._par else self._elbo_work
+                Gz, Z2, B = stats_of(m)
                 be.mofa_tau_elbo(V.yy, V.Ngm_d, Wm.EW, Wm.EW2, B, Gz, Z2, A0, B0, Wm.tau, Wm.ltau, parts[m], wk)
                 be.mofa_w_elbo(Wm.EWh2, Wm.gamma, Wm.sig2, o["ard_weights"], o["spikeslab_weights"],
                                A0 + 0.5 * V.D, A0, B0, TH_A0, TH_B0, Wm.alpha, Wm.lalpha, Wm.lth, Wm.l1mth,
                                parts[m], wk)
         self._join()
-        # factors: per-group column sums of <z^2> and ln sig2 over this rank's samples, added up over
-        # the ranks in one collective; the ARD update and the ELBO terms follow from the global sums
-        zs = self._zs
-        for g, (a_, b_) in enumerate(self.gslice):
-            be.mofa_z_sums(self.EZ2, self.sig2z, a_, b_, zs[g], work)
-        if self.comm.world_size > 1:
-            self.comm.all_reduce_sum(zs)
-        be.mofa_z_elbo(zs, self._Ng64, o["ard_factors"], A0, B0, self.alpha_z, self.lalpha_z, elbo)
+        if factor_sums is not None:
+            factor_sums()
+        be.mofa_z_elbo(self._zs, self._Ng64, o["ard_factors"], A0, B0, self.alpha_z, self.lalpha_z, elbo)
         if self._par:
             for extra in parts[1:]:
                 elbo = elbo + extra  # (the views' terms, in view order)
         return elbo
+
+    def _update_rest_and_elbo(self) -> torch.Tensor:
+        def factor_sums():  # (added up over the ranks in one collective: the ARD update and the ELBO terms need the global sums)
+            self._z_sums_local()
+            self._allreduce(self._zs)
+
+        self._moments_before_fork()
+        return self._nodes_and_elbo(self._zstats, factor_sums)
 
     # -- several ranks: an iteration as TWO captured segments around ONE packed all-reduce (r06) -------------------------
     # With collectives inside, r02 - r05 launched a multi-rank iteration eagerly (~150 launches: 1.1 ms at the 12 500-cell
@@ -789,17 +658,13 @@ class MofaEngine:
         self._loc_flat = flat
         # B with the implicit centring applied (sparse / implicitly centred views); the others read their B in place
         self._statB = [torch.empty((G, V.D, K), dtype=T, device=dev)
-                       if (V.kind == "sparse" or getattr(V, "implicit", False)) else None for V in self.views]
+                       if (V.kind == "sparse" or V.implicit) else None for V in self.views]
         self._zmom = {}  # (the next moments are written into the fixed tensors)
 
     def _seg_a(self):
-        if self.__dict__.get("_loc_flat") is None:
+        if self._loc_flat is None:
             self._seg_alloc()
-        self._fork()
-        for m in range(self.M):
-            with self._on(m):
-                self._update_w(m)
-        self._join()
+        self._update_w_all()
         self._update_z()
         if self._par:  # the factors' moments and the padded <Z> operands are shared by the views: before they part
             for m in range(self.M):
@@ -809,40 +674,25 @@ class MofaEngine:
             with self._on(m):
                 self._locB[m].copy_(self._stats_local(m)[3])  # (the moments are in the flat block already)
         self._join()
-        for g, (a_, b_) in enumerate(self.gslice):
-            self.be.mofa_z_sums(self.EZ2, self.sig2z, a_, b_, self._zs[g], self._elbo_work)
+        self._z_sums_local()
 
     def _seg_reduce(self):
-        if self._zs.dtype == self._loc_flat.dtype:
-            self.comm.all_reduce_sum(self._loc_flat)  # (an f64 fit: one message, the factors' sums inside)
-        else:
-            self.comm.all_reduce_sum(self._loc_flat)
-            self.comm.all_reduce_sum(self._zs)
+        self._allreduce(self._loc_flat)  # (an f64 fit: one message, the factors' sums inside)
+        if self._zs.dtype != self._loc_flat.dtype:
+            self._allreduce(self._zs)
 
     def _seg_b(self) -> torch.Tensor:
-        o, be = self.opts, self.be
-        elbo = torch.zeros((), dtype=torch.float64, device=self.EZ.device)
-        parts = [elbo] + ([torch.zeros((), dtype=torch.float64, device=self.EZ.device) for _ in range(self.M - 1)]
-                          if self._par else [elbo] * (self.M - 1))
-        self._fork()
-        for m, (V, Wm) in enumerate(zip(self.views, self.W)):
-            with self._on(m):
-                wk = self._elbo_work_v[m] if self._par else self._elbo_work
-                Gz, Z2, Zs = self._zmom_out["all" if V.full else m]
-                B = self._locB[m]
-                if self._statB[m] is not None:
-                    # implicit centring with the sums over all ranks: B - mu (x) Zs in one kernel
-                    B = torch.addcmul(B, V.mu[:, :, None], Zs[:, None, :], value=-1.0, out=self._statB[m])
-                self._stats[m] = (Gz, Z2, B)
-                be.mofa_tau_elbo(V.yy, V.Ngm_d, Wm.EW, Wm.EW2, B, Gz, Z2, A0, B0, Wm.tau, Wm.ltau, parts[m], wk)
-                be.mofa_w_elbo(Wm.EWh2, Wm.gamma, Wm.sig2, o["ard_weights"], o["spikeslab_weights"], A0 + 0.5 * V.D, A0,
-                               B0, TH_A0, TH_B0, Wm.alpha, Wm.lalpha, Wm.lth, Wm.l1mth, parts[m], wk)
-        self._join()
-        be.mofa_z_elbo(self._zs, self._Ng64, o["ard_factors"], A0, B0, self.alpha_z, self.lalpha_z, elbo)
-        if self._par:
-            for extra in parts[1:]:
-                elbo = elbo + extra  # (the views' terms, in view order)
-        return elbo
+        def stats_of(m):
+            V = self.views[m]
+            Gz, Z2, Zs = self._zmom_out["all" if V.full else m]
+            B = self._locB[m]
+            if self._statB[m] is not None:
+                # implicit centring with the sums over all ranks: B - mu (x) Zs in one kernel
+                B = torch.addcmul(B, V.mu[:, :, None], Zs[:, None, :], value=-1.0, out=self._statB[m])
+            self._stats[m] = (Gz, Z2, B)
+            return self._stats[m]
+
+        return self._nodes_and_elbo(stats_of)
 
     def _iteration_segments(self) -> torch.Tensor:
         self._seg_a()
@@ -873,75 +723,36 @@ class MofaEngine:
     def _iteration(self) -> torch.Tensor:
         """One coordinate-ascent sweep (W per view, Z, tau / alpha / theta, ELBO); device work only,
         returns the ELBO as a device scalar."""
-        if self._par and getattr(self, "_fused", False):
-            # (ADVICE r05) the factors' moments and the padded <Z> operands are SHARED by the views: when no statistics
-            # are cached (first eager iteration, the one after a refused capture) view 0's W update would compute them
-            # on the main stream after the fork while view 1's reads them on its side stream - made here, before the
-            # views part, exactly as _update_rest_and_elbo does
-            for m in range(self.M):
-                if self._stats.get(m) is None:
-                    self._z_moments(m)
-        self._fork()
-        for m in range(self.M):
-            with self._on(m):
-                self._update_w(m)
-        self._join()
+        self._moments_before_fork()
+        self._update_w_all()
         self._update_z()
         return self._update_rest_and_elbo()
 
-    def _capture(self):
+    def _before_capture(self):
         # the statistics the first W update reads must already sit in their fixed buffers
         for m in range(self.M):
             self._zstats(m)
-        torch.cuda.synchronize(self.be.device)
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(g):
-                out = self._iteration()
-        except Exception as e:  # capture refused (e.g. a library call that allocates): stay eager
-            warnings.warn(f"MOFA iteration not captured into a HIP graph ({e}); running eagerly")
-            self._graph_ok = False
-            self._stats = {}
-            return
-        self._graph, self._graph_elbo = g, out
 
-    def step(self):
-        if self._graph is None and self._graph_ok and self._eager_steps >= 2:
-            self._capture()
-        if self._graph is not None:
-            self._graph.replay()
-            e = float(self._graph_elbo.item())
-        elif self._seg_graphs is not None:
+    def _capture_refused(self):
+        self._stats = {}
+
+    def _eager_step(self) -> torch.Tensor:
+        if self._seg_graphs is not None:
             self._seg_graphs[0].replay()
             self._seg_reduce()
             self._seg_graphs[1].replay()
-            e = float(self._graph_elbo.item())
-        elif self._seg and self._eager_steps >= 1:
+            return self._graph_elbo
+        if self._seg and self._eager_steps >= 1:
             self._par = self._par_ok  # (no collective inside a segment: the views' shares on their own streams)
             out = None
             if self._seg_ok and self._eager_steps >= 3:
                 out = self._capture_segments()  # (runs the iteration it captures)
             if out is None:
                 out = self._iteration_segments()
-            e = float(out.item())
-            self._eager_steps += 1
         else:
-            e = float(self._iteration().item())
-            self._eager_steps += 1
-        self.elbo.append(e)
-        return e
-
-    def run(self, n_iterations=1000, convergence_mode="fast", min_iterations=2, callback=None):
-        tol = TOL[convergence_mode]
-        for it in range(n_iterations):
-            self.step()
-            if callback is not None:
-                callback(it, self)
-            if it >= min_iterations and len(self.elbo) >= 2:
-                # (rank 0 decides: a rank that leaves alone strands the others in their next collective)
-                if self.comm.agree(100.0 * abs((self.elbo[-1] - self.elbo[-2]) / self.elbo[0]) < tol):
-                    break
-        return len(self.elbo)
+            out = self._iteration()
+        self._eager_steps += 1
+        return out
 
     def variance_explained(self):
         """R2 (%) of every factor alone per (view, group): 1 - SS(y - z_k w_k^T) / SS(y), from the
@@ -957,17 +768,3 @@ class MofaEngine:
                     res = ss - 2.0 * (w * B[g][:, k]).sum() + (w * w).sum() * Gz[g][k, k]
                     r2[m, g, k] = float((100.0 * (1.0 - res / ss)).item()) if float(ss) > 0 else 0.0
         return r2.numpy()
-
-    def results(self, sort_factors=True):
-        """Factors / weights on the host in the caller's sample order."""
-        inv = np.empty_like(self.perm)
-        inv[self.perm] = np.arange(self.N)
-        Z = self.be.to_host(self.EZ)[inv].astype(np.float64)
-        W = [self.be.to_host(w.EW).astype(np.float64) for w in self.W]
-        r2 = self.variance_explained()
-        order = np.arange(self.K)
-        if sort_factors:
-            order = np.argsort(-r2.sum(axis=(0, 1)), kind="stable")
-        return {"Z": Z[:, order], "W": [w[:, order] for w in W], "r2": r2[:, :, order],
-                "elbo": list(self.elbo), "order": order,
-                "intercepts": [self.be.to_host(v.intercepts) for v in self.views]}

@@ -18,26 +18,53 @@ elements at a time); a sparse modality stays CSR in HBM and only the chunk in fl
 zeros are data for a count likelihood.  Per chunk the work is dense GEMMs against K- and K^2-column
 blocks plus element-wise transforms: PyTorch-ROCm tensor operations (north_star: "PyTorch-ROCm only
 for the MOFA dense factor blocks").  Three chunk passes per iteration (W statistics, Z update,
-tau / ELBO).  Gaussian models without missing entries keep the two-pass HIP engine (mofa_engine.py).
+tau / ELBO).  Views that need no dense chunk skip them: a dense gaussian view keeps masked sufficient
+statistics (``stats``), a sparse poisson or bernoulli view with every sample present runs on the sweeps of
+csrc/mofa_poisson.hip / csrc/mofa_bernoulli.hip (``fused`` / ``fusedb``) where the operator set has them.
+Gaussian models without missing entries keep the two-pass HIP engine (mofa_engine.py); driver, collectives
+and initial state are shared with it (mofa_common.MofaDriver).
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional
+from dataclasses import dataclass, field
+from typing import Any, List, Optional
 
 import numpy as np
 import torch
 from scipy.sparse import issparse
 
-from .._comm import default_comm
-from .mofa_engine import A0, B0, TH_A0, TH_B0, TOL
+from .mofa_common import A0, B0, LN_THETA0, TH_A0, TH_B0, MofaDriver, _can_ell16
 
 LIKELIHOODS = ("gaussian", "poisson", "bernoulli")
 
 
-class _GView:
-    pass
+@dataclass(slots=True)
+class PseudoDataView:
+    """One view of a GeneralMofaEngine: its data, masks and moments, and which passes it needs."""
+    lik: str
+    D: int
+    kind: Optional[str] = None             # "dense" | "sparse"
+    dev: Any = None
+    X: Any = None                          # sparse: the CSR view, rows in group order
+    Xt: Any = None                         # ... its transpose (fused / fusedb)
+    Xe: Any = None                         # ... and both as sliced ELL (fusedb, where the layout fits)
+    Xte: Any = None
+    rowmask: Optional[torch.Tensor] = None  # sparse: [N] 1 / 0, sample observed in this view
+    chunk_full: dict = field(default_factory=dict)  # (lo, hi) -> the chunk holds every sample (asked once per fit)
+    Y: Optional[torch.Tensor] = None       # dense: the block, unobserved entries 0 (centred / scaled once `centred`)
+    mask: Optional[torch.Tensor] = None    # dense: 0 / 1 per entry (None: all observed)
+    mu: Optional[torch.Tensor] = None      # [G, D] what centring subtracts (gaussian)
+    scale: Optional[torch.Tensor] = None   # [G]
+    intercepts: Optional[torch.Tensor] = None
+    kappa: Optional[torch.Tensor] = None   # [D] the Seeger bound's precision (poisson)
+    fused: bool = False                    # poisson, no dense chunk: csrc/mofa_poisson.hip
+    fusedb: bool = False                   # bernoulli, no dense chunk: csrc/mofa_bernoulli.hip
+    centred: bool = False                  # Y holds the centred / scaled / masked values
+    stats: bool = False                    # dense gaussian: masked sufficient statistics in place of chunk passes
+    yyM: Optional[torch.Tensor] = None     # [G, D] sum of the observed y^2 (stats)
+    Ngd: Optional[torch.Tensor] = None     # [G, D] observed entries (stats)
 
 
 def _lambda_jj(x: torch.Tensor) -> torch.Tensor:
@@ -57,79 +84,19 @@ def _beta_kl(a0, b0, a, b, elx, el1mx):
     return (lb(a, b) - lb0) + (a0 - a) * elx + (b0 - b) * el1mx
 
 
-class GeneralMofaEngine:
-    """Same driver interface as MofaEngine (step / run / results / elbo)."""
-
+class GeneralMofaEngine(MofaDriver):
     def __init__(self, backend, views: List, likelihoods: List[str], groups: np.ndarray, n_factors: int, *,
                  dtype=torch.float64, center_groups=True, scale_views=False, scale_groups=False,
                  ard_weights=True, ard_factors=True, spikeslab_weights=True, seed=1, comm=None,
                  row_offset: int = 0, n_total: Optional[int] = None, chunk_elems: int = 1 << 27,
                  spikeslab_factors: bool = False):
         assert len(likelihoods) == len(views) and set(likelihoods).issubset(LIKELIHOODS)
-        self.be = backend
-        self.comm = default_comm(comm)
         self.T = dtype
-        self.K = K = int(n_factors)
         self.lik = list(likelihoods)
         # spikeslab_factors (/root/reference/muon/_core/tools.py:305,486): the W node's spike-and-slab update with samples in
         # the place of features, one (alpha, theta) pair per (group, factor) - oracle/mofa_oracle.py run_general
         self.opts = dict(ard_weights=ard_weights, ard_factors=ard_factors, spikeslab_weights=spikeslab_weights,
                          spikeslab_factors=bool(spikeslab_factors))
-        groups = np.asarray(groups, dtype=np.int64)
-        self.N = N = len(groups)
-        gmax = int(groups.max()) if groups.size else 0
-        if self.comm.world_size > 1:
-            gmax = int(self._allreduce_max(torch.tensor([gmax], dtype=torch.int64)).item())
-        self.G = G = gmax + 1
-        self.perm = np.argsort(groups, kind="stable")
-        gs = groups[self.perm]
-        self.gslice = [(int(np.searchsorted(gs, g, "left")), int(np.searchsorted(gs, g, "right"))) for g in range(G)]
-        self.Ng = self._allreduce(torch.tensor([b - a for a, b in self.gslice], dtype=torch.float64))
-        self.M = len(views)
-        self.chunk_elems = int(chunk_elems)
-        self.views = [self._prepare_view(v, lk, center_groups, scale_views, scale_groups)
-                      for v, lk in zip(views, self.lik)]
-        self.Ds = [v.D for v in self.views]
-        self.dev = self.views[0].dev
-        # initialisation shared with the oracle (oracle/mofa_oracle.py init_state)
-        n_total = N if n_total is None else int(n_total)
-        z0 = np.random.default_rng(seed).standard_normal((n_total, K))[row_offset:row_offset + N]
-        self.EZ = backend.to_device(np.ascontiguousarray(z0[self.perm])).to(dtype)
-        self.EZ2 = self.EZ ** 2 + 1.0
-        self.sig2z = torch.ones_like(self.EZ)
-        c = float(torch.digamma(torch.tensor(1.0, dtype=torch.float64)) - torch.digamma(torch.tensor(2.0, dtype=torch.float64)))
-        # the alpha / theta / factor-ARD nodes and their ELBO terms: the fused kernels of MofaEngine (csrc/mofa_elbo.hip -
-        # the same equations; ~170 tensor launches per iteration otherwise) keep these nodes in the fit's type
-        # (the fused factor nodes have no spike: with spikeslab_factors the small nodes run as tensor operations)
-        self._fused_small = (hasattr(backend, "mofa_w_elbo") and hasattr(backend, "mofa_z_elbo") and K <= 32
-                             and not spikeslab_factors)
-        ST = dtype if self._fused_small else torch.float64
-        self.W = []
-        for D in self.Ds:
-            w = _GView()
-            w.EW = torch.zeros((D, K), dtype=dtype, device=self.dev)
-            w.EW2 = torch.ones((D, K), dtype=dtype, device=self.dev)
-            w.gamma = torch.ones((D, K), dtype=dtype, device=self.dev)
-            w.EWh2 = torch.ones((D, K), dtype=dtype, device=self.dev)
-            w.sig2 = torch.ones((D, K), dtype=dtype, device=self.dev)
-            w.tau = torch.ones((G, D), dtype=dtype, device=self.dev)
-            w.ltau = torch.zeros((G, D), dtype=dtype, device=self.dev)
-            w.alpha = torch.ones((K,), dtype=ST, device=self.dev)
-            w.lalpha = torch.zeros((K,), dtype=ST, device=self.dev)
-            w.lth = torch.full((K,), c, dtype=ST, device=self.dev)
-            w.l1mth = torch.full((K,), c, dtype=ST, device=self.dev)
-            self.W.append(w)
-        self.alpha_z = torch.ones((G, K), dtype=ST, device=self.dev)
-        self.lalpha_z = torch.zeros((G, K), dtype=ST, device=self.dev)
-        self.gamma_z = torch.ones_like(self.EZ)
-        self.EZh2 = self.EZ2.clone()
-        self.lthz = torch.full((G, K), c, dtype=torch.float64, device=self.dev)
-        self.l1mthz = torch.full((G, K), c, dtype=torch.float64, device=self.dev)
-        self._elbo_work = backend.mofa_elbo_work(K) if hasattr(backend, "mofa_elbo_work") and K <= 32 else None
-        if self._fused_small:
-            self._zs = torch.zeros((G, 2, K), dtype=torch.float64, device=self.dev)
-        self.elbo = []
-        self._Ng_dev = self.Ng.to(self.dev)  # (resident: an iteration has no host -> device copies)
         # One iteration is ~400 short launches (chunk passes of the masked / bernoulli views, the K x K algebra of the
         # tau / alpha / theta / ELBO terms).  Every expectation is updated in place (r04 rebound alpha / theta), so the
         # iteration CAN be captured into a HIP graph and replayed - MUON_AMD_MOFA_NG_GRAPH=1, bit-identical to eager
@@ -138,38 +105,33 @@ class GeneralMofaEngine:
         # 3 ms next to the poisson passes' 2 ms are not host launches: ~400 kernels of 2-20 us with the device's own
         # dispatch gap between them, replayed or not.  Fewer kernels (the masked gaussian view's chunk passes and the
         # tau / alpha / theta algebra fused as in MofaEngine) is what would move it.
-        self._graph = None
-        self._graph_elbo = None
-        self._graph_ok = (getattr(backend, "name", "") == "hip" and self.comm.world_size == 1
-                          and os.environ.get("MUON_AMD_MOFA_NG_GRAPH", "0") == "1")
-        self._eager_steps = 0
+        super().__init__(backend, groups, len(views), n_factors, comm, os.environ.get("MUON_AMD_MOFA_NG_GRAPH", "0") == "1")
+        K, G = self.K, self.G
+        self.chunk_elems = int(chunk_elems)
+        self.views = [self._prepare_view(v, lk, center_groups, scale_views, scale_groups)
+                      for v, lk in zip(views, self.lik)]
+        self.Ds = [v.D for v in self.views]
+        self.dev = self.views[0].dev
+        # the alpha / theta / factor-ARD nodes and their ELBO terms: the fused kernels of MofaEngine (csrc/mofa_elbo.hip -
+        # the same equations; ~170 tensor launches per iteration otherwise) keep these nodes in the fit's type
+        # (the fused factor nodes have no spike: with spikeslab_factors the small nodes run as tensor operations)
+        self._fused_small = (hasattr(backend, "mofa_w_elbo") and hasattr(backend, "mofa_z_elbo") and K <= 32
+                             and not spikeslab_factors)
+        self._init_nodes(self._draw_z0(seed, row_offset, n_total), dtype, dtype if self._fused_small else torch.float64)
+        self.gamma_z = torch.ones_like(self.EZ)
+        self.EZh2 = self.EZ2.clone()
+        self.lthz = torch.full((G, K), LN_THETA0, dtype=torch.float64, device=self.dev)
+        self.l1mthz = torch.full((G, K), LN_THETA0, dtype=torch.float64, device=self.dev)
+        self._elbo_work = backend.mofa_elbo_work(K) if hasattr(backend, "mofa_elbo_work") and K <= 32 else None
+        if self._fused_small:
+            self._zs = torch.zeros((G, 2, K), dtype=torch.float64, device=self.dev)
+        self._Ng_dev = self.Ng.to(self.dev)  # (resident: an iteration has no host -> device copies)
         self._zver = 0      # state counter of the factors (the cached statistics of _gauss_stats belong to one state)
         self._gstats = {}
+        self._zouter = None  # [state, <z z^T> rows] (_z_outer)
         self._wver = [0] * self.M  # ... and of every view's weights: b = R^T <Z> of a fused poisson view made by the ELBO
         self._pois_pads = {}       # padded factor blocks of the poisson passes (HipBackend.mofa_poisson_pass)
         self._bnext = {}           # pass (mode 3 of mofa_poisson_pass) serves the next W update if neither has changed
-
-    # -- collectives ------------------------------------------------------------------------------
-    def _on_comm_device(self, t):
-        if getattr(self.be, "name", "") == "hip" and not t.is_cuda:
-            return t.to(self.be.device)
-        return t
-
-    def _allreduce(self, *ts):
-        if self.comm.world_size > 1:
-            moved = [self._on_comm_device(t) for t in ts]
-            self.comm.all_reduce_sum(*moved)
-            for t, m in zip(ts, moved):
-                if m is not t:
-                    t.copy_(m)
-        return ts[0] if len(ts) == 1 else ts
-
-    def _allreduce_max(self, t):
-        if self.comm.world_size > 1:
-            m = self._on_comm_device(t)
-            self.comm.all_reduce_max(m)
-            t = m.to(t.device)
-        return t
 
     # -- data ---------------------------------------------------------------------------------------
     def _rows_per_chunk(self, D):
@@ -177,9 +139,8 @@ class GeneralMofaEngine:
 
     def _prepare_view(self, v, lik, center_groups, scale_views, scale_groups):
         be, T, G, N = self.be, self.T, self.G, self.N
-        V = _GView()
-        V.lik = lik
-        V.D = D = v.shape[1]
+        D = v.shape[1]
+        V = PseudoDataView(lik=lik, D=D)
         if issparse(v):
             m = v.tocsr()[self.perm]
             m.sort_indices()
@@ -193,7 +154,6 @@ class GeneralMofaEngine:
             if getattr(v, "_missing_rows", None) is not None:
                 pres = ~np.asarray(v._missing_rows)[self.perm]
             V.rowmask = be.to_device(pres.astype(np.float64)).to(T)
-            V.mask = None
             V.dev = V.X.values.device
         else:
             a = np.asarray(v, dtype=np.float64)[self.perm]
@@ -201,7 +161,6 @@ class GeneralMofaEngine:
             V.kind = "dense"
             V.Y = be.to_device(np.where(nan, 0.0, a)).to(T)
             V.mask = be.to_device((~nan).astype(np.float64)).to(T) if nan.any() else None
-            V.rowmask = None
             V.dev = V.Y.device
         # first / second moments per (group, feature) over the observed entries
         s1 = torch.zeros((G, D), dtype=torch.float64, device=V.dev)
@@ -222,7 +181,6 @@ class GeneralMofaEngine:
         s1, s2, cnt = self._allreduce(s1, s2, cnt)
         n = cnt.clamp(min=1.0)
         V.intercepts = (s1 / n).to(T)  # tools.py:283-286: nanmean per (view, group), whatever the likelihood
-        V.kappa = None
         if lik == "poisson":
             V.kappa = (0.25 + 0.17 * self._allreduce_max(mx)).to(T)
         if lik == "gaussian":
@@ -261,16 +219,11 @@ class GeneralMofaEngine:
             V.Xt = be.transpose(V.X)
         # the three sparse products of a fused bernoulli view multiply by one 16-column block each: the sliced-ELL layout
         # of MofaEngine's sparse views (csrc/spmm_ell.hip: 0.24 -> ~0.08 ms per product at 3e7 entries), laid out once
-        V.Xe = V.Xte = None
         if V.fusedb and hasattr(be, "ell16"):
-            from .mofa_engine import _can_ell16
-
             wide = T == torch.float64
             if min(V.X.shape) > 0 and _can_ell16(be, V.X, wide):
                 # (f64 values go in as hi + lo parts, the second only when some value is not exact in f32)
                 V.Xe, V.Xte = be.ell16(V.X, wide=wide), be.ell16(V.Xt, wide=wide)
-        V.centred = False
-        V.stats = False
         if lik == "gaussian" and V.kind == "dense":
             # the centred / scaled / masked values are a constant of the fit: made once, in place (r04 recomputed them in
             # every chunk pass - three tensor passes over the view, six times per iteration).  Same operations in the
@@ -320,7 +273,7 @@ class GeneralMofaEngine:
                 rm = V.rowmask[lo:hi]
                 # (whether a chunk has every sample is a property of the fit, not of the iteration: asked once -
                 #  a device -> host question per chunk and pass otherwise: 16.5 -> 14.8 ms per iteration at 20k x 22k)
-                full = V.__dict__.setdefault("_chunk_full", {})
+                full = V.chunk_full
                 if (lo, hi) not in full:
                     full[(lo, hi)] = bool((rm == 1).all())
                 M = None if full[(lo, hi)] else rm[:, None].expand(hi - lo, V.D)
@@ -386,7 +339,7 @@ class GeneralMofaEngine:
     def _z_outer(self):
         """<z z^T> rows of ALL local samples [N, K^2] for the current factors: the W update of a fused poisson view (its
         column sums) and the statistics of every dense gaussian view (rows times the mask) read the same block"""
-        hit = getattr(self, "_zouter", None)
+        hit = self._zouter
         if hit is None or hit[0] != self._zver:
             if hit is None or not self._graph_ok:
                 hit = self._zouter = [self._zver, self._outer_moments(self.EZ, self.EZ2)]
@@ -426,17 +379,17 @@ class GeneralMofaEngine:
         V, Wm, K = self.views[m], self.W[m], self.K
         # (the statistics are built from their first term, not added to zeros: an iteration of the poisson benchmark is
         #  ~130 small tensor kernels at ~5 us each next to 1 ms of passes - every fill and "+=" that is not needed counts)
-        if getattr(V, "fused", False):
+        if V.fused:
             # Omega does not depend on the sample: T_d = kappa_d sum_n <z_n z_n^T>; b = R^T <Z> without R
             Tm = V.kappa[:, None] * self._z_outer().sum(dim=0)[None, :]
             hit = self._bnext.get(m)
             if hit is not None and hit[0] == (self._zver, self._wver[m]):
                 # (made by the tau / ELBO pass of the iteration before, in the same sweep as its likelihood term; only
                 #  read below, unless the ranks add theirs up in place)
-                b = hit[1].clone() if getattr(self.comm, "world_size", 1) > 1 else hit[1]
+                b = hit[1].clone() if self.comm.world_size > 1 else hit[1]
             else:
                 b = self.be.mofa_poisson_pass(1, Wm.EW.contiguous(), self.EZ.contiguous(), V.kappa.contiguous(), V.Xt, pads=self._pois_pads)
-        elif getattr(V, "fusedb", False):
+        elif V.fusedb:
             # T_d = sum_n Omega_nd <z z^T>_n in one sweep over the factor blocks; b = (Y - 1/2)^T <Z> without Y dense
             Tm = self.be.mofa_jaakkola_sweep(Wm.EW, Wm.EW2, self.EZ, self.EZ2).reshape(V.D, K * K)
             b = self._times_block(V.Xte if V.Xte is not None else V.Xt, self.EZ) - 0.5 * self.EZ.sum(dim=0)[None, :]
@@ -495,18 +448,18 @@ class GeneralMofaEngine:
         # (chunks of samples sized by the views that are walked in dense chunks: a fused poisson view needs none, and
         #  the [rows, K^2] statistics themselves bound the rest)
         step = min([self._rows_per_chunk(v.D) for v in self.views
-                    if not (getattr(v, "fused", False) or getattr(v, "fusedb", False))]
+                    if not (v.fused or v.fusedb)]
                    + [self._rows_per_chunk(K * K)])
         # fused poisson views: a = R <W> for ALL samples at once (a sample's row depends on its own <z_n> only, which
         # changes in its own chunk, after use) and the sample-independent S
         fused = {m: (self.be.mofa_poisson_pass(0, self.EZ.contiguous(), self.W[m].EW.contiguous(), V.kappa.contiguous(), V.X, pads=self._pois_pads),
                      V.kappa @ WW[m])
-                 for m, V in enumerate(self.views) if getattr(V, "fused", False)}
+                 for m, V in enumerate(self.views) if V.fused}
         # fused bernoulli views: S_n = sum_d Omega_nd <w w^T>_d for ALL samples in one sweep (a sample's row depends on
         # its own moments only), a = (Y - 1/2) <W>
         fusedb = {m: (self._times_block(V.Xe if V.Xe is not None else V.X, self.W[m].EW) - 0.5 * self.W[m].EW.sum(dim=0)[None, :],
                       self.be.mofa_jaakkola_sweep(self.EZ, self.EZ2, self.W[m].EW, self.W[m].EW2).reshape(self.N, K * K))
-                  for m, V in enumerate(self.views) if getattr(V, "fusedb", False)}
+                  for m, V in enumerate(self.views) if V.fusedb}
         for g, (a0, b0) in enumerate(self.gslice):
             for lo in range(a0, b0, step):
                 hi = min(b0, lo + step)
@@ -585,7 +538,7 @@ class GeneralMofaEngine:
         return self._chunks(V, lo, hi)
 
     def _update_rest_and_elbo(self):
-        o, K, G = self.opts, self.K, self.G
+        o, K, G, be = self.opts, self.K, self.G, self.be
         f64 = torch.float64
         lik = torch.zeros((), dtype=f64, device=self.dev)
         for m, (V, Wm) in enumerate(zip(self.views, self.W)):
@@ -597,9 +550,9 @@ class GeneralMofaEngine:
                 S = torch.zeros((G, V.D), dtype=f64, device=self.dev)
                 Ngd = torch.zeros((G, V.D), dtype=f64, device=self.dev)
             part = torch.zeros((), dtype=f64, device=self.dev) if V.lik != "gaussian" else None
-            chunked = not (getattr(V, "fused", False) or getattr(V, "fusedb", False) or V.stats)
+            chunked = not (V.fused or V.fusedb or V.stats)
             W2, Wsq = (Wm.EW2, Wm.EW ** 2) if chunked else (None, None)
-            if getattr(V, "fused", False) and getattr(self.be, "mofa_poisson_lik_with_b", False):
+            if V.fused and getattr(be, "mofa_poisson_lik_with_b", False):
                 # the likelihood term and the NEXT W update's b = R^T <Z> read the same predictions: one sweep (r05)
                 out = self.be.mofa_poisson_pass(3, Wm.EW.contiguous(), self.EZ.contiguous(), V.kappa.contiguous(), V.Xt, pads=self._pois_pads)
                 hit = self._bnext.get(m)
@@ -608,9 +561,9 @@ class GeneralMofaEngine:
                 hit[1].copy_(out[:, :K])
                 hit[0] = (self._zver, self._wver[m])
                 part += out[:, K].sum(dtype=f64)
-            elif getattr(V, "fused", False):
+            elif V.fused:
                 part += self.be.mofa_poisson_pass(2, self.EZ.contiguous(), Wm.EW.contiguous(), None, V.X, pads=self._pois_pads).sum(dtype=f64)
-            elif getattr(V, "fusedb", False):
+            elif V.fusedb:
                 # sum y zeta - ln(1 + e^zeta): the stored entries through Y <W>, the rest as the poisson view's sweep
                 part += (self.EZ * self._times_block(V.Xe if V.Xe is not None else V.X, Wm.EW)).sum(dtype=f64)
                 part += self.be.mofa_softplus_sweep(self.EZ.contiguous(), Wm.EW.contiguous(), pads=self._pois_pads).sum(dtype=f64)
@@ -676,7 +629,7 @@ class GeneralMofaEngine:
                 Wm.lth.copy_(torch.digamma(a) - torch.digamma(a + b))
                 Wm.l1mth.copy_(torch.digamma(b) - torch.digamma(a + b))
         if self._fused_small:
-            be, work = self.be, self._elbo_work
+            work = self._elbo_work
             elbo = torch.zeros((), dtype=f64, device=self.dev)
             for V, Wm in zip(self.views, self.W):
                 be.mofa_w_elbo(Wm.EWh2, Wm.gamma, Wm.sig2, o["ard_weights"], o["spikeslab_weights"], A0 + 0.5 * V.D, A0, B0,
@@ -756,45 +709,8 @@ class GeneralMofaEngine:
         self._bump_z()
         return self._update_rest_and_elbo()
 
-    def _capture(self):
+    def _capture_refused(self):
         torch.cuda.synchronize(self.be.device)
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(g):
-                out = self._iteration()
-        except Exception as e:  # capture refused (a path that asks the device a question): stay eager
-            import warnings
-
-            warnings.warn(f"MOFA iteration not captured into a HIP graph ({e}); running eagerly")
-            self._graph_ok = False
-            torch.cuda.synchronize(self.be.device)
-            return
-        self._graph, self._graph_elbo = g, out
-
-    def step(self):
-        # (two eager iterations first: they answer the once-per-fit questions - which chunks hold every sample - and
-        #  warm the allocator)
-        if self._graph is None and self._graph_ok and self._eager_steps >= 2:
-            self._capture()
-        if self._graph is not None:
-            self._graph.replay()
-            e = float(self._graph_elbo.item())
-        else:
-            e = float(self._iteration().item())
-            self._eager_steps += 1
-        self.elbo.append(e)
-        return e
-
-    def run(self, n_iterations=1000, convergence_mode="fast", min_iterations=2, callback=None):
-        tol = TOL[convergence_mode]
-        for it in range(n_iterations):
-            self.step()
-            if callback is not None:
-                callback(it, self)
-            if it >= min_iterations and len(self.elbo) >= 2:
-                if self.comm.agree(100.0 * abs((self.elbo[-1] - self.elbo[-2]) / self.elbo[0]) < tol):
-                    break
-        return len(self.elbo)
 
     def variance_explained(self):
         """R2 (%) of every factor alone per (view, group) on the (pseudo-)data of the last sweep."""
@@ -817,16 +733,3 @@ class GeneralMofaEngine:
         ss, rs = self._allreduce(ss, rs)
         r2 = torch.where(ss[:, :, None] > 0, 100.0 * (1.0 - rs / ss[:, :, None].clamp(min=1e-300)), torch.zeros_like(rs))
         return r2.cpu().numpy()
-
-    def results(self, sort_factors=True):
-        inv = np.empty_like(self.perm)
-        inv[self.perm] = np.arange(self.N)
-        Z = self.be.to_host(self.EZ)[inv].astype(np.float64)
-        W = [self.be.to_host(w.EW).astype(np.float64) for w in self.W]
-        r2 = self.variance_explained()
-        order = np.arange(self.K)
-        if sort_factors:
-            order = np.argsort(-r2.sum(axis=(0, 1)), kind="stable")
-        return {"Z": Z[:, order], "W": [w[:, order] for w in W], "r2": r2[:, :, order],
-                "elbo": list(self.elbo), "order": order,
-                "intercepts": [self.be.to_host(v.intercepts) for v in self.views]}

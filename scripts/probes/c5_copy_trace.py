@@ -30,7 +30,7 @@ for _ in range(3):
     eng.step()
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=True) as prof:
-    eng._iteration_segments() if hasattr(eng, "_iteration_segments") and getattr(eng, "_seg", False) else eng.step()
+    eng._iteration_segments() if eng._seg else eng.step()
     torch.cuda.synchronize()
 from collections import Counter
 

@@ -666,3 +666,70 @@ def test_engine_choice(M, G, K, sparse, nan, general):
         views[0] = sp.csr_matrix(np.where(views[0] > 1, views[0], 0.0))
     groups = np.arange(70) % G
     assert tools._needs_general_engine(BE, views, ["gaussian"] * M, groups, K, False) == general
+
+
+# ---- declared state: the views' and the weight node's records, the operator set, the engines' attributes -----------------
+def _small_fit(kind, comm=None):
+    from muon_amd._core.mofa_general import GeneralMofaEngine
+
+    rng = np.random.default_rng(2)
+    y1 = rng.standard_normal((40, 7))
+    y2 = sp.csr_matrix(np.where(rng.random((40, 9)) < 0.3, 1.0, 0.0))
+    groups = np.arange(40) % 2
+    if kind == "gaussian":
+        return MofaEngine(BE, [y1, y2], groups, 3, seed=1, comm=comm)
+    return GeneralMofaEngine(BE, [y1, y2], ["gaussian", "bernoulli"], groups, 3, seed=1, comm=comm)
+
+
+def _lonely_pair():
+    """The two-rank stand-in of tests/test_gpu_mofa.py's segment test: claims two ranks, sums nothing."""
+    from muon_amd._comm import LocalComm
+
+    class LonelyPair(LocalComm):
+        world_size = 2
+
+    return LonelyPair()
+
+
+@pytest.mark.parametrize("kind", ["gaussian", "general"])
+def test_views_and_weight_nodes_take_declared_attributes_only(kind):
+    eng = _small_fit(kind)
+    for record in (eng.views[0], eng.views[1], eng.W[0]):
+        with pytest.raises(AttributeError):
+            record.implict = True  # (a misspelt name must not become a silent new attribute)
+    assert eng.views[0].kind == "dense" and eng.views[1].kind == "sparse" and eng.W[0].EW.shape == (7, 3)
+
+
+def test_two_pass_engine_refuses_an_operator_set_without_rowstats_up_front():
+    class NoRowstats(CpuTestBackend):
+        def __getattribute__(self, name):
+            if name == "mofa_rowstats":
+                raise AttributeError(name)
+            return super().__getattribute__(name)
+
+    assert not hasattr(NoRowstats(), "mofa_rowstats") and hasattr(NoRowstats(), "mofa_update_w")
+    rng = np.random.default_rng(0)
+    with pytest.raises(NotImplementedError, match="mofa_rowstats"):
+        MofaEngine(NoRowstats(), [rng.standard_normal((40, 6))], np.zeros(40, dtype=int), 3)
+
+
+@pytest.mark.parametrize("pair", [False, True])
+@pytest.mark.parametrize("kind", ["gaussian", "general"])
+def test_a_fresh_engine_has_every_attribute_its_step_reads(kind, pair):
+    eng = _small_fit(kind, _lonely_pair() if pair else None)
+    assert eng._graph is None and eng._graph_elbo is None and eng._graph_ok is False and eng._eager_steps == 0
+    assert eng.elbo == []
+    if kind == "gaussian":
+        assert eng._loc_flat is None and eng._zmom_out == {} and eng._seg_graphs is None
+        assert eng._seg is pair and eng._seg_ok is False and eng._par is False  # (no streams, no graphs on this operator set)
+        assert eng._stats == {} and eng._zmom == {}
+        Gz, Z2, Zs = eng._z_moments(0)
+        assert Gz.shape == (2, 3, 3) and Z2.shape == Zs.shape == (2, 3)
+        if pair:
+            eng._seg_a()
+            assert eng._loc_flat is not None and set(eng._zmom_out) == {"all"}
+    else:
+        assert eng._zouter is None and eng._gstats == {}
+    eng.step()
+    eng.step()
+    assert len(eng.elbo) == 2 and np.isfinite(eng.elbo).all() and eng._eager_steps == 2
