@@ -125,6 +125,37 @@ int mu_exclusive_scan_i64(int64_t n, const int64_t* d_in, int64_t* d_out, void* 
  * explicit stored zeros stay 0). */
 int mu_binarize_values(int dtype, int64_t nnz, void* d_values, void* stream);
 
+/* ---- QC metrics and in-place filtering (muon/_core/preproc.py:675-881) ------ */
+/* One sweep for the columns mu.pp.filter_var / filter_obs key on (the tutorials' `n_cells_by_counts`,
+ * `n_genes_by_counts`, `total_counts` of scanpy's calculate_qc_metrics, which _filter_attr reads at
+ * preproc.py:729 `subset = func(df[key].values)`):
+ *   row_nnz[i] = #{j : x_ij stored and != 0}, rowsum[i] = sum_j x_ij   (int64 / f64)
+ *   col_nnz[j], colsum[j]: the same per column.
+ * NaN counts as non-zero, an explicitly stored zero does not.  The sweep is mu_csr_row_col_sums' (same slabs, same
+ * order of additions, column partials of the workgroups reduced in fixed order, no global atomics): the sums are
+ * bit-identical to that entry point's on the same matrix.  Sorted column indices inside each row, like there;
+ * d_slab_ptr: mu_csr_slab_ptr's table of these index arrays, or NULL (searched into d_work).
+ * d_work: mu_csr_qc_worksize(n_rows, n_cols) bytes. */
+size_t mu_csr_qc_worksize(int64_t n_rows, int64_t n_cols);
+int mu_csr_qc(int dtype, int64_t n_rows, int64_t n_cols, const int64_t* d_indptr, const int32_t* d_indices,
+              const void* d_values, int64_t* d_row_nnz, double* d_rowsum, int64_t* d_col_nnz, double* d_colsum,
+              void* d_work, size_t work_bytes, const int64_t* d_slab_ptr, void* stream);
+
+/* The submatrix _filter_attr takes (preproc.py:782-784 `X[subset, :]` / `X[:, subset]`), both axes in one pass:
+ * d_rows int64[n_keep], ascending: new row -> old row; d_col_table int32[n_cols]: old column -> new column, -1 dropped.
+ *   1. mu_csr_submatrix_count: new_row_nnz[i] = surviving entries of row d_rows[i]
+ *   2. the caller scans it into new_indptr (mu_exclusive_scan_i64) and allocates new_indices / new_values
+ *   3. mu_csr_submatrix_fill writes them.
+ * Entries keep their STORED order inside a row (nothing is sorted), explicitly stored zeros survive and values are copied
+ * bit for bit - what scipy's slicing does.  Offsets are 64-bit throughout. */
+int mu_csr_submatrix_count(int64_t n_rows, int64_t n_cols, int64_t n_keep, const int64_t* d_indptr,
+                           const int32_t* d_indices, const int64_t* d_rows, const int32_t* d_col_table,
+                           int64_t* d_new_row_nnz, void* stream);
+int mu_csr_submatrix_fill(int dtype, int64_t n_rows, int64_t n_cols, int64_t n_keep, const int64_t* d_indptr,
+                          const int32_t* d_indices, const void* d_values, const int64_t* d_rows,
+                          const int32_t* d_col_table, const int64_t* d_new_indptr, int32_t* d_new_indices,
+                          void* d_new_values, void* stream);
+
 /* ---- CSR transpose (device CSC copy used for X^T * Y) ----------------------- */
 size_t mu_csr_transpose_worksize(int64_t n_rows, int64_t n_cols, int64_t nnz);
 /* Builds the CSR of X^T: t_indptr int64[n_cols+1], t_indices int32[nnz] (row ids of X,

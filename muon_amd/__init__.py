@@ -9,6 +9,7 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.pp.neighbors    <->  muon.pp.neighbors   (the consumer of X_lsi / X_mofa)
     muon_amd.prot.pp.dsb     <->  muon.prot.pp.dsb    (protein normalisation ahead of neighbors on CITE-seq data)
     muon_amd.prot.pp.clr     <->  muon.prot.pp.clr
+    muon_amd.pp.filter_obs   <->  muon.pp.filter_obs  (filter_var alike; pp.qc_metrics: scanpy's QC columns they key on)
 
 Everything else of muon (I/O, plotting, clustering, ...) is out of scope; see DESIGN.md.
 """
@@ -16,7 +17,8 @@ from ._containers import AnnData, MuData  # duck-typed stand-ins when anndata/mu
 from . import atac  # noqa: F401
 from . import prot  # noqa: F401
 from ._core import tools as tl  # noqa: F401
-from ._core import preproc as pp  # noqa: F401  (mu.pp.neighbors - weighted nearest neighbours -, mu.pp.l2norm)
+from ._core import preproc as pp  # noqa: F401  (mu.pp.neighbors - weighted nearest neighbours -, mu.pp.l2norm,
+#   mu.pp.filter_obs / filter_var on the resident device copy, qc_metrics: the columns they key on)
 from ._core import io  # noqa: F401  (arrays of 10x / mtx / snap files -> row-sharded device CSR)
 
 __version__ = "0.1.0"

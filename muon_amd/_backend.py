@@ -622,6 +622,47 @@ class HipBackend:
                                                   _p(new_values), st))
         return DeviceCSR(new_indptr, new_indices, new_values, X.shape)
 
+    # -- QC metrics and filtering (reference _core/preproc.py:675-881) ----------------
+    def csr_qc(self, X: DeviceCSR):
+        """(row_nnz int64, rowsum f64, col_nnz int64, colsum f64) of X in one sweep (csrc/filter.hip): the counts are
+        of the stored values that are not zero (NaN counts), the sums are ``row_col_sums``' bit for bit."""
+        n, d = X.shape
+        row_nnz, rowsum = self.empty((n,), torch.int64), self.empty((n,), torch.float64)
+        col_nnz, colsum = self.empty((d,), torch.int64), self.empty((d,), torch.float64)
+        wb = int(self.lib.mu_csr_qc_worksize(n, d))
+        work = self.empty((wb,), torch.uint8)
+        with self._dev_ctx():
+            check(self.lib.mu_csr_qc(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values), _p(row_nnz),
+                                     _p(rowsum), _p(col_nnz), _p(colsum), _p(work), wb, _p(self._slab_ptr_of(X)),
+                                     self._stream()))
+        return row_nnz, rowsum, col_nnz, colsum
+
+    def csr_submatrix(self, X: DeviceCSR, rows: torch.Tensor, col_table: torch.Tensor, n_cols: int) -> DeviceCSR:
+        """Rows ``rows`` (int64, ascending: new row -> old row) and the columns ``col_table`` keeps (int32[d]: old ->
+        new column, -1 dropped; ``n_cols`` of them) of X: stored order inside the rows, explicit zeros kept, values bit
+        for bit (csrc/filter.hip).  The result has index arrays of its own and so none of X's derived tables (they
+        describe other arrays); a caller that knows the rows to be sorted asks ``with_slab_ptr`` for new ones."""
+        n, d = X.shape
+        k = int(rows.numel())
+        if rows.dtype != torch.int64 or col_table.dtype != torch.int32 or int(col_table.numel()) != d:
+            raise TypeError("csr_submatrix: rows int64, col_table int32[n_cols of X]")
+        rows, col_table = rows.contiguous(), col_table.contiguous()
+        row_nnz = self.empty((k,), torch.int64)
+        new_indptr = self.zeros((k + 1,), torch.int64)
+        with self._dev_ctx():
+            st = self._stream()
+            check(self.lib.mu_csr_submatrix_count(n, d, k, _p(X.indptr), _p(X.indices), _p(rows), _p(col_table),
+                                                  _p(row_nnz), st))
+            if k:
+                check(self.lib.mu_exclusive_scan_i64(k, _p(row_nnz), _p(new_indptr), st))
+            new_nnz = int(new_indptr[-1].item())
+            new_indices = self.empty((new_nnz,), torch.int32)
+            new_values = self.empty((new_nnz,), X.values.dtype)
+            check(self.lib.mu_csr_submatrix_fill(_dt(X.values), n, d, k, _p(X.indptr), _p(X.indices), _p(X.values),
+                                                 _p(rows), _p(col_table), _p(new_indptr), _p(new_indices),
+                                                 _p(new_values), st))
+        return DeviceCSR(new_indptr, new_indices, new_values, (k, int(n_cols)))
+
     def binarize_values(self, values: torch.Tensor) -> None:
         with self._dev_ctx():
             check(self.lib.mu_binarize_values(_dt(values), values.numel(), _p(values),

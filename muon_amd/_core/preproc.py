@@ -772,3 +772,271 @@ def neighbors(mdata, n_neighbors: Optional[int] = None, n_bandwidth_neighbors: i
     if hasattr(mdata, "update_obs"):
         mdata.update_obs()
     return mdata if copy else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# muon.pp.filter_obs / filter_var (reference _core/preproc.py:675-881) and the QC columns they key on
+# ---------------------------------------------------------------------------------------------------------------------
+# The step every ATAC workflow takes between reading and tfidf.  A host matrix that carries a device copy
+# (_atac.preproc.attach_device: the ingest, binarize, tfidf leave one) is subset on the host with scipy AND on the
+# device with csrc/filter.hip, and the new device copy goes with the new host matrix - the matrix does not cross PCIe
+# a second time.  A matrix without a device copy is subset on the host alone: filtering never starts using the GPU.
+
+
+def _resident_copy(m, backend):
+    """(DeviceCSR, backend) of the valid device copy attached to host matrix ``m``, else (None, backend).  Without a
+    ``backend`` argument the copy's own backend serves: no backend is constructed for a host-only matrix."""
+    from .._atac.preproc import DEVICE_ATTR, resident
+
+    ent = getattr(m, DEVICE_ATTR, None) if issparse(m) else None
+    if ent is None:
+        return None, backend
+    be = ent[1] if backend is None else backend
+    return resident(m, be), be
+
+
+def _submatrix_tensor(X, rows, table, n_cols):
+    """``csr_submatrix`` as tensor operations, for operator sets without the kernel: the same three arrays."""
+    from .._backend import DeviceCSR
+
+    k = int(rows.numel())
+    dev = X.indptr.device
+    lo = X.indptr[rows]
+    ln = X.indptr[rows + 1] - lo
+    row_of = torch.repeat_interleave(torch.arange(k, device=dev), ln)
+    first = torch.cumsum(ln, 0) - ln
+    pos = lo[row_of] + (torch.arange(int(row_of.numel()), device=dev) - first[row_of])
+    nc = table[X.indices[pos].long()]
+    keep = nc >= 0
+    indptr = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(row_of[keep], minlength=k), 0, out=indptr[1:])
+    return DeviceCSR(indptr, nc[keep].to(torch.int32).contiguous(), X.values[pos][keep].contiguous(), (k, int(n_cols)))
+
+
+def submatrix_device(backend, X, row_mask=None, col_mask=None):
+    """Rows / columns of device CSR ``X`` where the boolean masks are True (None: all): stored order inside the rows,
+    explicit zeros kept, values bit for bit - scipy's ``X[rows][:, cols]``.  The result gets the slab pointers and plans
+    of its own index arrays where the backend makes them (like the ingest)."""
+    n, d = X.shape
+    rows = np.arange(n, dtype=np.int64) if row_mask is None else np.nonzero(np.asarray(row_mask, dtype=bool))[0].astype(np.int64)
+    if col_mask is None:
+        table, n_cols = np.arange(d, dtype=np.int32), d
+    else:
+        col_mask = np.asarray(col_mask, dtype=bool)
+        table = (np.cumsum(col_mask, dtype=np.int64) - 1).astype(np.int32)
+        table[~col_mask] = -1
+        n_cols = int(col_mask.sum())
+    rows_d, table_d = backend.to_device(rows, np.int64), backend.to_device(table, np.int32)
+    if hasattr(backend, "csr_submatrix"):
+        Y = backend.csr_submatrix(X, rows_d, table_d, n_cols)
+    else:
+        Y = _submatrix_tensor(X, rows_d, table_d, n_cols)
+    if hasattr(backend, "with_slab_ptr"):
+        Y = backend.with_slab_ptr(Y)  # (resident copies are canonical: sorted rows stay sorted)
+    return Y
+
+
+def _subset_matrix(m, attr, subset, backend):
+    """``m[subset, :]`` (obs) or ``m[:, subset]`` (var); a CSR with a valid device copy keeps one."""
+    if m is None:
+        return None
+    X, be = _resident_copy(m, backend)
+    new = m[subset, :] if attr == "obs" else m[:, subset]
+    if X is not None:
+        from .._atac.preproc import attach_device
+
+        Y = submatrix_device(be, X, subset, None) if attr == "obs" else submatrix_device(be, X, None, subset)
+        new.has_sorted_indices = True  # (a resident copy is canonical, and slicing keeps the stored order)
+        attach_device(new, Y, be)
+    return new
+
+
+def _set_slot(data, name, value):
+    """Rebind ``data.<name>`` past anndata's length validation where the class has a private slot (reference :757)."""
+    setattr(data, f"_{name}" if hasattr(data, f"_{name}") else name, value)
+
+
+def _filter_attr(data, attr, key, func=None, backend=None):
+    if getattr(data, "is_view", False):
+        raise ValueError("The provided adata is a view. In-place filtering does not operate on views.")
+    assert attr in ("obs", "var"), "Attribute has to be either 'obs' or 'var'."
+    df = getattr(data, attr)
+    names = getattr(data, f"{attr}_names")
+    other = "obs" if attr == "var" else "var"
+    other_names = getattr(data, f"{other}_names")
+
+    if isinstance(key, str):
+        if key in df.columns:
+            if func is None:
+                if df[key].dtypes.name != "bool":
+                    raise ValueError(f"Function has to be provided since {key} is not boolean")
+                func = lambda x: x  # noqa: E731
+            subset = func(df[key].values)
+        elif key in other_names and getattr(data, "X", None) is not None:
+            j = np.where(other_names == key)[0]
+            piece = data.X[:, j] if attr == "obs" else data.X[j, :]
+            piece = piece.toarray() if issparse(piece) else np.asarray(piece)
+            subset = func(piece.reshape(-1))
+        else:
+            raise ValueError(f"Column name from .{attr} or one of the {other}_names was expected but got {key}.")
+    else:
+        if func is not None:
+            raise ValueError(f"When providing {attr}_names directly, func has to be None.")
+        subset = np.array(key) if np.array(key).dtype == bool else names.isin(key)
+    subset = np.asarray(subset, dtype=bool).reshape(-1)
+    if subset.size != len(names):
+        raise ValueError(f"The filter has {subset.size} entries for {len(names)} {attr}_names.")
+
+    attrm = {k: (v[subset] if not hasattr(v, "iloc") else v.iloc[subset]) for k, v in dict(getattr(data, f"{attr}m")).items()}
+    pairs = getattr(data, f"{attr}p", None)
+    attrp = None if pairs is None else {k: v[subset][:, subset] for k, v in dict(pairs).items()}
+
+    if is_mudata(data):
+        kept = names[subset]
+        _set_slot(data, attr, df[subset])
+        setattr(data, f"{attr}m", attrm)
+        if attrp is not None:
+            setattr(data, f"{attr}p", attrp)
+        for mod in data.mod.values():
+            # every modality keeps exactly the named ones it has, in its own order
+            _filter_attr(mod, attr, np.asarray(getattr(mod, f"{attr}_names").isin(kept)), backend=backend)
+        data.update()
+        return
+
+    layers = {k: _subset_matrix(v, attr, subset, backend) for k, v in dict(data.layers).items()}
+    X = _subset_matrix(getattr(data, "X", None), attr, subset, backend)
+    n_kept = int(subset.sum())
+    if hasattr(data, "_shape"):  # the duck-typed AnnData keeps its shape in a slot of its own
+        data._shape = (n_kept, data._shape[1]) if attr == "obs" else (data._shape[0], n_kept)
+    _set_slot(data, attr, df[subset])
+    setattr(data, f"{attr}m", attrm)
+    if attrp is not None:
+        setattr(data, f"{attr}p", attrp)
+    data.layers = layers
+    if X is not None:
+        _set_slot(data, "X", X)
+    raw = getattr(data, "raw", None)
+    if attr == "obs" and raw is not None:  # raw keeps every variable: only observations are dropped (:797-799)
+        _set_slot(raw, "X", raw.X[subset, :])
+
+
+def filter_obs(data, var, func=None, *, backend=None) -> None:
+    """
+    Filter observations (samples or cells) in-place using any column in .obs or in .X
+    (reference _core/preproc.py:834-856: same positional signature, same errors).
+
+    var
+            Column name in .obs, or a var_name (that column of .X), with ``func``; a boolean column of .obs without
+            ``func``; a sequence of obs_names; or a boolean array.
+    func
+            Applied to the values; may be omitted for a boolean column.
+    backend
+            Only consulted for a matrix that carries a device copy (default: the copy's own backend).  The copy is
+            subset on the device (csrc/filter.hip) and stays attached to the new host matrix, so ``tfidf`` / ``lsi``
+            still start without an upload.  A matrix without a device copy is filtered on the host alone.
+    """
+    _filter_attr(data, "obs", var, func, backend)
+
+
+def filter_var(data, var, func=None, *, backend=None) -> None:
+    """
+    Filter variables (features, e.g. peaks) in-place using any column in .var or row in .X
+    (reference _core/preproc.py:859-881); see ``filter_obs``.
+    """
+    _filter_attr(data, "var", var, func, backend)
+
+
+def qc_device(backend, X, comm=None):
+    """``(row_nnz, rowsum, col_nnz, colsum)`` of (this rank's row shard of) device CSR ``X`` as host arrays, the
+    per-column pair summed over the ranks in ONE packed all-reduce (counts travel as f64: exact below 2^53)."""
+    from .._comm import default_comm
+
+    comm = default_comm(comm)
+    if hasattr(backend, "csr_qc"):
+        row_nnz, rowsum, col_nnz, colsum = backend.csr_qc(X)
+    else:  # operator sets without the kernel: the same numbers as tensor operations
+        n, d = X.shape
+        rowsum, colsum = backend.row_col_sums(X)
+        nz = X.values != 0  # NaN != 0
+        row_of = torch.repeat_interleave(torch.arange(n, device=X.indptr.device), X.indptr[1:] - X.indptr[:-1])
+        row_nnz = torch.bincount(row_of[nz], minlength=n)
+        col_nnz = torch.bincount(X.indices[nz].long(), minlength=d)
+    if getattr(comm, "world_size", 1) > 1:
+        cnt = col_nnz.to(torch.float64)
+        comm.all_reduce_sum(cnt, colsum)
+        col_nnz = cnt.to(torch.int64)
+    return tuple(backend.to_host(t) for t in (row_nnz, rowsum, col_nnz, colsum))
+
+
+def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p: bool = True, comm=None, backend=None):
+    """
+    The per-cell and per-feature columns of scanpy's ``calculate_qc_metrics`` that the reference's tutorials filter
+    on (``mu.pp.filter_var(atac, "n_cells_by_counts", lambda x: x >= 10)``), computed on the device copy of the matrix.
+
+    ``obs``: ``n_genes_by_counts``, ``total_counts``; ``var``: ``n_cells_by_counts``, ``mean_counts``,
+    ``pct_dropout_by_counts``, ``total_counts``; with ``log1p`` also ``log1p_n_genes_by_counts``,
+    ``log1p_total_counts`` and ``log1p_mean_counts``.  ``inplace=False`` returns the two DataFrames instead.
+
+    One deliberate difference from scanpy, which counts with ``getnnz``: an explicitly stored zero is NOT counted as a
+    detected feature / cell (NaN is).  Totals are f64 whatever the matrix's dtype.
+
+    A sparse matrix is swept where it is resident; otherwise it is uploaded once and the copy stays attached, so the
+    ``filter_*`` / ``tfidf`` / ``lsi`` calls that follow start from it.  With ``comm`` every rank holds a row shard, as
+    in ``tfidf``: the per-feature counts and sums are summed over the ranks and ``n_obs`` is the global count.
+    ``percent_top`` and ``qc_vars`` are not implemented.
+    """
+    import pandas as pd
+
+    from .._comm import default_comm
+
+    if is_anndata(data):
+        adata = data
+    elif is_mudata(data) and "atac" in data.mod:
+        adata = data.mod["atac"]
+    else:
+        raise TypeError("Expected AnnData or MuData object with 'atac' modality")
+    comm = default_comm(comm)
+    counts = adata.X if layer is None else adata.layers[layer]
+    if issparse(counts):
+        from .._atac.preproc import attach_device, upload_canonical
+
+        X, backend = _resident_copy(counts, backend)
+        if X is None:
+            backend = _backend(backend)
+            host, X = upload_canonical(backend, counts)
+            if host is counts:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
+                attach_device(counts, X, backend)
+        row_nnz, rowsum, col_nnz, colsum = qc_device(backend, X, comm)
+    else:
+        backend = _backend(backend)
+        t = backend.to_device(np.asarray(counts)).to(torch.float64)
+        nz = (t != 0).to(torch.float64)
+        cnt, colsum = nz.sum(dim=0), t.sum(dim=0)
+        if getattr(comm, "world_size", 1) > 1:
+            comm.all_reduce_sum(cnt, colsum)
+        row_nnz, rowsum, col_nnz, colsum = (backend.to_host(x) for x in (nz.sum(dim=1).to(torch.int64), t.sum(dim=1),
+                                                                         cnt.to(torch.int64), colsum))
+    n_obs = float(comm.sum_scalar(adata.shape[0]))
+
+    obs = pd.DataFrame(index=adata.obs_names)
+    obs["n_genes_by_counts"] = row_nnz.astype(np.int64)
+    if log1p:
+        obs["log1p_n_genes_by_counts"] = np.log1p(obs["n_genes_by_counts"].values)
+    obs["total_counts"] = rowsum
+    if log1p:
+        obs["log1p_total_counts"] = np.log1p(rowsum)
+    var = pd.DataFrame(index=adata.var_names)
+    var["n_cells_by_counts"] = col_nnz.astype(np.int64)
+    var["mean_counts"] = colsum / n_obs
+    if log1p:
+        var["log1p_mean_counts"] = np.log1p(var["mean_counts"].values)
+    var["pct_dropout_by_counts"] = (1.0 - col_nnz / n_obs) * 100.0
+    var["total_counts"] = colsum
+    if log1p:
+        var["log1p_total_counts"] = np.log1p(colsum)
+    if not inplace:
+        return obs, var
+    for c in obs.columns:
+        adata.obs[c] = obs[c].values
+    for c in var.columns:
+        adata.var[c] = var[c].values

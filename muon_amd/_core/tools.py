@@ -11,7 +11,8 @@ Deliberate deviations, all explicit:
   * sparse modalities are NOT densified (tools.py:117-141 does ``.todense()``);
   * only the Gaussian likelihood is implemented: views whose likelihood the reference's default
     would GUESS as bernoulli / poisson are modelled as gaussian with a warning; asking for them
-    explicitly, SVI, MEFISTO (smooth_*) and ``spikeslab_factors`` raise NotImplementedError;
+    explicitly, SVI and MEFISTO (smooth_*) raise NotImplementedError (``spikeslab_factors=True`` runs, on the
+    general engine: ``_needs_general_engine``);
   * a bad ``groups_label`` raises ValueError where the reference calls ``sys.exit()`` (:106-113);
   * the model file is HDF5 (mofapy2's layout) when h5py is importable; otherwise ``outfile`` +
     ".npz" (NumPy archive, with a warning); results reach the write-back directly, not through it.

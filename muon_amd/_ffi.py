@@ -55,6 +55,10 @@ SIGNATURES = {
     "mu_csr_compact_nonzero": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_exclusive_scan_i64": (C.c_int, [_i64, _vp, _vp, _vp]),
     "mu_binarize_values": (C.c_int, [_i32, _i64, _vp, _vp]),
+    "mu_csr_qc_worksize": (_sz, [_i64, _i64]),
+    "mu_csr_qc": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "mu_csr_submatrix_count": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mu_csr_submatrix_fill": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_csr_transpose_worksize": (_sz, [_i64, _i64, _i64]),
     "mu_csr_transpose": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mu_spmm_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
