@@ -156,6 +156,55 @@ int mu_csr_submatrix_fill(int dtype, int64_t n_rows, int64_t n_cols, int64_t n_k
                           const int32_t* d_col_table, const int64_t* d_new_indptr, int32_t* d_new_indices,
                           void* d_new_values, void* stream);
 
+/* ---- fragment tools (muon/_atac/tools.py:746-1201) --------------------------- */
+/* The loops of count_fragments_features (:859-878), _tss_pileup (:1044-1059) and nucleosome_signal (:1170-1180) over a
+ * fragment table in device memory: five int32 columns of equal length in file order - chrom (code), start, end (BED,
+ * half-open), barcode (code), score - grouped by contig and non-decreasing in start inside a contig;
+ * d_chrom_ptr int64[n_contigs + 1] bounds the contigs' segments and max_len = max(end - start).
+ * d_cell_of int32[n_barcodes]: barcode code -> row of the caller's object, -1 = not in it (the KeyError the
+ * reference swallows).  Everything is integer arithmetic; results do not depend on the order of execution.
+ *
+ * mu_frag_ranges: per window (d_wchrom code, -1 = a contig the table lacks; [d_wlo, d_whi), lo < 0 read as 0) the
+ * candidates start > lo - max_len && start < hi of the contig's segment, by two binary searches: rng_lo (index of the
+ * first one) and rng_len.  Every fragment that tabix's fetch would yield for the window is among them. */
+int mu_frag_chunk(void); /* candidates per work item of the passes below (256) */
+int mu_frag_ranges(int64_t n_win, int64_t n_contigs, const int32_t* d_wchrom, const int32_t* d_wlo,
+                   const int32_t* d_whi, const int64_t* d_chrom_ptr, const int32_t* d_start, int64_t max_len,
+                   int64_t* d_rng_lo, int64_t* d_rng_len, void* stream);
+/* The work item of the next three passes is a chunk of mu_frag_chunk() candidates of one window:
+ * d_chunk_ptr int64[n_win + 1] = exclusive scan of ceil(rng_len / chunk), n_chunks its last element.  A candidate
+ * passes when end > max(lo, 0) && start < hi (tabix's overlap rule) and its barcode is a cell of the caller.
+ *   1. mu_frag_overlap_count: chunk_cnt[c] = passing candidates of chunk c
+ *   2. the caller scans it into chunk_off int64[n_chunks + 1] (mu_exclusive_scan_i64) and allocates keys / vals
+ *   3. mu_frag_overlap_emit: keys = cell * n_features + window (int64), vals = score (d_score NULL: 1), in window order
+ *      and file order inside a window (wave ballot + popcount: the order is a function of the input). */
+int mu_frag_overlap_count(int64_t n_win, int64_t n_chunks, const int64_t* d_chunk_ptr, const int64_t* d_rng_lo,
+                          const int64_t* d_rng_len, const int32_t* d_wlo, const int32_t* d_whi, const int32_t* d_start,
+                          const int32_t* d_end, const int32_t* d_barcode, const int32_t* d_cell_of, int64_t n_barcodes,
+                          int64_t n_obs, int64_t* d_chunk_cnt, void* stream);
+int mu_frag_overlap_emit(int64_t n_win, int64_t n_chunks, const int64_t* d_chunk_ptr, const int64_t* d_rng_lo,
+                         const int64_t* d_rng_len, const int32_t* d_wlo, const int32_t* d_whi, const int32_t* d_start,
+                         const int32_t* d_end, const int32_t* d_barcode, const int32_t* d_score,
+                         const int32_t* d_cell_of, int64_t n_barcodes, int64_t n_obs, int64_t n_features,
+                         const int64_t* d_chunk_off, int64_t* d_keys, int32_t* d_vals, void* stream);
+/* tools.py:1055-1057 `mx[rowind, colind_start:colind_end] += score` as two adds into the ZEROED difference array
+ * d_diff int32[n_obs, width + 1]: +score at max(start - lo, 0), -score at min(end - lo, width) (lo NOT clamped here:
+ * it is the region's first position).  int32 atomics; the caller checks that n_win * max(score) fits. */
+int mu_frag_pileup(int64_t n_win, int64_t n_chunks, const int64_t* d_chunk_ptr, const int64_t* d_rng_lo,
+                   const int64_t* d_rng_len, const int32_t* d_wlo, const int32_t* d_whi, const int32_t* d_start,
+                   const int32_t* d_end, const int32_t* d_barcode, const int32_t* d_score, const int32_t* d_cell_of,
+                   int64_t n_barcodes, int64_t n_obs, int64_t width, int32_t* d_diff, void* stream);
+/* Row-wise inclusive scan of the first `width` columns of d_diff in place (the pileup; column `width` is left as it
+ * is) and, in the same pass, tools.py:1095-1104: d_sums int64[n_obs, 2] = (sum of the first and last flank_size columns,
+ * sum of the columns center_dist .. width - center_dist). */
+int mu_frag_pileup_scan(int64_t n_obs, int64_t width, int64_t flank_size, int64_t center_dist, int32_t* d_diff,
+                        int64_t* d_sums, void* stream);
+/* tools.py:1173-1178 over the first n_take fragments in file order into the ZEROED d_classes int32[n_obs, 2]:
+ * column 0 counts end - start < free_bound, column 1 the others with end - start < mono_bound. */
+int mu_frag_length_classes(int64_t n_take, const int32_t* d_start, const int32_t* d_end, const int32_t* d_barcode,
+                           const int32_t* d_cell_of, int64_t n_barcodes, int64_t n_obs, int free_bound, int mono_bound,
+                           int32_t* d_classes, void* stream);
+
 /* ---- CSR transpose (device CSC copy used for X^T * Y) ----------------------- */
 size_t mu_csr_transpose_worksize(int64_t n_rows, int64_t n_cols, int64_t nnz);
 /* Builds the CSR of X^T: t_indptr int64[n_cols+1], t_indices int32[nnz] (row ids of X,

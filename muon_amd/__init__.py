@@ -10,6 +10,9 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.prot.pp.dsb     <->  muon.prot.pp.dsb    (protein normalisation ahead of neighbors on CITE-seq data)
     muon_amd.prot.pp.clr     <->  muon.prot.pp.clr
     muon_amd.pp.filter_obs   <->  muon.pp.filter_obs  (filter_var alike; pp.qc_metrics: scanpy's QC columns they key on)
+    muon_amd.atac.tl.count_fragments_features / tss_enrichment / nucleosome_signal  <->  muon.atac.tl.* (the fragment
+                             tools: gene-activity counts and the two QC columns, over a fragment table on the device;
+                             atac.tl.locate_fragments reads the TSV, atac.tl.fragments_from_arrays takes its columns)
 
 Everything else of muon (I/O, plotting, clustering, ...) is out of scope; see DESIGN.md.
 """

@@ -32,6 +32,8 @@ from .._comm import default_comm
 from .._containers import is_anndata, is_mudata
 from .._trace import phase
 from .preproc import canonical_csr, resident, upload_canonical  # noqa: F401
+from .fragments import (FragmentTable, count_fragments_features, fragments_from_arrays,  # noqa: F401
+                        locate_fragments, nucleosome_signal, tss_enrichment)
 
 logger = logging.getLogger("muon_amd")
 

@@ -663,6 +663,96 @@ class HipBackend:
                                                  _p(new_values), st))
         return DeviceCSR(new_indptr, new_indices, new_values, (k, int(n_cols)))
 
+    # -- fragment tools (reference _atac/tools.py:746-1201; csrc/fragments.hip) ------
+    @staticmethod
+    def _i32(*tensors):
+        for t in tensors:
+            if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+                raise TypeError("fragment kernels take contiguous int32 columns")
+
+    def frag_ranges(self, start, chrom_ptr, wchrom, wlo, whi, max_len: int):
+        """(rng_lo, rng_len) int64 per window: the candidates start > lo - max_len && start < hi of the window's contig."""
+        self._i32(start, wchrom, wlo, whi)
+        if chrom_ptr.dtype != torch.int64:
+            raise TypeError("frag_ranges: chrom_ptr int64")
+        n_win = int(wchrom.numel())
+        rng_lo, rng_len = self.empty((n_win,), torch.int64), self.empty((n_win,), torch.int64)
+        with self._dev_ctx():
+            check(self.lib.mu_frag_ranges(n_win, int(chrom_ptr.numel()) - 1, _p(wchrom), _p(wlo), _p(whi),
+                                          _p(chrom_ptr.contiguous()), _p(start), int(max_len), _p(rng_lo), _p(rng_len),
+                                          self._stream()))
+        return rng_lo, rng_len
+
+    def _frag_chunks(self, rng_len):
+        """(chunk_ptr int64[n_win + 1], n_chunks): the windows' candidates cut into work items of 256."""
+        n_win = int(rng_len.numel())
+        chunk = int(self.lib.mu_frag_chunk())
+        per = torch.div(rng_len + (chunk - 1), chunk, rounding_mode="floor")
+        chunk_ptr = self.zeros((n_win + 1,), torch.int64)
+        if n_win:
+            check(self.lib.mu_exclusive_scan_i64(n_win, _p(per), _p(chunk_ptr), self._stream()))
+        return chunk_ptr, int(chunk_ptr[-1].item())
+
+    def frag_overlap(self, start, end, barcode, score, cell_of, n_obs: int, wlo, whi, rng_lo, rng_len, n_features: int):
+        """(keys int64, vals int32) of the fragments that overlap their window and belong to a cell: key = cell *
+        n_features + window, value = score (None: 1); window order, file order inside a window."""
+        self._i32(start, end, barcode, score, cell_of, wlo, whi)
+        n_win, nb = int(wlo.numel()), int(cell_of.numel())
+        with self._dev_ctx():
+            st = self._stream()
+            chunk_ptr, n_chunks = self._frag_chunks(rng_len)
+            cnt = self.empty((n_chunks,), torch.int64)
+            off = self.zeros((n_chunks + 1,), torch.int64)
+            check(self.lib.mu_frag_overlap_count(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo),
+                                                 _p(whi), _p(start), _p(end), _p(barcode), _p(cell_of), nb, int(n_obs),
+                                                 _p(cnt), st))
+            if n_chunks:
+                check(self.lib.mu_exclusive_scan_i64(n_chunks, _p(cnt), _p(off), st))
+            total = int(off[-1].item())
+            keys, vals = self.empty((total,), torch.int64), self.empty((total,), torch.int32)
+            if total:
+                check(self.lib.mu_frag_overlap_emit(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo),
+                                                    _p(whi), _p(start), _p(end), _p(barcode), _p(score), _p(cell_of),
+                                                    nb, int(n_obs), int(n_features), _p(off), _p(keys), _p(vals), st))
+        return keys, vals
+
+    def frag_pileup(self, start, end, barcode, score, cell_of, n_obs: int, wlo, whi, rng_lo, rng_len, width: int):
+        """Difference array int32[n_obs, width + 1] of the windows' pileup: +score at a fragment's first column, -score
+        behind its last one (columns count from ``wlo``)."""
+        self._i32(start, end, barcode, score, cell_of, wlo, whi)
+        n_win, nb = int(wlo.numel()), int(cell_of.numel())
+        diff = self.zeros((int(n_obs), int(width) + 1), torch.int32)
+        with self._dev_ctx():
+            chunk_ptr, n_chunks = self._frag_chunks(rng_len)
+            check(self.lib.mu_frag_pileup(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo), _p(whi),
+                                          _p(start), _p(end), _p(barcode), _p(score), _p(cell_of), nb, int(n_obs),
+                                          int(width), _p(diff), self._stream()))
+        return diff
+
+    def frag_pileup_scan(self, diff, flank_size: int, center_dist: int):
+        """Scan the rows of ``diff`` (int32[n, W + 1]) into the pileup IN PLACE; returns int64[n, 2]: the sums of the
+        flank columns and of the centre columns."""
+        self._i32(diff)
+        n, w1 = diff.shape
+        sums = self.zeros((n, 2), torch.int64)
+        with self._dev_ctx():
+            check(self.lib.mu_frag_pileup_scan(n, w1 - 1, int(flank_size), int(center_dist), _p(diff), _p(sums),
+                                               self._stream()))
+        return sums
+
+    def frag_length_classes(self, start, end, barcode, cell_of, n_obs: int, n_take: int, free_bound: int,
+                            mono_bound: int):
+        """int32[n_obs, 2]: fragments among the first ``n_take`` shorter than ``free_bound`` / the others shorter than
+        ``mono_bound``, per cell."""
+        self._i32(start, end, barcode, cell_of)
+        n_take = max(0, min(int(n_take), int(start.numel())))
+        classes = self.zeros((int(n_obs), 2), torch.int32)
+        with self._dev_ctx():
+            check(self.lib.mu_frag_length_classes(n_take, _p(start), _p(end), _p(barcode), _p(cell_of),
+                                                  int(cell_of.numel()), int(n_obs), int(free_bound), int(mono_bound),
+                                                  _p(classes), self._stream()))
+        return classes
+
     def binarize_values(self, values: torch.Tensor) -> None:
         with self._dev_ctx():
             check(self.lib.mu_binarize_values(_dt(values), values.numel(), _p(values),

@@ -156,18 +156,28 @@ def _sort_rows(backend, X):
 
 def device_csr_from_coo(rows, cols, vals, shape, backend=None, values_dtype=np.float32, sum_duplicates=True):
     """Coordinate triplets (Matrix Market bodies, snap count tables: _atac/io.py:125) -> device CSR of
-    ``shape`` = (n_rows, n_cols): one key sort on the device, duplicates summed."""
-    from .._backend import DeviceCSR
-
+    ``shape`` = (n_rows, n_cols): one key sort on the device, duplicates summed.  Host arrays are uploaded; device
+    tensors (the fragment counts of _atac/fragments.py) are taken where they are."""
     if backend is None:
         from .._backend import get_backend
 
         backend = get_backend()
+    d = int(shape[1])
+
+    def dev(a, dtype):
+        if torch.is_tensor(a):
+            return a.to(getattr(torch, np.dtype(dtype).name))
+        return backend.to_device(np.asarray(a), dtype)
+
+    r, c, v = dev(rows, np.int64), dev(cols, np.int64), dev(vals, values_dtype)
+    return device_csr_from_keys(r * d + c, v, shape, sum_duplicates)
+
+
+def device_csr_from_keys(key, v, shape, sum_duplicates=True):
+    """Device tensors ``key`` = row * n_cols + column (int64) and values ``v`` -> device CSR of ``shape``."""
+    from .._backend import DeviceCSR
+
     n, d = int(shape[0]), int(shape[1])
-    r = backend.to_device(np.asarray(rows), np.int64)
-    c = backend.to_device(np.asarray(cols), np.int64)
-    v = backend.to_device(np.asarray(vals), values_dtype)
-    key = r * d + c
     key, order = torch.sort(key, stable=True)
     v = v[order]
     if sum_duplicates and key.numel() > 1:

@@ -59,6 +59,13 @@ SIGNATURES = {
     "mu_csr_qc": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "mu_csr_submatrix_count": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_csr_submatrix_fill": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mu_frag_chunk": (C.c_int, []),
+    "mu_frag_ranges": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mu_frag_overlap_count": (C.c_int, [_i64, _i64] + [_vp] * 9 + [_i64, _i64, _vp, _vp]),
+    "mu_frag_overlap_emit": (C.c_int, [_i64, _i64] + [_vp] * 10 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mu_frag_pileup": (C.c_int, [_i64, _i64] + [_vp] * 10 + [_i64, _i64, _i64, _vp, _vp]),
+    "mu_frag_pileup_scan": (C.c_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mu_frag_length_classes": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "mu_csr_transpose_worksize": (_sz, [_i64, _i64, _i64]),
     "mu_csr_transpose": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mu_spmm_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
