@@ -709,6 +709,24 @@ int mu_prot_dsb_fit(int dtype, int64_t n, int64_t d, const void* d_X, const int6
                     const double* d_resp, int64_t resp_cell_stride, int64_t resp_model_stride, double* d_scaled,
                     double* d_bgmean, double* d_bic, int32_t* d_niter, void* stream);
 
+/* ---- muon.tl.ica: one fixed-point sweep of parallel FastICA (/root/reference/muon/_core/tools.py:1365-1386 hands the
+ * arithmetic to scikit-learn's FastICA; csrc/ica.hip, C-ABI v801) --------------------------------------------------------
+ * d_Z [n x ldz] row-major f64: the whitened data, k components in columns 0 .. k - 1 (ldz >= kp = k rounded up to a
+ * multiple of 16, ldz even, d_Z 16-byte aligned; columns k .. ldz - 1 are read and ignored, whatever they hold).
+ * d_W [k x k] row-major.  With y_ij = sum_c Z[i][c] W[j][c]  (i < n; j, c < k):
+ *     d_A[j][c] = sum_i g(y_ij) Z[i][c]        [k x k] row-major
+ *     d_gp[j]   = sum_i g'(y_ij)               [k]
+ *   fun 0 (logcosh): t = tanh(alpha y), g = t, g' = alpha (1 - t^2)
+ *   fun 1 (exp):     e = exp(-y^2 / 2), g = y e, g' = (1 - y^2) e
+ *   fun 2 (cube):    g = y^3, g' = 3 y^2
+ * all in f64 on the matrix cores, Z read once.  No float atomics: every workgroup leaves its partial sums in its slot of
+ * d_work (mu_ica_worksize bytes) and a second kernel adds the slots in order - two calls agree bit for bit.  The grid is
+ * min(ceil(n / 64), max_blocks) workgroups (max_blocks 0: 512).  1 <= k <= mu_ica_max_components() = 64; n = 0 gives zeros. */
+int mu_ica_max_components(void);
+size_t mu_ica_worksize(int64_t n, int k, int max_blocks);
+int mu_ica_sweep_f64(int64_t n, int k, int64_t ldz, const double* d_Z, const double* d_W, int fun, double alpha,
+                     double* d_A, double* d_gp, void* d_work, size_t work_bytes, int max_blocks, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

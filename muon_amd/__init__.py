@@ -13,6 +13,7 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.atac.tl.count_fragments_features / tss_enrichment / nucleosome_signal  <->  muon.atac.tl.* (the fragment
                              tools: gene-activity counts and the two QC columns, over a fragment table on the device;
                              atac.tl.locate_fragments reads the TSV, atac.tl.fragments_from_arrays takes its columns)
+    muon_amd.tl.ica          <->  muon.tl.ica         (FastICA of X_pca / X_lsi / X_mofa: one fused sweep per iteration)
 
 Everything else of muon (I/O, plotting, clustering, ...) is out of scope; see DESIGN.md.
 """

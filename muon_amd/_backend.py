@@ -1554,6 +1554,33 @@ class HipBackend:
                                                self._stream()))
         return scaled, bg, bic, niter
 
+    # -- muon.tl.ica (csrc/ica.hip; muon_amd/_core/ica.py tests for these with hasattr) --------------------------------
+    _ICA_FUN = {"logcosh": 0, "exp": 1, "cube": 2}
+
+    def ica_max_components(self) -> int:
+        """The most components the fused sweep takes (more: the tensor formulation)."""
+        return int(self.lib.mu_ica_max_components())
+
+    def ica_sweep(self, Z, W, fun: str, alpha: float = 1.0, max_blocks: int = 0):
+        """One fixed-point sweep of parallel FastICA (include/muon_amd.h): with y = Z[:, :k] W^T, returns
+        (A = g(y)^T Z[:, :k] [k, k], gp = column sums of g'(y) [k]), f64.  Z: [n, >= k rounded up to 16] f64 with unit
+        column stride; columns past k are ignored.  Two calls with the same arguments agree bit for bit."""
+        n, k = int(Z.shape[0]), int(W.shape[0])
+        if fun not in self._ICA_FUN:
+            raise ValueError(f"fun must be one of {sorted(self._ICA_FUN)}, got {fun!r}")
+        assert Z.dtype == torch.float64 and W.dtype == torch.float64 and tuple(W.shape) == (k, k) and W.is_contiguous()
+        assert Z.dim() == 2 and (Z.shape[1] == 0 or Z.stride(1) == 1)
+        ld = int(Z.stride(0)) if n > 1 else int(Z.shape[1])
+        A, gp = self.empty((k, k), torch.float64), self.empty((k,), torch.float64)
+        wb = int(self.lib.mu_ica_worksize(n, k, int(max_blocks))) if 1 <= k <= self.ica_max_components() else 0
+        work = self.empty((max(wb, 8),), torch.uint8)
+        if min(int(Z.shape[1]), ld) < (k + 15) // 16 * 16:
+            ld = int(Z.shape[1])  # (a view narrower than the padded width: the library refuses it by its ldz)
+        with self._dev_ctx():
+            check(self.lib.mu_ica_sweep_f64(n, k, ld, _p(Z), _p(W), self._ICA_FUN[fun], float(alpha), _p(A), _p(gp),
+                                            _p(work), wb, int(max_blocks), self._stream()))
+        return A, gp
+
     def mofa_jaakkola(self, zeta, a, b):
         """Bernoulli pseudo-data precision 2 lambda(xi), xi^2 = zeta^2 + a - b, written over ``a``."""
         assert zeta.is_contiguous() and a.is_contiguous() and b.is_contiguous() and a.shape == zeta.shape == b.shape

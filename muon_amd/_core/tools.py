@@ -32,6 +32,7 @@ import torch
 from scipy.sparse import csr_matrix, issparse
 
 from .._containers import MuData, is_anndata, is_mudata
+from .ica import ConvergenceWarning, ica  # noqa: F401  (mu.tl.ica: FastICA of an embedding on the device)
 
 logger = logging.getLogger("muon_amd")
 

@@ -155,6 +155,9 @@ SIGNATURES = {
     "mu_prot_log_moments_dense": (C.c_int, [_i32, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
     "mu_prot_dsb_fit": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
                                   _vp, _vp]),
+    "mu_ica_max_components": (C.c_int, []),
+    "mu_ica_worksize": (_sz, [_i64, _i32, _i32]),
+    "mu_ica_sweep_f64": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _i32, _dbl, _vp, _vp, _vp, _sz, _i32, _vp]),
     "mu_synth_row_nnz": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp]),
     "mu_synth_fill": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp, _vp, _vp]),
 }
