@@ -372,3 +372,81 @@ def test_l2norm_against_the_reference_executing(golden_dir):
     b = AnnData(s.copy())
     pp.l2norm(b)
     np.testing.assert_allclose(b.X.tocsr().data, g["l2_csr_out_data"], rtol=1e-14)
+
+
+# ---- the references of tests/test_gpu_knn_edges.py against the tensor paths (tests/knn_edge_refs.py) ---------------
+#      the same checks with the CPU operator set and the filter's emulation in the kernels' place: what the GPU tests
+#      compare the kernels with is itself compared with an independent formulation here
+@pytest.mark.parametrize("square", [False, True], ids=["distinct", "square"])
+@pytest.mark.parametrize("p_pad", [4, 156])
+def test_filter_reference_agrees_with_the_emulation(p_pad, square):
+    from tests import knn_edge_refs as ref
+
+    ref.check_filter(_FilterEmulation(), p_pad, square, n_qs=(1, 65) + ((ref.FILTER_N_CAND,) if square else ()))
+
+
+@pytest.mark.parametrize("n,p,kc", [(2500, 3, 5), (2500, 64, 40), (4500, 3, 40), (4500, 64, 5)])
+def test_candidate_search_reference_agrees_with_the_emulation(n, p, kc):
+    from tests import knn_edge_refs as ref
+
+    ref.check_candidates_separated(_FilterEmulation(), n, p, kc)
+
+
+def test_candidate_search_reference_agrees_with_the_emulation_on_tied_rows():
+    from tests import knn_edge_refs as ref
+
+    ref.check_candidates_tied(_FilterEmulation())
+
+
+@pytest.mark.parametrize("p", [3, 64])
+def test_candidate_search_reference_agrees_with_the_emulation_at_kc_300(p):
+    from tests import knn_edge_refs as ref
+
+    ref.check_candidates_separated(_FilterEmulation(), 4500, p, 300, cap=3 * 300 + 64)
+
+
+@pytest.mark.parametrize("n_bw", [1, 20, 64])
+@pytest.mark.parametrize("p", [1, 63, 64, 65, 256])
+@pytest.mark.parametrize("n", [3, 5, 67, 300])
+def test_bandwidth_reference_agrees_with_the_tensor_formulation(n, p, n_bw):
+    import torch
+
+    from tests import knn_edge_refs as ref
+
+    X, G = ref.irregular_graph(n, p)
+    want = ref.check_bandwidth(BE, X, G, n_bw, direct=False)
+    assert bool(torch.isnan(want).any()) and bool(torch.isfinite(want).any())
+
+
+@pytest.mark.parametrize("n_bw", [1, 10, 20])
+def test_bandwidth_reference_agrees_with_the_tensor_formulation_on_tied_keys(n_bw):
+    from tests import knn_edge_refs as ref
+
+    X, G = ref.tied_graph()
+    ref.check_bandwidth(BE, X, G, n_bw, min_gap=None, direct=False)
+
+
+@pytest.mark.parametrize("listers", [63, 64, 65, 4095, 4096, 4097])
+def test_bandwidth_reference_agrees_with_the_tensor_formulation_on_hubs(listers):
+    from tests import knn_edge_refs as ref
+
+    X, G = ref.hub_graph(listers)
+    ref.check_bandwidth(BE, X, G, 20, cells=None if listers < 100 else ref.hub_sample(G, listers), direct=False)
+
+
+def test_bandwidth_reference_gaps_on_the_buffer_boundary_graphs():
+    """(the two 8k graphs run on the GPU only: here the condition on their input)"""
+    from tests import knn_edge_refs as ref
+
+    for listers in (8193, 8194):
+        X, G = ref.hub_graph(listers, private=False)
+        want, gap = ref.bandwidth_reference(X, G.indptr, G.indices, 20, ref.hub_sample(G, listers))
+        assert gap > 1e-9 and np.isnan(want[0]) and np.isfinite(want[1:]).all()
+
+
+@pytest.mark.parametrize("k", [2, 3, 21])
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_umap_oracle_agrees_with_the_tensor_bisection(n, k):
+    from tests import knn_edge_refs as ref
+
+    ref.check_umap(BE, n, k, backend=None)
