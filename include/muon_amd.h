@@ -727,6 +727,30 @@ size_t mu_ica_worksize(int64_t n, int k, int max_blocks);
 int mu_ica_sweep_f64(int64_t n, int k, int64_t ldz, const double* d_Z, const double* d_W, int fun, double alpha,
                      double* d_A, double* d_gp, void* d_work, size_t work_bytes, int max_blocks, void* stream);
 
+/* ---- muon.atac.tl.rank_peaks_groups: per-group statistics of every peak (scanpy's rank_genes_groups under
+ * /root/reference/muon/_atac/tools.py:337-373; csrc/rank.hip, C-ABI v802) ------------------------------------------------
+ * Both take X^T as a CSR (d rows = peaks, d_cells = the cell of every entry, n_cells columns) and d_labels [n_cells]:
+ * 0 .. n_buckets - 1 is the cell's bucket, -1 leaves the cell out entirely.  1 <= n_buckets <= mu_group_moments_max_groups()
+ * = 64.  Outputs are [d x n_buckets] row-major, written once; no atomics: two calls agree bit for bit.  A row longer than
+ * mu_rank_row_cap() entries is split over the four waves of its workgroup and the pieces are joined in piece order.
+ * n_cells < 2^31, and no row may hold 2^31 entries or more (a canonical CSR has at most n_cells per row): positions and
+ * counts inside a row are 32-bit, ranks and sums are formed in f64 from them.
+ *   mu_group_moments: d_sum / d_sumsq (f64 whatever the value type) and d_nnz = number of stored values != 0 (NaN counts,
+ *     an explicitly stored zero does not) of the entries of bucket b in row j.
+ *   mu_rank_sums: every row's entries must be sorted ascending by value (d_cells permuted alike).  Ranks are those of the
+ *     row over the n_kept labelled cells, ties averaged, the implicit and the explicitly stored zeros forming one tie block
+ *     between the negative and the positive values.  d_ranksum[j][b]: sum of the ranks of the stored non-zero entries of
+ *     bucket b; d_zero_rank[j]: the rank of the zero block; d_tie[j]: sum over the tie blocks of t^3 - t, the zero block
+ *     included.  The caller adds (n_b - nnz[j][b]) * zero_rank[j].  n_kept: the number of labels >= 0. */
+int mu_group_moments_max_groups(void);
+int mu_rank_row_cap(void);
+int mu_group_moments(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_buckets, const int64_t* d_indptr,
+                     const int32_t* d_cells, const void* d_values, const int32_t* d_labels, double* d_sum,
+                     double* d_sumsq, int64_t* d_nnz, void* stream);
+int mu_rank_sums(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_buckets, int64_t n_kept,
+                 const int64_t* d_indptr, const int32_t* d_cells, const void* d_values, const int32_t* d_labels,
+                 double* d_ranksum, double* d_zero_rank, double* d_tie, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

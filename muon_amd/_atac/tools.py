@@ -34,6 +34,8 @@ from .._trace import phase
 from .preproc import canonical_csr, resident, upload_canonical  # noqa: F401
 from .fragments import (FragmentTable, count_fragments_features, fragments_from_arrays,  # noqa: F401
                         locate_fragments, nucleosome_signal, tss_enrichment)
+from .rank import (add_genes_peaks_groups, add_peak_annotation, rank_genes_groups,  # noqa: F401
+                   rank_peaks_groups)
 
 logger = logging.getLogger("muon_amd")
 

@@ -1581,6 +1581,53 @@ class HipBackend:
                                             _p(work), wb, int(max_blocks), self._stream()))
         return A, gp
 
+    # -- muon.atac.tl.rank_peaks_groups (csrc/rank.hip; muon_amd/_atac/rank.py tests for these with hasattr) -----------
+    def group_moments_max_groups(self) -> int:
+        """The most buckets the two kernels take (more: the tensor formulation)."""
+        return int(self.lib.mu_group_moments_max_groups())
+
+    def rank_row_cap(self) -> int:
+        """Rows of X^T longer than this are split over the waves of a workgroup."""
+        return int(self.lib.mu_rank_row_cap())
+
+    def _rank_args(self, Xt: DeviceCSR, labels, n_buckets: int):
+        d, n = Xt.shape
+        if labels.dtype != torch.int32 or int(labels.numel()) != n:
+            raise TypeError("labels: int32, one per column of Xt")
+        if not 1 <= int(n_buckets) <= self.group_moments_max_groups():
+            raise ValueError(f"n_buckets must be 1..{self.group_moments_max_groups()}, got {n_buckets}")
+        if Xt.indptr.dtype != torch.int64 or Xt.indices.dtype != torch.int32:
+            raise TypeError("Xt: indptr int64, indices int32")
+        return d, n, Xt.indptr.contiguous(), Xt.indices.contiguous(), Xt.values.contiguous(), labels.contiguous()
+
+    def group_moments(self, Xt: DeviceCSR, labels, n_buckets: int):
+        """``(sum f64, sumsq f64, nnz int64)``, each [d, n_buckets], of the rows of ``Xt`` (X^T as a CSR: rows are the
+        features, indices the cells) per bucket of ``labels`` (int32 per cell: 0 .. n_buckets - 1, or -1 = the cell is
+        left out).  ``nnz`` counts the stored values that are not zero (NaN counts).  Two calls agree bit for bit."""
+        d, n, indptr, cells, values, labels = self._rank_args(Xt, labels, n_buckets)
+        B = int(n_buckets)
+        s, ss = self.empty((d, B), torch.float64), self.empty((d, B), torch.float64)
+        cnt = self.empty((d, B), torch.int64)
+        with self._dev_ctx():
+            check(self.lib.mu_group_moments(_dt(values), d, n, int(cells.numel()), B, _p(indptr), _p(cells), _p(values),
+                                            _p(labels), _p(s), _p(ss), _p(cnt), self._stream()))
+        return s, ss, cnt
+
+    def rank_sums(self, Xt_sorted: DeviceCSR, labels, n_buckets: int):
+        """``(ranksum [d, n_buckets], zero_rank [d], tie [d])``, f64, of ``Xt_sorted``: X^T as a CSR whose rows are
+        sorted ascending by VALUE (indices permuted alike).  Ranks are tie-averaged over the cells with a label >= 0; the
+        implicit and the stored zeros are one tie block at ``zero_rank``; ``ranksum`` covers the stored non-zero entries
+        of every bucket, ``tie`` is the sum of t^3 - t over the tie blocks.  Two calls agree bit for bit."""
+        d, n, indptr, cells, values, labels = self._rank_args(Xt_sorted, labels, n_buckets)
+        B = int(n_buckets)
+        n_kept = int((labels >= 0).sum().item())
+        rs = self.empty((d, B), torch.float64)
+        zr, tie = self.empty((d,), torch.float64), self.empty((d,), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_rank_sums(_dt(values), d, n, int(cells.numel()), B, n_kept, _p(indptr), _p(cells),
+                                        _p(values), _p(labels), _p(rs), _p(zr), _p(tie), self._stream()))
+        return rs, zr, tie
+
     def mofa_jaakkola(self, zeta, a, b):
         """Bernoulli pseudo-data precision 2 lambda(xi), xi^2 = zeta^2 + a - b, written over ``a``."""
         assert zeta.is_contiguous() and a.is_contiguous() and b.is_contiguous() and a.shape == zeta.shape == b.shape

@@ -158,6 +158,10 @@ SIGNATURES = {
     "mu_ica_max_components": (C.c_int, []),
     "mu_ica_worksize": (_sz, [_i64, _i32, _i32]),
     "mu_ica_sweep_f64": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _i32, _dbl, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "mu_group_moments_max_groups": (C.c_int, []),
+    "mu_rank_row_cap": (C.c_int, []),
+    "mu_group_moments": (C.c_int, [_i32, _i64, _i64, _i64, _i32] + [_vp] * 8),
+    "mu_rank_sums": (C.c_int, [_i32, _i64, _i64, _i64, _i32, _i64] + [_vp] * 8),
     "mu_synth_row_nnz": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp]),
     "mu_synth_fill": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp, _vp, _vp]),
 }
