@@ -375,6 +375,21 @@ int mu_spmm_stream_ranges_f32(int64_t n_pos, const int64_t* d_sptr, const void* 
 int mu_spmm_stream_f64(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, const void* d_ent,
                        const int32_t* d_perm, int k_layout, const double* d_Q, int B, double* d_Y,
                        int accumulate, void* stream);
+/* r08 - the width of the Q slabs as an argument.  mu_spmm_stream_f32 / mu_spmm_stream_ranges_f32 sweep the columns in
+ * slabs of 256 (2 x 64 KiB of LDS at B = 64); the B = 64 kernels for K >= 6 row-sets per wave also exist with slabs of
+ * 320 columns (2 x 80 KiB: all of a gfx950 CU's LDS), which pays the per-pass costs of a (row-set, slab) 20 % less often.
+ * A row's entries are accumulated in column order whatever the width: the products are bit-identical.
+ * slab_cols = 256: the entries above.  slab_cols = 320: an error unless B = 64 and the K in effect (k_layout, or the
+ * tune key "spmm_k") is 6, 7 or 8.  Any other width is an error.  mu_spmm_stream_slab_ok: 1 if (B, K, slab_cols) has an
+ * instance, else 0.  The host decides (HipBackend.spmm_slab; tune key "spmm_slab": 0 decide, 256 / 320 force). */
+int mu_spmm_stream_slab_ok(int B, int K, int slab_cols);
+int mu_spmm_stream_slab_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, const void* d_ent,
+                            const int32_t* d_perm, int k_layout, const float* d_Q, int B, float* d_Y,
+                            int slab_cols, void* stream);
+int mu_spmm_stream_ranges_slab_f32(int64_t n_pos, const int64_t* d_sptr, const void* d_ent, const int32_t* d_perm,
+                                   int k_layout, const float* d_Q, int64_t q_rows, float* d_Y, int64_t y_stride,
+                                   const uint32_t* d_tbl, int64_t tbl_stride, int n_ranges, const int32_t* h_ranges5,
+                                   int per_wg, int slab_cols, void* stream);
 
 
 /* ---- narrow-block SpMM on a sliced-ELL operand (r04; csrc/spmm_ell.hip) -------------------------------------
@@ -421,6 +436,7 @@ int mu_ell16_fill(int64_t n_groups, int64_t n_cols, int64_t nnz, int slab_cols, 
 
 /* Tuning / ablation knobs (tests and bench only; all default to 0 = what ships):
  *   "spmm_k"     row-sets per wave of the packed SpMM (0 = automatic)
+ *   "spmm_slab"  Q slab width of the row-stream SpMM the host asks for: 0 decide, 256 / 320 force (320 where it exists)
  *   "spmm_waves" waves per workgroup of the packed SpMM: 16 (default), 12, 8
  *   "spmm_pipe"  software pipelining level of the packed SpMM
  *   "spmm_mode"  timing ablations of the packed SpMM (bit mask; results are then WRONG)

@@ -174,6 +174,30 @@ def pick_block(width: int) -> int:
     )
 
 
+SLAB_NARROW, SLAB_WIDE = 256, 320
+
+
+def spmm_slab_cols(lib, B: int, K: int, dtype, force: int = 0, mode: int = 0, ranged: bool = False) -> int:
+    """Q slab width of a row-stream product (csrc/spmm_win.hip): 256 columns, or 320 where the library has such an
+    instance - f32 blocks of 64 columns on a layout of K >= 6 row-sets per wave (mu_spmm_stream_slab_ok); the products
+    are bit-identical.  ``K`` is the K the launch will run with, ``force`` the tune key spmm_slab: 0 decide, 256 / 320
+    that width where an instance exists (a forced 320 without one falls back to 256, it is never an error).
+    ``mode`` is the tune key spmm_mode: the timing ablations are 256-column instances, except the cycle accounting
+    (mode 64) at K = 8, which exists at both widths.
+    The rule: 320 wherever it exists.  Measured (profiles/r08_spmm_slab_step_ab.md): the plain products at
+    10^6 x 200 000 (X Q at K = 6, X^T Y at K = 7), 125 000 x 200 000, 600 000 x 200 000 at density 0.05 and on the
+    unstructured generator - 320 is faster on every one; the ``ranged`` products of the warm start at the 10^6 x 200 000
+    shapes (K = 8 and K = 7) - 320 does not lose there (3-4 % less on average, inside the spread of six launches).
+    No shape was found where 320 is slower, so there is no density gate."""
+    if force not in (0, SLAB_NARROW, SLAB_WIDE):
+        raise ValueError(f"spmm_slab must be 0, {SLAB_NARROW} or {SLAB_WIDE}, not {force}")
+    if dtype != torch.float32 or force == SLAB_NARROW:
+        return SLAB_NARROW
+    if mode != 0 and not (mode == 64 and K == 8 and not ranged):
+        return SLAB_NARROW
+    return SLAB_WIDE if lib.mu_spmm_stream_slab_ok(int(B), int(K), SLAB_WIDE) == 1 else SLAB_NARROW
+
+
 def ell16_layout(X: DeviceCSR, waves: int = 15, slab_cols: int = 1024, slab_ptr_fn=None, fill_fn=None) -> "DeviceEll":
     """The sliced-ELL layout of csrc/spmm_ell.hip (built once per fit).  See DeviceEll / include/muon_amd.h for the
     format.  ``slab_cols`` = 1024 for f32 blocks, 512 for f64 blocks (a slab is 64 KiB of Q rows).  As tensor
@@ -1051,9 +1075,15 @@ class HipBackend:
         for r in range(ny):  # (the super-slabs r g .. (r + 1) g - 1 are contiguous in the columns and in every row)
             h[5 * r:5 * r + 5] = [r * g * 8192, min((r + 1) * g * 8192, d), r * g * 8192, r * g, min((r + 1) * g, ns)]
         with self._dev_ctx():
-            check(self.lib.mu_spmm_stream_ranges_f32(n_s, _p(S["sptr"]), _p(S["ent"]), None, S["K"], _p(Q), d, _p(part),
-                                                     n_s * 64, _p(S["rel"]), n_s, ny, h, 1, self._stream()))
+            check(self.lib.mu_spmm_stream_ranges_slab_f32(n_s, _p(S["sptr"]), _p(S["ent"]), None, S["K"], _p(Q), d,
+                                                          _p(part), n_s * 64, _p(S["rel"]), n_s, ny, h, 1,
+                                                          self.spmm_slab_ranged(S["K"]), self._stream()))
         return part[0] if ny == 1 else part.sum(dim=0)
+
+    def spmm_slab_ranged(self, k_layout: int) -> int:
+        """The slab width of a ranged product (B = 64, f32; the ranged entry takes the layout's K as it is and has no
+        ablation modes)."""
+        return spmm_slab_cols(self.lib, 64, k_layout, torch.float32, self.lib.mu_tune_get(b"spmm_slab"), ranged=True)
 
     def spmm_slice_t(self, Xt: DeviceStream, plan, Ys: torch.Tensor) -> torch.Tensor:
         """Z = X_S^T Y_S [d x B] on the row stream of X^T as it is: the slice's cells are <= 16 contiguous pieces of
@@ -1077,9 +1107,9 @@ class HipBackend:
             h[5 * i:5 * i + 5] = [r["row0"], r["row1"], q_off, r["g0"], r["g1"]]
             q_off += r["row1"] - r["row0"]
         with self._dev_ctx():
-            check(self.lib.mu_spmm_stream_ranges_f32(Xt.n_pos, _p(Xt.sptr), _p(Xt.ent), _p(Xt.perm), Xt.k, _p(Ys),
-                                                     plan["n_s"], _p(Z), 0, _p(t4["cnt"]), t4["stride"], len(rg), h,
-                                                     len(rg), self._stream()))
+            check(self.lib.mu_spmm_stream_ranges_slab_f32(Xt.n_pos, _p(Xt.sptr), _p(Xt.ent), _p(Xt.perm), Xt.k, _p(Ys),
+                                                          plan["n_s"], _p(Z), 0, _p(t4["cnt"]), t4["stride"], len(rg), h,
+                                                          len(rg), self.spmm_slab_ranged(Xt.k), self._stream()))
         return Z
 
     def split_streams(self, X: DeviceCSR):
@@ -1290,6 +1320,15 @@ class HipBackend:
     def tune(self, key: str, value: int) -> None:
         check(self.lib.mu_tune_set(key.encode(), int(value)))
 
+    def spmm_slab(self, k_layout: int, n_pos: int, B: int, dtype=torch.float32) -> int:
+        """The slab width for a product on a row stream dealt for ``k_layout`` row-sets per wave (0: the library picks
+        K from n_pos) - spmm_slab_cols with the K in effect (tune key spmm_k) and the tune key spmm_slab."""
+        lib = self.lib
+        K = lib.mu_tune_get(b"spmm_k")
+        if not 1 <= K <= 8:
+            K = k_layout if 1 <= k_layout <= 8 else lib.mu_spmm_stream_k(n_pos)
+        return spmm_slab_cols(lib, B, K, dtype, lib.mu_tune_get(b"spmm_slab"), lib.mu_tune_get(b"spmm_mode"))
+
     def spmm(self, X, Q: torch.Tensor, out=None, accumulate: bool = False) -> torch.Tensor:
         n, d = X.shape
         B = Q.shape[1]
@@ -1321,8 +1360,9 @@ class HipBackend:
                     check(self.lib.mu_spmm_stream_f64(X.n_pos, d, _p(X.sptr), _p(X.ent), _p(X.perm), X.k,
                                                       _p(Q), B, _p(out), int(bool(accumulate)), self._stream()))
                 else:
-                    check(self.lib.mu_spmm_stream_f32(X.n_pos, d, _p(X.sptr), _p(X.ent), _p(X.perm), X.k,
-                                                      _p(Q), B, _p(out), self._stream()))
+                    check(self.lib.mu_spmm_stream_slab_f32(X.n_pos, d, _p(X.sptr), _p(X.ent), _p(X.perm), X.k,
+                                                           _p(Q), B, _p(out), self.spmm_slab(X.k, X.n_pos, B),
+                                                           self._stream()))
             return out
         if X.values.dtype != Q.dtype:
             raise TypeError("spmm needs values and dense block of one dtype")

@@ -91,6 +91,9 @@ SIGNATURES = {
     "mu_spmm_stream_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp]),
     "mu_csr_slice_stream": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mu_spmm_stream_ranges_f32": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp]),
+    "mu_spmm_stream_slab_ok": (C.c_int, [_i32, _i32, _i32]),
+    "mu_spmm_stream_slab_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp]),
+    "mu_spmm_stream_ranges_slab_f32": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
     "mu_tpack4_cnt_offset": (_sz, [_i64, _i64, _i64]),
     "mu_tperm_stage_pairs": (C.c_int, []),
     "mu_tperm_plan": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -19,7 +19,8 @@
 // its 4 MiB).
 //
 // Kernel structure (one 1024-thread workgroup = 64*K rows, K <= 8, per CU):
-//   * the columns of X are swept in slabs of 256; the slab's 256 Q rows (64 KiB at B = 64) are
+//   * the columns of X are swept in slabs of 256 (r08: 320 in the k_spmm_wide instances, B = 64 and K >= 6);
+//     the slab's 256 Q rows (64 KiB at B = 64; 320 rows = 80 KiB) are
 //     copied to LDS by LDS-DMA, double buffered; a wave issues its 1 KiB pieces of the NEXT slab
 //     one per pass, not as one burst (the burst kept every wave ~200 cycles per pass in the issue
 //     queue of the texture path and delayed the window requests queued behind it);
@@ -41,7 +42,11 @@
 
 namespace {
 
-constexpr int kSlabCols = 256;   // Q rows per slab: 256 x 256 B = 64 KiB, double buffered
+constexpr int kSlabNarrow = 256;  // Q rows per slab: 256 x 256 B = 64 KiB, double buffered
+// r08: the B = 64 f32 instances for K >= 6 also exist with slabs of 320 columns - 2 x 320 x 256 B is all of the CU's
+// 160 KiB of LDS; a slab is a whole number of 16 x 1 KiB DMA pieces, i.e. a multiple of 64 columns: 320 is the only step
+// above 256.  The work per stored entry is the same, the work per (row-set, slab) pass is paid 20 % less often.
+constexpr int kSlabWide = 320;
 constexpr int kWaves = 16;
 constexpr int kKMax = 8;
 constexpr int kNX = 110;         // hipcc owns v[0 .. kNX-1] (amdgpu_num_vgpr(55)), the asm v[kNX .. kNX+2K-1]
@@ -210,7 +215,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 //   * X_S Q on a compact stream of the slice's rows with the COLUMN SLABS SPLIT over blockIdx.y (a slice of a few
 //     thousand rows is a handful of workgroups: each would sweep all 782 slabs on 1/20 of the chip): 8192-column
 //     super-slabs from the slab pointers, partial products per blockIdx.y, summed in fixed order by the caller.
-// A range may start at any column: its slabs are the 256 columns from there on (LDS row = (column - start) mod 256).
+// A range may start at any column: its slabs are the 256 columns from there on (LDS row = (column - start) mod 256;
+// the 320-column instances: column - first column of the slab).
 constexpr int kMaxRanges = 32;
 struct WinRange {
   int col0, col1;  // columns [col0, col1) of the operand's index space
@@ -236,7 +242,8 @@ struct Win {      // what stage A of a pass hands to stage B
 // (results are then wrong on purpose): 1 no LDS gathers / FMAs, 8 no window requests (and no
 // overflow passes), 32 window slots 0-7 as two batches of four LDS reads (r01), 64 per-wave cycle
 // accounting instead of the product.
-template <int K, int MODE, int NB, typename DT, bool RNG = false>
+// SLAB = columns per slab: kSlabNarrow, or kSlabWide (NB = 4, f32, K >= 6 only: k_spmm_wide / k_spmm_wide_rng).
+template <int K, int MODE, int NB, typename DT, bool RNG = false, int SLAB = kSlabNarrow>
 __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
                                               const int64_t* __restrict__ sptr,
                                               const unsigned long long* __restrict__ ent,
@@ -246,11 +253,15 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
   static_assert(K >= 1 && K <= kKMax, "K out of range");
   static_assert(sizeof(DT) == 4 || MODE == 0, "the timing ablations exist for f32 only");
   constexpr int W = kWaves;
+  constexpr int kSlabCols = SLAB;
+  constexpr bool kPow2 = (kSlabCols & (kSlabCols - 1)) == 0;
+  static_assert(kSlabCols % 64 == 0, "a slab is a whole number of 16 x 1 KiB pieces at B = 64");
   typedef typename Vec<NB, DT>::type acc_t;
   constexpr int kRowBytes = 16 * NB * (int)sizeof(DT);       // one Q row: 16 NB elements (64 .. 256 B)
   constexpr int kSlabBytes = kSlabCols * kRowBytes;          // 64 / 32 / 16 KiB
   constexpr int kRowShift = kRowBytes == 256 ? 8 : (kRowBytes == 128 ? 7 : 6);
   static_assert(kRowBytes <= 256, "a Q row is at most 256 bytes");
+  static_assert(2 * kSlabBytes <= 160 * 1024, "the double-buffered slab fits the CU's LDS");
   constexpr int kPieces = kSlabBytes / 1024;                 // 1 KiB LDS-DMA pieces per slab
   constexpr int kMyPieces = kPieces / W;                     // per wave and slab: 4 / 2 / 1
   static_assert(kPieces % W == 0, "every wave issues the same number of DMA pieces");
@@ -310,7 +321,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
   const unsigned q4_last = (unsigned)(q4_total - 1);
   // MODE & 64: per-wave cycle accounting (s_memtime) of the places a pass can spend time in;
   // the passes run unpipelined (A(k) then B(k)) and the sums replace the product in Y.
-  unsigned t_wait = 0, t_a = 0, t_b = 0, t_bar = 0, t_dma = 0;
+  unsigned t_wait = 0, t_a = 0, t_b = 0, t_bar = 0, t_dma = 0, n_rev = 0;  // (n_rev: revisit passes of this wave)
   auto now = [&]() -> unsigned { return (unsigned)__builtin_amdgcn_s_memtime(); };
 
   // RNG: the ranges of this workgroup one after the other - cursors, windows and the first slab are set up again per
@@ -390,7 +401,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
       constexpr bool SLOW = decltype(slowc)::value;
       if constexpr (MODE & 128) {  // stage B alone: a synthetic 12-entry window for every group
         Win ws;
-        ws.a = ((lane * 37 + k * 13 + (int)s0) & (kSlabCols - 1)) << kRowShift;
+        ws.a = (int)((unsigned)(lane * 37 + k * 13 + (int)s0) % (unsigned)kSlabCols) << kRowShift;
         ws.vv = 1.0f;
         // (+ 65536 / 131072: the windows of waves 12-15 / 8-15 are empty - stage B alone on 12 / 8 of the
         //  16 waves, what that many "gather" waves of a wave-specialised kernel could deliver)
@@ -426,7 +437,10 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
       //  time, scripts/probes/spmm_power_probe.py -, and a third of the window slots a pass gathers are
       //  padding: they all read row 0 of the slab instead of whatever row their stale column names, so
       //  the padded gathers return the same bytes again and again)
-      w.a = valid ? (((col - col0) & (kSlabCols - 1)) << kRowShift) : 0;  // (col0 = 0 unless ranged: a range may start anywhere)
+      // (col0 = 0 unless ranged: a range may start anywhere.  A width that is no power of two has no mask: the row is
+      //  the distance from the slab's first column - a range's slabs start at its col0 -, one VALU either way)
+      if constexpr (kPow2) w.a = valid ? (((col - col0) & (kSlabCols - 1)) << kRowShift) : 0;
+      else w.a = valid ? ((col - (int)s0) << kRowShift) : 0;
       w.vv = valid ? __builtin_bit_cast(float, valbits) : 0.f;
       if constexpr (!(MODE & 8)) {
         // entries consumed by this lane's group: the bits of its 16 lanes in the ballot, counted on
@@ -440,7 +454,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
         if (__ballot(cnt == 16u)) again |= 1u << k;
       }
       if constexpr (MODE & 1024) {  // real stage A, synthetic 12-entry window for stage B
-        w.a = ((lane * 37 + k * 13 + (int)s0) & (kSlabCols - 1)) << kRowShift;
+        w.a = (int)((unsigned)(lane * 37 + k * 13 + (int)s0) % (unsigned)kSlabCols) << kRowShift;
         w.vv = 1.0f;
         w.any16 = 0x0fffu;
       }
@@ -632,7 +646,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
           if (pend & (1u << k)) {
             const Win wo = stage_a(kc, std::true_type{});
             unsigned t2 = 0;
-            if constexpr (MODE & 64) { t2 = now(); t_a += t2; }
+            if constexpr (MODE & 64) { t2 = now(); t_a += t2; ++n_rev; }
             stage_b(kc, wo);
             if constexpr (MODE & 64) t_b += now() - t2;
           }
@@ -659,8 +673,8 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
       for (int c = 0; c < NB; ++c) dep += (float)acc[decltype(kc)::value][c];
     });
     if (__ballot(dep == 1.2345e-30f)) t_b += 1;
-    if (lane < 5) {
-      const unsigned t = lane == 0 ? t_wait : lane == 1 ? t_a : lane == 2 ? t_b : lane == 3 ? t_bar : t_dma;
+    if (lane < 6) {
+      const unsigned t = lane == 0 ? t_wait : lane == 1 ? t_a : lane == 2 ? t_b : lane == 3 ? t_bar : lane == 4 ? t_dma : n_rev;
       Y[((int64_t)blockIdx.x * W + wave) * (16 * NB) + lane] = (DT)t;
     }
     return;
@@ -692,6 +706,27 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(55))) void k_s
     int64_t n_pos, const int64_t* __restrict__ sptr, const unsigned long long* __restrict__ ent,
     const int32_t* __restrict__ perm, const float* __restrict__ Q, float* __restrict__ Y, const WinRanges rg) {
   spmm_win_body<K, 0, 4, float, true>(n_pos, 0, sptr, ent, perm, Q, Y, 0, &rg);
+}
+
+// r08 - the 320-column instances (B = 64, f32, K = 6 .. 8; MODE 0, and 64 for the probe's cycle accounting).  The names
+// differ on purpose: the ISA audits count the instances of a family by name.
+// The accounting instance exists for K = 8 only, like the 256-column one: it describes layouts dealt for K = 8
+// (scripts/spmm_probe.py --account), not the K = 6 / 7 instances the bench launches; spmm_mode 64 at K = 6 / 7 with
+// 320 columns is an error of the entry, and the host's rule (spmm_slab_cols) asks for 256 whenever a mode has no wide instance.
+template <int K, int MODE>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(55))) void k_spmm_wide(
+    int64_t n_pos, int64_t n_cols, const int64_t* __restrict__ sptr,
+    const unsigned long long* __restrict__ ent, const int32_t* __restrict__ perm,
+    const float* __restrict__ Q, float* __restrict__ Y) {
+  static_assert(K >= 6, "the wide slab's five DMA pieces per wave need K >= 6 (kMyPieces <= kMid + 2)");
+  spmm_win_body<K, MODE, 4, float, false, kSlabWide>(n_pos, n_cols, sptr, ent, perm, Q, Y, 0);
+}
+template <int K>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(55))) void k_spmm_wide_rng(
+    int64_t n_pos, const int64_t* __restrict__ sptr, const unsigned long long* __restrict__ ent,
+    const int32_t* __restrict__ perm, const float* __restrict__ Q, float* __restrict__ Y, const WinRanges rg) {
+  static_assert(K >= 6, "the wide slab's five DMA pieces per wave need K >= 6");
+  spmm_win_body<K, 0, 4, float, true, kSlabWide>(n_pos, 0, sptr, ent, perm, Q, Y, 0, &rg);
 }
 
 // ---- the row stream ------------------------------------------------------------------------
@@ -895,6 +930,22 @@ int launch(int B, hipStream_t st, int64_t n_pos, int64_t n_cols, const int64_t* 
   return MU_OK;
 }
 
+template <int K, int MODE>
+int launch_wide(hipStream_t st, int64_t n_pos, int64_t n_cols, const int64_t* sptr, const unsigned long long* ent,
+                const int32_t* perm, const float* Q, float* Y) {
+  const int64_t wgs = (n_pos + 64 * K - 1) / (64 * K);
+  hipLaunchKernelGGL((k_spmm_wide<K, MODE>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, sptr, ent, perm, Q, Y);
+  MU_CHECK_LAUNCH();
+  return MU_OK;
+}
+
+// which (B, K) have an instance with slabs of `slab_cols` columns (f32 blocks)
+bool slab_ok(int B, int K, int slab_cols) {
+  if (K < 1 || K > kKMax || !(B == 16 || B == 32 || B == 64)) return false;
+  if (slab_cols == kSlabNarrow) return true;
+  return slab_cols == kSlabWide && B == 64 && K >= 6;
+}
+
 // f32 stored values, f64 dense operand and product (B = 16 / 32)
 template <int K>
 int launch_f64(int B, hipStream_t st, int64_t n_pos, int64_t n_cols, const int64_t* sptr,
@@ -954,10 +1005,19 @@ int mu_csr_stream_fill(int64_t n_pos, const int32_t* d_perm, const int64_t* d_in
   return MU_OK;
 }
 
+int mu_spmm_stream_slab_ok(int B, int K, int slab_cols) { return slab_ok(B, K, slab_cols) ? 1 : 0; }
+
 int mu_spmm_stream_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, const void* d_ent,
                        const int32_t* d_perm, int k_layout, const float* d_Q, int B, float* d_Y,
                        void* stream) {
+  return mu_spmm_stream_slab_f32(n_pos, n_cols, d_sptr, d_ent, d_perm, k_layout, d_Q, B, d_Y, kSlabNarrow, stream);
+}
+
+int mu_spmm_stream_slab_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, const void* d_ent,
+                            const int32_t* d_perm, int k_layout, const float* d_Q, int B, float* d_Y,
+                            int slab_cols, void* stream) {
   MU_REQUIRE(B == 16 || B == 32 || B == 64, "B must be 16, 32 or 64");
+  MU_REQUIRE(slab_cols == kSlabNarrow || slab_cols == kSlabWide, "slab_cols must be 256 or 320");
   MU_REQUIRE(n_pos >= 0 && n_cols > 0 && n_cols < ((int64_t)1 << 31), "shape out of range");
   // (the Q slabs are addressed with 32-bit byte offsets from d_Q)
   MU_REQUIRE((n_cols + 512) * (int64_t)B * 4 < ((int64_t)1 << 32), "dense operand of 4 GiB or more");
@@ -968,7 +1028,23 @@ int mu_spmm_stream_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr, con
   int K = (k_layout >= 1 && k_layout <= kKMax) ? k_layout : pick_k(n_pos);
   const int force_k = mu_tune_get("spmm_k");  // tests / tuning only (mu_tune_set); 0 in production
   if (force_k >= 1 && force_k <= kKMax) K = force_k;
+  if (slab_cols == kSlabWide && !slab_ok(B, K, slab_cols)) {
+    mu_set_error("320-column slabs exist for B = 64 and K >= 6 only (B = %d, K = %d)", B, K);
+    return MU_ERR_ARG;
+  }
   const int mode = mu_tune_get("spmm_mode");
+  if (slab_cols == kSlabWide) {
+    if (mode == 64 && K == 8) return launch_wide<8, 64>(st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y);
+    if (mode != 0) {
+      mu_set_error("spmm_mode %d has no compiled 320-column instance for K = %d", mode, K);
+      return MU_ERR_ARG;
+    }
+    switch (K) {
+      case 6: return launch_wide<6, 0>(st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y);
+      case 7: return launch_wide<7, 0>(st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y);
+      default: return launch_wide<8, 0>(st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y);
+    }
+  }
   // B = 16: the narrow-block kernel (tune spmm_narrow_off = 1: this file's NB = 1 instance, kept for A/B runs)
   if (B == 16 && (mode == 0 || (mode >= 2 && mode <= 6)) && mu_tune_get("spmm_narrow_off") == 0)
     return mu_spmm_narrow_f32_launch(st, n_pos, n_cols, K, d_sptr, ent, d_perm, d_Q, d_Y);
@@ -1040,8 +1116,21 @@ int mu_spmm_stream_ranges_f32(int64_t n_pos, const int64_t* d_sptr, const void* 
                               int k_layout, const float* d_Q, int64_t q_rows, float* d_Y, int64_t y_stride,
                               const uint32_t* d_tbl, int64_t tbl_stride, int n_ranges, const int32_t* h_ranges5,
                               int per_wg, void* stream) {
+  return mu_spmm_stream_ranges_slab_f32(n_pos, d_sptr, d_ent, d_perm, k_layout, d_Q, q_rows, d_Y, y_stride, d_tbl,
+                                        tbl_stride, n_ranges, h_ranges5, per_wg, kSlabNarrow, stream);
+}
+
+int mu_spmm_stream_ranges_slab_f32(int64_t n_pos, const int64_t* d_sptr, const void* d_ent, const int32_t* d_perm,
+                                   int k_layout, const float* d_Q, int64_t q_rows, float* d_Y, int64_t y_stride,
+                                   const uint32_t* d_tbl, int64_t tbl_stride, int n_ranges, const int32_t* h_ranges5,
+                                   int per_wg, int slab_cols, void* stream) {
+  MU_REQUIRE(slab_cols == kSlabNarrow || slab_cols == kSlabWide, "slab_cols must be 256 or 320");
   MU_REQUIRE(n_pos >= 0 && q_rows > 0 && n_ranges >= 1 && n_ranges <= kMaxRanges && per_wg >= 1, "shape out of range");
   MU_REQUIRE(k_layout >= 1 && k_layout <= kKMax, "the layout's K is needed");
+  if (slab_cols == kSlabWide && !slab_ok(64, k_layout, slab_cols)) {
+    mu_set_error("320-column slabs exist for B = 64 and K >= 6 only (B = 64, K = %d)", k_layout);
+    return MU_ERR_ARG;
+  }
   MU_REQUIRE((q_rows + 512) * (int64_t)64 * 4 < ((int64_t)1 << 32), "dense operand of 4 GiB or more");
   if (n_pos == 0) return MU_OK;
   MU_REQUIRE(d_sptr && d_ent && d_Q && d_Y && d_tbl && h_ranges5, "null pointer");
@@ -1065,7 +1154,14 @@ int mu_spmm_stream_ranges_f32(int64_t n_pos, const int64_t* d_sptr, const void* 
   const unsigned long long* ent = (const unsigned long long*)d_ent;
 #define MU_RNG(K_)                                                                                                   \
   hipLaunchKernelGGL((k_spmm_win_rng<K_>), dim3(wgs, ny), dim3(1024), 0, st, n_pos, d_sptr, ent, d_perm, d_Q, d_Y, rg)
-  switch (K) {
+#define MU_RNG_WIDE(K_)                                                                                              \
+  hipLaunchKernelGGL((k_spmm_wide_rng<K_>), dim3(wgs, ny), dim3(1024), 0, st, n_pos, d_sptr, ent, d_perm, d_Q, d_Y, rg)
+  if (slab_cols == kSlabWide) switch (K) {
+    case 6: MU_RNG_WIDE(6); break;
+    case 7: MU_RNG_WIDE(7); break;
+    default: MU_RNG_WIDE(8); break;
+  }
+  else switch (K) {
     case 1: MU_RNG(1); break;
     case 2: MU_RNG(2); break;
     case 3: MU_RNG(3); break;
@@ -1076,6 +1172,7 @@ int mu_spmm_stream_ranges_f32(int64_t n_pos, const int64_t* d_sptr, const void* 
     default: MU_RNG(8); break;
   }
 #undef MU_RNG
+#undef MU_RNG_WIDE
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

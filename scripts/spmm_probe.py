@@ -22,18 +22,24 @@ ap.add_argument("--no-packed", action="store_true")
 ap.add_argument("--B", type=int, default=64)
 ap.add_argument("--ks", default="", help="also time layouts dealt for these K (row-sets per wave)")
 ap.add_argument("--k-modes", default="", help="ablation modes to time on the --ks layouts as well")
+ap.add_argument("--slab", type=int, default=0, choices=(0, 256, 320),
+                help="Q slab width (tune key spmm_slab): 0 = the backend's rule, 256 / 320 forced where an instance exists")
+ap.add_argument("--account", action="store_true",
+                help="cycle accounting (spmm_mode 64) of both directions on layouts dealt for K = 8, at the --slab width")
+ap.add_argument("--density", type=float, default=0.03)
 ap.add_argument("--calibrate", action="store_true",
                 help="run a 4 GiB device copy first (known HBM byte count for PMC calibration)")
 args = ap.parse_args()
 
 be = HipBackend(0)
+be.tune("spmm_slab", args.slab)
 if args.calibrate:
     src = torch.empty(1 << 30, dtype=torch.float32, device="cuda").normal_()
     dst = torch.empty_like(src)
     dst.copy_(src)  # reads 4 GiB, writes 4 GiB (far beyond the 256 MiB Infinity Cache)
     torch.cuda.synchronize()
     del src, dst
-X = be.synth_counts(0, args.cells, args.peaks, 50, 0.03, 0)
+X = be.synth_counts(0, args.cells, args.peaks, 50, args.density, 0)
 print(f"planted-topic {args.cells} x {args.peaks}, nnz {X.nnz}", flush=True)
 T = tfidf_device(be, X, args.cells, 3, 1e4)
 
@@ -78,20 +84,48 @@ def bench(name, M, D):
 bench("X*Q  stream      ", Ts, Q)
 bench("Xt*Y stream      ", Tts, Yn)
 names = ["wait window", "stage A", "stage B", "barrier+dma wait", "dma issue"]
+
+
+def account(M, D, tag):
+    """spmm_mode 64 on M (dealt for K = 8): cycles per pass and wave of the five phases, passes and revisits per wave."""
+    width = be.spmm_slab(M.k, M.n_pos, B)
+    be.tune("spmm_mode", 64)
+    t = be.spmm(M, D)
+    be.tune("spmm_mode", 0)
+    nw = M.n_pos // (64 * M.k) * 16
+    tt = t.reshape(-1)[: nw * B].reshape(nw, B)[:, :6].double()
+    passes = -(-M.shape[1] // width) * M.k
+    rev = float(tt[:, 5].mean())
+    print(f"{tag} slab {width}: passes per wave {passes}, revisits per wave {rev:.1f} ({rev / passes:.3f} per pass); cycles per "
+          "pass and wave: " + ", ".join(f"{n} {float(tt[:, i].mean()) / passes:7.1f}" for i, n in enumerate(names))
+          + f"; sum {float(tt[:, :5].sum(dim=1).mean()) / passes:7.1f}; per wave and launch {float(tt[:, :5].sum(dim=1).mean()):.0f}",
+          flush=True)
+
+
+if args.account:
+    A8, At8 = be.stream(T, K=8), be.transpose_stream(T, K=8)
+    bench(f"X*Q  stream K=8 ({A8.n_pos // 512} workgroups)", A8, Q)
+    bench(f"Xt*Y stream K=8 ({At8.n_pos // 512} workgroups)", At8, Yn)
+    account(A8, Q, "X*Q ")
+    account(At8, Yn, "Xt*Y")
+    del A8, At8
 for M, D, tag in ((Ts, Q, "X*Q "), (Tts, Yn, "Xt*Y")):
     if M.k != 8 and not all(int(m) in (4096, 16384, 262144) for m in args.modes.split(",") if m):
         continue
     for mode in [int(m) for m in args.modes.split(",") if m]:
         be.tune("spmm_mode", mode)
+        be.tune("spmm_slab", args.slab if mode == 64 else 256)  # (the accounting is the only ablation with a 320-column instance)
         bench(f"{tag} stream mode {mode:2d}", M, D)
         if mode & 64:
             t = be.spmm(M, D)
             nw = M.n_pos // (64 * M.k) * 16
             tt = t.reshape(-1)[: nw * B].reshape(nw, B)[:, :5].double()
-            passes = (M.shape[1] + 255) // 256 * M.k
+            width = be.spmm_slab(M.k, M.n_pos, B)
+            passes = -(-M.shape[1] // width) * M.k
             print("   cycles per pass and wave: " + ", ".join(f"{n} {float(tt[:, i].mean()) / passes:7.1f}" for i, n in enumerate(names))
                   + f"; sum {float(tt.sum(dim=1).mean()) / passes:7.1f}", flush=True)
     be.tune("spmm_mode", 0)
+    be.tune("spmm_slab", args.slab)
 
 for K in [int(k) for k in args.ks.split(",") if k]:
     for mode in [0] + [int(m) for m in args.k_modes.split(",") if m]:
