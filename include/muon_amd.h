@@ -767,6 +767,35 @@ int mu_rank_sums(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_bucke
                  const int64_t* d_indptr, const int32_t* d_cells, const void* d_values, const int32_t* d_labels,
                  double* d_ranksum, double* d_zero_rank, double* d_tie, void* stream);
 
+/* ---- muon.tl.snf: similarity network fusion (/root/reference/muon/_core/tools.py:716-920; csrc/snf.hip, C-ABI v804) ----
+ * Every matrix is n x n row-major f64 with a leading dimension >= n; what lies past column n of a row is never read into
+ * a result.  No atomics: two calls agree bit for bit.  Arguments are checked before any HIP call.
+ *   mu_snf_affinity_f64: d_W = _affinity_matrix(d_D, k, sigma): D <- (D + D^T) / 2 with a zero diagonal, means_i = mean of
+ *     the finite values among the 2nd .. (k+1)-th smallest of row i, + eps (d_means [n], written), sig = (means_i +
+ *     means_j) / 3 + D / 3 + eps, W = N(0, sigma sig).pdf(D).  d_W may be d_D.  1 <= k <= mu_snf_affinity_max_k() = 127,
+ *     n <= 65535.
+ *   mu_snf_normalize_f64: r_i = sum_j x_ij - x_ii, 1 where that is 0 (d_r [n], written); out_ij = (x_ij / (2 r_i) +
+ *     x_ji / (2 r_j)) / 2, diagonal 0.5: symmetric bit for bit.  d_out may be d_X (one read, one write of the matrix).
+ *   mu_snf_topk_f64: the k largest of every row with their columns, descending: d_idx / d_val [n x k].
+ *     1 <= k <= mu_snf_max_k() = 64, k <= n.  Equal values: in no promised order.
+ *   mu_snf_p_scale_f64: on the CSR of z (n rows): d_rowsum[i] = sum of row i in stored order (compensated), then every
+ *     entry (i, j) is divided by d_rowsum[j], in place - the reference's `z / z.sum(axis=1)`.
+ *   mu_snf_diffuse_f64: Y = (P X)^T, P the CSR (d_indptr int64, d_cols int32, d_vals), X = (X_0 + .. + X_{nmat-1}) / nmat
+ *     formed while it is read (h_X: HOST array of nmat device pointers, all with the leading dimension ldx, added in this
+ *     order), the entries of a row of P added in stored order.  1 <= nmat <= mu_snf_max_terms() = 8; d_Y is none of the
+ *     terms.  Twice in a row it gives P S P^T for a symmetric S. */
+int mu_snf_max_k(void);
+int mu_snf_affinity_max_k(void);
+int mu_snf_max_terms(void);
+int mu_snf_affinity_f64(int64_t n, int k, int64_t ldd, const double* d_D, int64_t ldw, double* d_W, double sigma,
+                        double eps, double* d_means, void* stream);
+int mu_snf_normalize_f64(int64_t n, int64_t ldx, const double* d_X, int64_t ldo, double* d_out, double* d_r, void* stream);
+int mu_snf_topk_f64(int64_t n, int k, int64_t ldw, const double* d_W, int32_t* d_idx, double* d_val, void* stream);
+int mu_snf_p_scale_f64(int64_t n, int64_t nnz, const int64_t* d_indptr, const int32_t* d_cols, double* d_vals,
+                       double* d_rowsum, void* stream);
+int mu_snf_diffuse_f64(int64_t n, int nmat, const void* const* h_X, int64_t ldx, const int64_t* d_indptr,
+                       const int32_t* d_cols, const double* d_vals, int64_t ldy, double* d_Y, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

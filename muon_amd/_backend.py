@@ -13,6 +13,7 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -1620,6 +1621,107 @@ class HipBackend:
             check(self.lib.mu_ica_sweep_f64(n, k, ld, _p(Z), _p(W), self._ICA_FUN[fun], float(alpha), _p(A), _p(gp),
                                             _p(work), wb, int(max_blocks), self._stream()))
         return A, gp
+
+    # -- muon.tl.snf (csrc/snf.hip; muon_amd/_core/snf.py tests for these with hasattr) --------------------------------
+    def free_memory(self) -> int:
+        """Bytes the device can still hand out: what the driver reports free plus what torch's allocator holds unused."""
+        with self._dev_ctx():
+            free, _total = torch.cuda.mem_get_info(self.device)
+            held = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        return int(free) + int(held)
+
+    def snf_max_k(self) -> int:
+        """The widest dominate set ``snf_topk`` selects (more: ``torch.topk``)."""
+        return int(self.lib.mu_snf_max_k())
+
+    def snf_affinity_max_k(self) -> int:
+        """The most neighbours ``snf_affinity`` averages over (more: the tensor formulation)."""
+        return int(self.lib.mu_snf_affinity_max_k())
+
+    def snf_max_terms(self) -> int:
+        """The most matrices ``snf_diffuse`` adds while it reads (more: pre-summed by the caller)."""
+        return int(self.lib.mu_snf_max_terms())
+
+    @staticmethod
+    def _snf_square(t, name: str):
+        """(n, leading dimension) of an n x n f64 matrix or of the n x n view of a wider buffer."""
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[0] == t.shape[1]):
+            raise TypeError(f"{name}: a square float64 tensor")
+        n = int(t.shape[0])
+        if n > 1 and (t.stride(1) != 1 or t.stride(0) < n):
+            raise ValueError(f"{name}: rows must be contiguous")
+        return n, (int(t.stride(0)) if n > 1 else max(n, 1))
+
+    def snf_affinity(self, D, k: int, sigma: float, eps: float, out=None):
+        """The reference's ``_affinity_matrix(D, k, sigma)`` (include/muon_amd.h); ``out`` may be D itself."""
+        n, ldd = self._snf_square(D, "D")
+        out = self.empty((n, n), torch.float64) if out is None else out
+        n2, ldw = self._snf_square(out, "out")
+        if n2 != n:
+            raise ValueError("out: the shape of D")
+        means = self.empty((max(n, 1),), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_snf_affinity_f64(n, int(k), ldd, _p(D), ldw, _p(out), float(sigma), float(eps), _p(means),
+                                               self._stream()))
+        return out
+
+    def snf_normalize(self, X, out=None):
+        """The reference's ``_normalize(X)``: symmetric bit for bit, diagonal 0.5; ``out`` may be X itself."""
+        n, ldx = self._snf_square(X, "X")
+        out = self.empty((n, n), torch.float64) if out is None else out
+        n2, ldo = self._snf_square(out, "out")
+        if n2 != n:
+            raise ValueError("out: the shape of X")
+        r = self.empty((max(n, 1),), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_snf_normalize_f64(n, ldx, _p(X), ldo, _p(out), _p(r), self._stream()))
+        return out
+
+    def snf_topk(self, W, k: int):
+        """``(idx int32 [n, k], val f64 [n, k])``: the k largest of every row of W with their columns, descending."""
+        n, ldw = self._snf_square(W, "W")
+        idx = self.empty((n, int(k)), torch.int32)
+        val = self.empty((n, int(k)), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_snf_topk_f64(n, int(k), ldw, _p(W), _p(idx), _p(val), self._stream()))
+        return idx, val
+
+    def snf_p_scale(self, indptr, cols, vals):
+        """On the CSR of z: ``rowsum[i]`` = sum of row i in stored order; every entry (i, j) of ``vals`` is divided by
+        ``rowsum[j]`` in place.  Returns ``rowsum``."""
+        if indptr.dtype != torch.int64 or cols.dtype != torch.int32 or vals.dtype != torch.float64:
+            raise TypeError("indptr int64, cols int32, vals float64")
+        assert indptr.is_contiguous() and cols.is_contiguous() and vals.is_contiguous() and cols.numel() == vals.numel()
+        n = int(indptr.numel()) - 1
+        rowsum = self.empty((max(n, 1),), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_snf_p_scale_f64(n, int(vals.numel()), _p(indptr), _p(cols), _p(vals), _p(rowsum),
+                                              self._stream()))
+        return rowsum[:n]
+
+    def snf_diffuse(self, P, terms, out):
+        """``out = (P X)^T``: P = ``(indptr int64, cols int32, vals f64)`` a CSR with n rows, X the mean of ``terms`` (n x n
+        f64 matrices with one leading dimension, added in list order while they are read).  ``out`` is none of them."""
+        indptr, cols, vals = P
+        if indptr.dtype != torch.int64 or cols.dtype != torch.int32 or vals.dtype != torch.float64:
+            raise TypeError("P: indptr int64, cols int32, vals float64")
+        assert indptr.is_contiguous() and cols.is_contiguous() and vals.is_contiguous() and cols.numel() == vals.numel()
+        n, ldy = self._snf_square(out, "out")
+        if int(indptr.numel()) != n + 1:
+            raise ValueError("P: one row per row of out")
+        lds = set()
+        for t in terms:
+            nt, ld = self._snf_square(t, "term")
+            if nt != n:
+                raise ValueError("terms: the shape of out")
+            lds.add(ld)
+        if len(lds) > 1:
+            raise ValueError("terms: one leading dimension")
+        ptrs = (ctypes.c_void_p * max(len(terms), 1))(*[t.data_ptr() for t in terms])
+        with self._dev_ctx():
+            check(self.lib.mu_snf_diffuse_f64(n, len(terms), ptrs, lds.pop() if lds else max(n, 1), _p(indptr), _p(cols),
+                                              _p(vals), ldy, _p(out), self._stream()))
+        return out
 
     # -- muon.atac.tl.rank_peaks_groups (csrc/rank.hip; muon_amd/_atac/rank.py tests for these with hasattr) -----------
     def group_moments_max_groups(self) -> int:

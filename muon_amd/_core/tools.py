@@ -33,6 +33,7 @@ from scipy.sparse import csr_matrix, issparse
 
 from .._containers import MuData, is_anndata, is_mudata
 from .ica import ConvergenceWarning, ica  # noqa: F401  (mu.tl.ica: FastICA of an embedding on the device)
+from .snf import snf  # noqa: F401  (mu.tl.snf: similarity network fusion on the device)
 
 logger = logging.getLogger("muon_amd")
 

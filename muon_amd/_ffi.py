@@ -165,6 +165,14 @@ SIGNATURES = {
     "mu_rank_row_cap": (C.c_int, []),
     "mu_group_moments": (C.c_int, [_i32, _i64, _i64, _i64, _i32] + [_vp] * 8),
     "mu_rank_sums": (C.c_int, [_i32, _i64, _i64, _i64, _i32, _i64] + [_vp] * 8),
+    "mu_snf_max_k": (C.c_int, []),
+    "mu_snf_affinity_max_k": (C.c_int, []),
+    "mu_snf_max_terms": (C.c_int, []),
+    "mu_snf_affinity_f64": (C.c_int, [_i64, _i32, _i64, _vp, _i64, _vp, _dbl, _dbl, _vp, _vp]),
+    "mu_snf_normalize_f64": (C.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "mu_snf_topk_f64": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "mu_snf_p_scale_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mu_snf_diffuse_f64": (C.c_int, [_i64, _i32, C.POINTER(_vp), _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mu_synth_row_nnz": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp]),
     "mu_synth_fill": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp, _vp, _vp]),
 }
