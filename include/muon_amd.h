@@ -796,6 +796,34 @@ int mu_snf_p_scale_f64(int64_t n, int64_t nnz, const int64_t* d_indptr, const in
 int mu_snf_diffuse_f64(int64_t n, int nmat, const void* const* h_X, int64_t ldx, const int64_t* d_indptr,
                        const int32_t* d_cols, const double* d_vals, int64_t ldy, double* d_Y, void* stream);
 
+/* ---- muon.atac.tl.scan_sequences: position weight matrices against every window of every sequence (csrc/motif.hip,
+ * C-ABI v805; the arithmetic is stated in DESIGN.md 9.10) -------------------------------------------------------------
+ * The sequences are one stream d_codes [total] (uint8: 0..3 = A C G T, 4 = invalid) with d_offsets [n_seq + 1] (int64,
+ * offsets[0] = 0, ascending, offsets[n_seq] = total).  The bank is sorted by length and cut into n_mtiles tiles of
+ * mu_motif_group() = 16 motifs: d_bank [n_mtiles][mu_motif_max_len() = 32][4][16] f64 (tile, column, base, motif; zero
+ * past a motif's length), d_tile_len [n_mtiles] the longest motif of a tile, d_mlen / d_thr / d_orig [16 n_mtiles] every
+ * motif's length (a padding slot: 255), threshold (padding: +inf) and index in the caller's order.  Every value of the
+ * bank must be finite.
+ *   mu_motif_room: d_room[p] = number of valid codes from p to the next invalid one or the end of p's sequence, capped
+ *     at mu_motif_max_len().
+ *   mu_motif_count: d_counts [n_mtiles][ceil(total / mu_motif_tile())] = hits of every (motif tile, position tile).  A
+ *     window is a hit iff room >= length and the j-ascending f64 sum of M[code[p + j], j] is >= the threshold.
+ *   mu_motif_write: with d_base = the exclusive scan of d_counts (int64) and n_hits its total, every hit goes to its own
+ *     slot of d_seq / d_motif / d_pos (int32) / d_score (f64): no atomics, two calls agree byte for byte.  Slots are in
+ *     (motif tile, position tile) order; the caller orders the rows. */
+int mu_motif_max_len(void);
+int mu_motif_tile(void);
+int mu_motif_group(void);
+int mu_motif_room(int64_t total, int64_t n_seq, const uint8_t* d_codes, const int64_t* d_offsets, uint8_t* d_room,
+                  void* stream);
+int mu_motif_count(int64_t total, int64_t n_seq, int n_mtiles, const uint8_t* d_codes, const uint8_t* d_room,
+                   const double* d_bank, const int32_t* d_tile_len, const int32_t* d_mlen, const double* d_thr,
+                   int32_t* d_counts, void* stream);
+int mu_motif_write(int64_t total, int64_t n_seq, int n_mtiles, const uint8_t* d_codes, const uint8_t* d_room,
+                   const int64_t* d_offsets, const double* d_bank, const int32_t* d_tile_len, const int32_t* d_mlen,
+                   const double* d_thr, const int32_t* d_orig, const int32_t* d_counts, const int64_t* d_base,
+                   int64_t n_hits, int32_t* d_seq, int32_t* d_motif, int32_t* d_pos, double* d_score, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -17,6 +17,8 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.tl.snf          <->  muon.tl.snf         (similarity network fusion: P S P^T as two sparse-dense passes)
     muon_amd.atac.tl.rank_peaks_groups  <->  muon.atac.tl.rank_peaks_groups  (scanpy's rank_genes_groups on the device
                              copy of the peak matrix, then add_genes_peaks_groups; atac.tl.add_peak_annotation alike)
+    muon_amd.atac.tl.scan_sequences  <->  muon.atac.tl.scan_sequences  (every window of every peak sequence against a
+                             bank of position weight matrices on the f64 matrix cores; atac.tl.get_sequences reads the FASTA)
 
 Everything else of muon (I/O, plotting, clustering, ...) is out of scope; see DESIGN.md.
 """

@@ -14,7 +14,7 @@ Documented differences from the reference / scanpy:
   * ``pts`` counts values that are not zero: an explicitly stored zero is not counted (like ``pp.qc_metrics``).
 
 Out of scope: ``comm`` with more than one rank, ``use_raw=True``, ``method='logreg'``,
-``add_peak_annotation_gene_names`` and the motif tools.
+``add_peak_annotation_gene_names`` (the motif tools are ``motifs.py``).
 """
 from __future__ import annotations
 

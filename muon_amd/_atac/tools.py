@@ -36,6 +36,9 @@ from .fragments import (FragmentTable, count_fragments_features, fragments_from_
                         locate_fragments, nucleosome_signal, tss_enrichment)
 from .rank import (add_genes_peaks_groups, add_peak_annotation, rank_genes_groups,  # noqa: F401
                    rank_peaks_groups)
+from .motifs import (MotifScanner, encode_sequences, get_sequences, parse_motif_ids,  # noqa: F401
+                     parse_motif_matrices, prepare_motif_scanner, scan_sequences, scan_sequences_device,
+                     threshold_from_p)
 
 logger = logging.getLogger("muon_amd")
 

@@ -1770,6 +1770,65 @@ class HipBackend:
                                         _p(values), _p(labels), _p(rs), _p(zr), _p(tie), self._stream()))
         return rs, zr, tie
 
+    # -- muon.atac.tl.scan_sequences (csrc/motif.hip; muon_amd/_atac/motifs.py tests for motif_scan with hasattr) -------
+    def motif_max_len(self) -> int:
+        """The longest motif the kernel takes (longer ones: the tensor formulation)."""
+        return int(self.lib.mu_motif_max_len())
+
+    def motif_tile(self) -> int:
+        """Stream positions a workgroup of the scan takes per step."""
+        return int(self.lib.mu_motif_tile())
+
+    def motif_group(self) -> int:
+        """Motifs per tile of the bank."""
+        return int(self.lib.mu_motif_group())
+
+    def motif_room(self, codes, offsets):
+        """uint8 per stream position: valid codes from there to the next invalid one or the end of its sequence,
+        capped at ``motif_max_len()``."""
+        total, n_seq = int(codes.numel()), int(offsets.numel()) - 1
+        if codes.dtype != torch.uint8 or offsets.dtype != torch.int64 or n_seq < 1:
+            raise TypeError("codes uint8 [total], offsets int64 [n_seq + 1], n_seq >= 1")
+        codes, offsets = codes.contiguous(), offsets.contiguous()
+        room = self.empty((total,), torch.uint8)
+        with self._dev_ctx():
+            check(self.lib.mu_motif_room(total, n_seq, _p(codes), _p(offsets), _p(room), self._stream()))
+        return room
+
+    def motif_scan(self, codes, offsets, bank):
+        """The hits of a packed motif bank (``MotifScanner.bank``: ``n_tiles``, ``bank`` [n_tiles, cap, 4, group] f64,
+        ``tile_len`` [n_tiles], ``mlen`` / ``thr`` / ``orig`` [n_tiles * group]) in the code stream ``codes`` (uint8, 4 =
+        invalid) with ``offsets`` (int64 [n_seq + 1], 0 first, ascending, ``codes.numel()`` last - the caller's
+        promise): ``(sequence int32, motif int32 - the bank's ``orig`` -, position int32, score f64)`` in the kernel's
+        slot order, which is the same on every call.  Count pass, exclusive scan, write pass: no atomics."""
+        total, n_seq = int(codes.numel()), int(offsets.numel()) - 1
+        nt, cap, group = int(bank["n_tiles"]), self.motif_max_len(), self.motif_group()
+        B, tl, ml, th, og = (bank[k].contiguous() for k in ("bank", "tile_len", "mlen", "thr", "orig"))
+        if tuple(B.shape) != (nt, cap, 4, group) or B.dtype != torch.float64:
+            raise TypeError("bank: f64 [n_tiles, motif_max_len(), 4, motif_group()]")
+        for t, dt, n in ((tl, torch.int32, nt), (ml, torch.int32, nt * group), (th, torch.float64, nt * group),
+                         (og, torch.int32, nt * group)):
+            if t.dtype != dt or int(t.numel()) != n:
+                raise TypeError("bank: tile_len int32 [n_tiles]; mlen int32, thr f64, orig int32 [n_tiles * group]")
+        room = self.motif_room(codes, offsets)
+        codes, offsets = codes.contiguous(), offsets.contiguous()
+        n_ptiles = -(-total // self.motif_tile())
+        counts = self.empty((nt * n_ptiles,), torch.int32)
+        with self._dev_ctx():
+            check(self.lib.mu_motif_count(total, n_seq, nt, _p(codes), _p(room), _p(B), _p(tl), _p(ml), _p(th),
+                                          _p(counts), self._stream()))
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        n_hits = int(ends[-1].item()) if ends.numel() else 0
+        base = (ends - counts).contiguous()
+        seq, mot, pos = (self.empty((n_hits,), torch.int32) for _ in range(3))
+        score = self.empty((n_hits,), torch.float64)
+        if n_hits:
+            with self._dev_ctx():
+                check(self.lib.mu_motif_write(total, n_seq, nt, _p(codes), _p(room), _p(offsets), _p(B), _p(tl), _p(ml),
+                                              _p(th), _p(og), _p(counts), _p(base), n_hits, _p(seq), _p(mot), _p(pos),
+                                              _p(score), self._stream()))
+        return seq, mot, pos, score
+
     def mofa_jaakkola(self, zeta, a, b):
         """Bernoulli pseudo-data precision 2 lambda(xi), xi^2 = zeta^2 + a - b, written over ``a``."""
         assert zeta.is_contiguous() and a.is_contiguous() and b.is_contiguous() and a.shape == zeta.shape == b.shape

@@ -165,6 +165,12 @@ SIGNATURES = {
     "mu_rank_row_cap": (C.c_int, []),
     "mu_group_moments": (C.c_int, [_i32, _i64, _i64, _i64, _i32] + [_vp] * 8),
     "mu_rank_sums": (C.c_int, [_i32, _i64, _i64, _i64, _i32, _i64] + [_vp] * 8),
+    "mu_motif_max_len": (C.c_int, []),
+    "mu_motif_tile": (C.c_int, []),
+    "mu_motif_group": (C.c_int, []),
+    "mu_motif_room": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
+    "mu_motif_count": (C.c_int, [_i64, _i64, _i32] + [_vp] * 8),
+    "mu_motif_write": (C.c_int, [_i64, _i64, _i32] + [_vp] * 10 + [_i64] + [_vp] * 5),
     "mu_snf_max_k": (C.c_int, []),
     "mu_snf_affinity_max_k": (C.c_int, []),
     "mu_snf_max_terms": (C.c_int, []),
