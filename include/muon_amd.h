@@ -824,6 +824,32 @@ int mu_motif_write(int64_t total, int64_t n_seq, int n_mtiles, const uint8_t* d_
                    const double* d_thr, const int32_t* d_orig, const int32_t* d_counts, const int64_t* d_base,
                    int64_t n_hits, int32_t* d_seq, int32_t* d_motif, int32_t* d_pos, double* d_score, void* stream);
 
+/* ---- muon.tl.leiden / muon.tl.louvain: multiplex clustering (/root/reference/muon/_core/tools.py:928-1206; csrc/cluster.hip,
+ * C-ABI v806; the optimiser is stated in muon_amd/_core/cluster.py and DESIGN.md 9.11) -----------------------------------
+ * All arithmetic f64, labels int32, offsets int64.  No atomics: two calls agree bit for bit.  Arguments are checked
+ * before any HIP call.
+ *   mu_cluster_move_f64: one sub-round.  S without its diagonal is the CSR (d_indptr [nv + 1], d_cols, d_vals [nnz]);
+ *     d_labels [nv] the snapshot, d_size [nv] the members per community id, d_P / d_K [nv][2 n_layers] the strengths
+ *     (kout^1, kin^1, ...) of the vertices / their totals per community id, h_coef (HOST) the n_layers coefficients.
+ *     For each of the nverts vertices v of d_verts: the candidates are labels[v] = a and the labels of v's neighbours
+ *     (with d_bound, nullable: of the neighbours u with bound[u] == bound[v]); score(C) = w(v, C) - sum_l coef_l
+ *     (kout_v Kin_C + kin_v Kout_C), P[v] taken out of K[a]; when size[a] == 1 a candidate C != a with size[C] == 1
+ *     and C > a is none; the best is the largest score, ties to the smallest id; d_prop[v] = the best if it is not a and
+ *     scores above a strictly, else a; d_score[v] = the score of d_prop[v].  only_single: a vertex with size[a] != 1
+ *     gets d_prop[v] = a, d_score[v] = 0.  A vertex with more than mu_cluster_max_table() = 512 candidates stores 1 to
+ *     *d_overflow (never 0: the caller clears it), d_prop[v] = a, d_score[v] = 0.  Entries of vertices not in d_verts are
+ *     not written.  1 <= n_layers <= mu_cluster_max_layers() = 4.
+ *   mu_cluster_segsum_f64: d_out[s][:] = sum of the rows d_ptr[s] .. d_ptr[s + 1] of d_vals [n][w]; lane j of a wave
+ *     adds rows j, j + 64, ... in order, then the xor butterfly. */
+int mu_cluster_max_table(void);
+int mu_cluster_max_layers(void);
+int mu_cluster_move_f64(int64_t nverts, const int32_t* d_verts, int64_t nv, int64_t nnz, const int64_t* d_indptr,
+                        const int32_t* d_cols, const double* d_vals, const int32_t* d_labels, const int32_t* d_bound,
+                        const int32_t* d_size, int n_layers, const double* d_P, const double* d_K, const double* h_coef,
+                        int only_single, int32_t* d_prop, double* d_score, int32_t* d_overflow, void* stream);
+int mu_cluster_segsum_f64(int64_t n, int64_t nseg, int w, const double* d_vals, const int64_t* d_ptr, double* d_out,
+                          void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -20,7 +20,10 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.atac.tl.scan_sequences  <->  muon.atac.tl.scan_sequences  (every window of every peak sequence against a
                              bank of position weight matrices on the f64 matrix cores; atac.tl.get_sequences reads the FASTA)
 
-Everything else of muon (I/O, plotting, clustering, ...) is out of scope; see DESIGN.md.
+    muon_amd.tl.leiden / muon_amd.tl.louvain  <->  muon.tl.leiden / muon.tl.louvain  (multiplex clustering over the
+                             modalities' graphs: a wave per vertex groups its neighbours' communities in an LDS table)
+
+Everything else of muon (I/O, plotting, UMAP, ...) is out of scope; see DESIGN.md.
 """
 from ._containers import AnnData, MuData  # duck-typed stand-ins when anndata/mudata are absent
 from . import atac  # noqa: F401

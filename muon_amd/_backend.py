@@ -1770,6 +1770,64 @@ class HipBackend:
                                         _p(values), _p(labels), _p(rs), _p(zr), _p(tie), self._stream()))
         return rs, zr, tie
 
+    # -- muon.tl.leiden / muon.tl.louvain (csrc/cluster.hip; muon_amd/_core/cluster.py tests for these with hasattr) -----
+    def cluster_max_table(self) -> int:
+        """Entries of a wave's community table in ``cluster_move``: the own community and the distinct neighbouring ones
+        (a vertex with more makes the kernel report, and its level runs the tensor formulation)."""
+        return int(self.lib.mu_cluster_max_table())
+
+    def cluster_max_layers(self) -> int:
+        """The most layers ``cluster_move`` scores (more: the tensor formulation)."""
+        return int(self.lib.mu_cluster_max_layers())
+
+    def cluster_move(self, verts, indptr, cols, vals, labels, bound, size, P, K, coef, only_single: bool, prop, score,
+                     overflow):
+        """One sub-round of the local moving (include/muon_amd.h): for every vertex of ``verts`` (int32) the proposal goes
+        to ``prop[v]`` and the score of the community it names to ``score[v]``; ``overflow[0]`` becomes 1 where a vertex
+        met more distinct communities than ``cluster_max_table()``.  ``bound`` may be None."""
+        nv = int(labels.numel())
+        L = len(coef)
+        i32 = [("verts", verts), ("cols", cols), ("labels", labels), ("size", size), ("prop", prop), ("overflow", overflow)]
+        if bound is not None:
+            i32.append(("bound", bound))
+        for name, t in i32:
+            if t.dtype != torch.int32 or not t.is_contiguous():
+                raise TypeError(f"{name}: a contiguous int32 tensor")
+        for name, t in (("vals", vals), ("P", P), ("K", K), ("score", score)):
+            if t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError(f"{name}: a contiguous float64 tensor")
+        if indptr.dtype != torch.int64 or not indptr.is_contiguous() or int(indptr.numel()) != nv + 1:
+            raise TypeError("indptr: a contiguous int64 tensor of nv + 1 offsets")
+        if cols.numel() != vals.numel():
+            raise ValueError("cols and vals: one entry each per edge")
+        if tuple(P.shape) != (nv, 2 * L) or tuple(K.shape) != (nv, 2 * L):
+            raise ValueError("P and K: [nv, 2 L]")
+        if any(int(t.numel()) != nv for t in (size, prop, score)) or (bound is not None and int(bound.numel()) != nv):
+            raise ValueError("size, prop, score and bound: one entry per vertex")
+        if int(overflow.numel()) < 1:
+            raise ValueError("overflow: at least one entry")
+        h_coef = (ctypes.c_double * max(L, 1))(*[float(c) for c in coef])
+        with self._dev_ctx():
+            check(self.lib.mu_cluster_move_f64(int(verts.numel()), _p(verts), nv, int(vals.numel()), _p(indptr), _p(cols),
+                                               _p(vals), _p(labels), _p(bound), _p(size), L, _p(P), _p(K), h_coef,
+                                               1 if only_single else 0, _p(prop), _p(score), _p(overflow), self._stream()))
+        return prop, score
+
+    def cluster_segsum(self, vals, ptr):
+        """``out[s] = sum(vals[ptr[s]:ptr[s + 1]])`` for f64 rows [n, w] and int64 offsets [nseg + 1], in a fixed order."""
+        if vals.dtype != torch.float64 or vals.dim() != 2 or not vals.is_contiguous():
+            raise TypeError("vals: a contiguous float64 [n, w] tensor")
+        if ptr.dtype != torch.int64 or ptr.dim() != 1 or not ptr.is_contiguous() or int(ptr.numel()) < 1:
+            raise TypeError("ptr: a contiguous int64 tensor of nseg + 1 offsets")
+        n, w = int(vals.shape[0]), int(vals.shape[1])
+        nseg = int(ptr.numel()) - 1
+        out = self.empty((nseg, w), torch.float64)
+        if w == 0:
+            return out
+        with self._dev_ctx():
+            check(self.lib.mu_cluster_segsum_f64(n, nseg, w, _p(vals), _p(ptr), _p(out), self._stream()))
+        return out
+
     # -- muon.atac.tl.scan_sequences (csrc/motif.hip; muon_amd/_atac/motifs.py tests for motif_scan with hasattr) -------
     def motif_max_len(self) -> int:
         """The longest motif the kernel takes (longer ones: the tensor formulation)."""

@@ -165,6 +165,11 @@ SIGNATURES = {
     "mu_rank_row_cap": (C.c_int, []),
     "mu_group_moments": (C.c_int, [_i32, _i64, _i64, _i64, _i32] + [_vp] * 8),
     "mu_rank_sums": (C.c_int, [_i32, _i64, _i64, _i64, _i32, _i64] + [_vp] * 8),
+    "mu_cluster_max_table": (C.c_int, []),
+    "mu_cluster_max_layers": (C.c_int, []),
+    "mu_cluster_move_f64": (C.c_int, [_i64, _vp, _i64, _i64] + [_vp] * 6 + [_i32, _vp, _vp, C.POINTER(_dbl), _i32, _vp, _vp,
+                                      _vp, _vp]),
+    "mu_cluster_segsum_f64": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mu_motif_max_len": (C.c_int, []),
     "mu_motif_tile": (C.c_int, []),
     "mu_motif_group": (C.c_int, []),
