@@ -25,6 +25,7 @@ import pandas as pd
 import torch
 
 from .._containers import AnnData, is_anndata, is_mudata
+from .._operators import has
 
 _NO_FRAGMENTS = "There is no fragments file located yet. Run muon.atac.tl.locate_fragments first."
 _I32_MAX = 2 ** 31 - 1
@@ -249,14 +250,14 @@ def length_classes_tensor(table, cell_of, n_obs, n_take, free_bound, mono_bound)
 
 def window_ranges(table, wchrom, wlo, whi):
     be = table.backend
-    if hasattr(be, "frag_ranges"):
+    if has(be, "frag_ranges"):
         return be.frag_ranges(table.start, table.chrom_ptr_device, wchrom, wlo, whi, table.max_len)
     return ranges_tensor(table, wchrom, wlo, whi)
 
 
 def overlap_triplets(table, cell_of, n_obs, wlo, whi, rng_lo, rng_len, n_features, use_score=True):
     be = table.backend
-    if hasattr(be, "frag_overlap"):
+    if has(be, "frag_overlap"):
         return be.frag_overlap(table.start, table.end, table.barcode, table.score if use_score else None, cell_of,
                                n_obs, wlo, whi, rng_lo, rng_len, n_features)
     return overlap_tensor(table, cell_of, wlo, whi, rng_lo, rng_len, n_features, use_score)
@@ -264,7 +265,7 @@ def overlap_triplets(table, cell_of, n_obs, wlo, whi, rng_lo, rng_len, n_feature
 
 def pileup_diff(table, cell_of, n_obs, wlo, whi, rng_lo, rng_len, width):
     be = table.backend
-    if hasattr(be, "frag_pileup"):
+    if has(be, "frag_pileup"):
         return be.frag_pileup(table.start, table.end, table.barcode, table.score, cell_of, n_obs, wlo, whi, rng_lo,
                               rng_len, width)
     return pileup_tensor(table, cell_of, n_obs, wlo, whi, rng_lo, rng_len, width)
@@ -272,14 +273,14 @@ def pileup_diff(table, cell_of, n_obs, wlo, whi, rng_lo, rng_len, width):
 
 def pileup_scan(table, diff, flank_size, center_dist):
     be = table.backend
-    if hasattr(be, "frag_pileup_scan"):
+    if has(be, "frag_pileup_scan"):
         return be.frag_pileup_scan(diff, flank_size, center_dist)
     return scan_tensor(diff, flank_size, center_dist)
 
 
 def length_classes(table, cell_of, n_obs, n_take, free_bound, mono_bound):
     be = table.backend
-    if hasattr(be, "frag_length_classes"):
+    if has(be, "frag_length_classes"):
         return be.frag_length_classes(table.start, table.end, table.barcode, cell_of, n_obs, n_take, free_bound,
                                       mono_bound)
     return length_classes_tensor(table, cell_of, n_obs, n_take, free_bound, mono_bound)
@@ -380,7 +381,7 @@ def count_fragments_features(data, features: Optional[pd.DataFrame] = None, stra
     keys, vals = overlap_triplets(table, cell_of, n, wlo, whi, rng_lo, rng_len, n_features, use_score=bool(count_reads))
     X = device_csr_from_keys(keys, vals.long(), (n, n_features))  # (duplicates summed as integers)
     X.values = X.values.to(getattr(torch, np.dtype(values_dtype).name))
-    if hasattr(be, "with_slab_ptr"):
+    if has(be, "with_slab_ptr"):
         X = be.with_slab_ptr(X)
     host = csr_matrix((be.to_host(X.values), be.to_host(X.indices), be.to_host(X.indptr)), shape=X.shape)
     host.has_sorted_indices = True

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from .._containers import is_anndata, is_mudata
+from .._operators import has
 
 COLUMNS = ["sequence", "motif_id", "position", "score"]
 TENSOR_CHUNK = 1 << 22  # stream positions the tensor formulation scores at a time
@@ -194,7 +195,7 @@ class MotifScanner:
         if self.thresholds.size != self.n_motifs:
             raise ValueError("one threshold per matrix")
         self.max_hits = max_hits  # kept for the signature; limits nothing
-        has_kernel = hasattr(backend, "motif_scan")
+        has_kernel = has(backend, "motif_scan")
         if use_kernel is None:
             use_kernel = has_kernel
         elif use_kernel and not has_kernel:

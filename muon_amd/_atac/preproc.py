@@ -16,6 +16,7 @@ from scipy.sparse import csr_matrix, issparse
 from .._comm import default_comm
 from .._containers import is_anndata, is_mudata, view_to_actual
 from .._ffi import TFIDF_LOG_IDF, TFIDF_LOG_TF, TFIDF_LOG_TFIDF
+from .._operators import has
 
 DEVICE_ATTR = "_muon_amd_device"
 
@@ -346,7 +347,7 @@ def canonical_csr_deferred(counts):
 def upload_canonical(backend, counts, values_dtype=None):
     """Host matrix -> (host canonical CSR, DeviceCSR with its slab pointers)."""
     host, checked = canonical_csr_deferred(counts)
-    if not checked and hasattr(backend, "with_slab_ptr"):
+    if not checked and has(backend, "with_slab_ptr"):
         from .._core.io import canonicalize
 
         X = backend.upload_csr(host.indptr, host.indices, host.data, host.shape, values_dtype=values_dtype,
@@ -392,7 +393,7 @@ def tfidf_device(backend, X, n_obs, flags: int, scale: float, comm=None, out=Non
     comm = default_comm(comm)
     # HipBackend's sweeps hand the slab pointers they search from the sum pass to the scale pass and on to the result
     # (`keep_work`, `work`); other operator sets (CPU tests) have the plain forms only
-    hands_on = hasattr(backend, "slab_ptr_from_work")
+    hands_on = has(backend, "slab_ptr_from_work")
     work = None
     with phase("tfidf/sums"):
         if hands_on:
@@ -406,9 +407,8 @@ def tfidf_device(backend, X, n_obs, flags: int, scale: float, comm=None, out=Non
     # transposes from the stream.  Operator sets without the kernel (CPU tests) simply do not offer it.
     emit = sp = None
     kw = {} if work is None else {"work": work}
-    can = getattr(backend, "can_emit_stream", None)
     with phase("tfidf/scale"):
-        if emit_stream and can is not None and can(X):
+        if emit_stream and has(backend, "can_emit_stream") and backend.can_emit_stream(X):
             emit = kw["emit"] = backend.stream_layout(X)
         vals, zero_count = backend.tfidf_scale(X, rowsum, idf, scale, flags, out=out, **kw)
         if work is not None:
@@ -533,7 +533,7 @@ def tfidf(
         n_r, n_c = counts.shape
         Xc = backend.upload_csr(counts.indptr, counts.indices, counts.data, (n_c, n_r))
         # f32: the tile-staged transposition of csrc/tpack4.hip (3x the rate of the general kernel)
-        fast = counts.dtype == np.float32 and hasattr(backend, "transpose_csr") and counts.nnz > 0
+        fast = counts.dtype == np.float32 and has(backend, "transpose_csr") and counts.nnz > 0
         X = backend.transpose_csr(Xc) if fast else backend.transpose(Xc)
         host = None
     else:

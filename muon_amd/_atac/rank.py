@@ -26,6 +26,7 @@ import torch
 from scipy.sparse import issparse
 
 from .._containers import is_anndata, is_mudata
+from .._operators import OperatorSet, has
 
 METHODS = ("t-test", "t-test_overestim_var", "wilcoxon", "logreg")
 SORT_BUDGET_BYTES = 1 << 30  # device memory the per-row sort of X^T may hold at a time
@@ -98,13 +99,13 @@ def _rank_sums_tensor(Xs, labels, n_buckets):
 
 
 def moments_device(backend, Xt, labels, n_buckets):
-    if hasattr(backend, "group_moments") and n_buckets <= backend.group_moments_max_groups():
+    if has(backend, "group_moments") and n_buckets <= backend.group_moments_max_groups():
         return backend.group_moments(Xt, labels, n_buckets)
     return _moments_tensor(Xt, labels, n_buckets)
 
 
 def rank_sums_device(backend, Xs, labels, n_buckets):
-    if hasattr(backend, "rank_sums") and n_buckets <= backend.group_moments_max_groups():
+    if has(backend, "rank_sums") and n_buckets <= backend.group_moments_max_groups():
         return backend.rank_sums(Xs, labels, n_buckets)
     return _rank_sums_tensor(Xs, labels, n_buckets)
 
@@ -149,7 +150,7 @@ def _dense_transposed(backend, arr):
     return DeviceCSR(indptr, cells, t[nz].contiguous(), (int(t.shape[0]), int(t.shape[1])))
 
 
-class _NoKernels:
+class _NoKernels(OperatorSet):
     """An operator set seen through its tensor operations alone (a dense matrix takes the tensor path)."""
 
     def __init__(self, backend):
@@ -171,7 +172,7 @@ def _transposed(adata, layer, backend):
         host, X = upload_canonical(backend, counts)
         if host is counts:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
             attach_device(counts, X, backend)
-    if X.values.dtype == torch.float32 and hasattr(backend, "transpose_csr"):
+    if X.values.dtype == torch.float32 and has(backend, "transpose_csr"):
         return backend.transpose_csr(X), backend
     return backend.transpose(X), backend
 

@@ -30,6 +30,7 @@ import scipy.linalg
 
 from .._comm import default_comm
 from .._containers import is_anndata, is_mudata
+from .._operators import has
 from .._trace import phase
 from .preproc import canonical_csr, resident, upload_canonical  # noqa: F401
 from .fragments import (FragmentTable, count_fragments_features, fragments_from_arrays,  # noqa: F401
@@ -447,7 +448,7 @@ def _warm_start(backend, comm, Xcsr, Xt, B, w, seed, start, adaptive, n_obs, nnz
     # (what follows holds collectives, so entering it must be ONE decision of all ranks.  `pack` is per rank -
     #  a rank whose shard has no rows has no row stream - and such a rank still takes part: with an empty slice it
     #  contributes zeros to the sums.  `warm_spec`, `start`, `n_iter` are the same on every rank by construction.)
-    can_slice = bool(pack and hasattr(Xcsr, "indptr") and hasattr(backend, "stream_both"))
+    can_slice = bool(pack and hasattr(Xcsr, "indptr") and has(backend, "stream_both"))
     n_local = Xcsr.shape[0]
     frac, qsteps = (int(v) for v in (warm_spec.split(":") + ["2"])[:2])
     # this rank's slice: 1 / frac of its cells; the slices of ALL ranks together at least 16 384 cells (an experiment
@@ -462,7 +463,7 @@ def _warm_start(backend, comm, Xcsr, Xt, B, w, seed, start, adaptive, n_obs, nnz
     # transposition of the slice, no sorted layout, no device -> host read after the first call (the plan is cached
     # with the index arrays).  At a 125 000-cell shard the slice's operands and four products took 8.3 ms of r05's 50.
     wplan = None
-    if n_s > 0 and getattr(Xt, "t4", None) is not None and hasattr(backend, "slice_plan") \
+    if n_s > 0 and getattr(Xt, "t4", None) is not None and has(backend, "slice_plan") \
             and os.environ.get("MUON_AMD_LSI_WARM_SLICE", "ranges") == "ranges":
         wplan = backend.slice_plan(Xcsr, n_s)
         if wplan is not None:
@@ -821,7 +822,7 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
     # both operands of the iteration are read from their row streams; X^T's is built
     # straight from the CSR of X, no CSR of X^T in between.  (`pack=False`: plain CSR kernels.)
     if pack is None:
-        pack = Xt is None and hasattr(backend, "can_stream") and backend.can_stream(X, B)
+        pack = Xt is None and has(backend, "can_stream") and backend.can_stream(X, B)
 
     # Algorithm (ours; the reference's is ARPACK, tools.py:53).  Blocks Q_0 .. Q_j (d x B, replicated)
     # are an orthonormal basis K_j of the block Krylov space of A = X^T X started at a random block:
@@ -857,7 +858,7 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
         # of independent directions (it can on matrices with a few thousand rows or columns: the host
         # path detects that and truncates)
         if device_qr is None:
-            device_qr = hasattr(backend, "chol_rinv") and min(n_obs, d) >= 8192
+            device_qr = has(backend, "chol_rinv") and min(n_obs, d) >= 8192
         qr_flag = backend.zeros((1,), torch.int32) if device_qr else None
     with phase("lsi/warm_start"):
         Q0, warm_used, t4_err = _warm_start(backend, comm, Xcsr, Xt, B, w, seed, start, n_iter is None, n_obs, nnz_rank,

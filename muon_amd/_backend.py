@@ -5,7 +5,8 @@
 only containers whose ``data_ptr()`` is handed to the kernels.  There is no CPU
 implementation in this package - constructing ``HipBackend`` without a GPU raises.
 (The multi-process *host logic* is exercised on CPU by tests that inject their own
-operator set; see tests/cpu_backend.py.)
+operator set; see tests/cpu_backend.py.)  Which operators there are, and which of them a set may leave out, is
+declared once in ``_operators.OperatorSet``.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 
 from . import _ffi
 from ._ffi import F32, F64, check
+from ._operators import OperatorSet
 
 
 @dataclass(slots=True)
@@ -263,7 +265,7 @@ def ell16_layout(X: DeviceCSR, waves: int = 15, slab_cols: int = 1024, slab_ptr_
     return DeviceEll(hdr, wave_base, ent, perm, (n, d), X.nnz, total * 64, int(waves), int(slab_cols))
 
 
-class HipBackend:
+class HipBackend(OperatorSet):
     name = "hip"
 
     def __init__(self, device: Optional[int] = None):
@@ -1544,7 +1546,7 @@ class HipBackend:
                                                _p(X.indices), _p(X.values), _p(out), self._stream()))
         return out
 
-    # -- muon.prot.pp.dsb (csrc/prot.hip; muon_amd/_prot/preproc.py tests for these with hasattr) ---------------------
+    # -- muon.prot.pp.dsb (csrc/prot.hip) ----------------------------------------------------------------------------
     def prot_max_proteins(self) -> int:
         """The widest protein panel the two kernels below take (wider panels: the tensor formulation)."""
         return int(self.lib.mu_prot_max_proteins())
@@ -1595,7 +1597,7 @@ class HipBackend:
                                                self._stream()))
         return scaled, bg, bic, niter
 
-    # -- muon.tl.ica (csrc/ica.hip; muon_amd/_core/ica.py tests for these with hasattr) --------------------------------
+    # -- muon.tl.ica (csrc/ica.hip) ----------------------------------------------------------------------------------
     _ICA_FUN = {"logcosh": 0, "exp": 1, "cube": 2}
 
     def ica_max_components(self) -> int:
@@ -1622,7 +1624,7 @@ class HipBackend:
                                             _p(work), wb, int(max_blocks), self._stream()))
         return A, gp
 
-    # -- muon.tl.snf (csrc/snf.hip; muon_amd/_core/snf.py tests for these with hasattr) --------------------------------
+    # -- muon.tl.snf (csrc/snf.hip) ----------------------------------------------------------------------------------
     def free_memory(self) -> int:
         """Bytes the device can still hand out: what the driver reports free plus what torch's allocator holds unused."""
         with self._dev_ctx():
@@ -1723,7 +1725,7 @@ class HipBackend:
                                               _p(vals), ldy, _p(out), self._stream()))
         return out
 
-    # -- muon.atac.tl.rank_peaks_groups (csrc/rank.hip; muon_amd/_atac/rank.py tests for these with hasattr) -----------
+    # -- muon.atac.tl.rank_peaks_groups (csrc/rank.hip) --------------------------------------------------------------
     def group_moments_max_groups(self) -> int:
         """The most buckets the two kernels take (more: the tensor formulation)."""
         return int(self.lib.mu_group_moments_max_groups())
@@ -1770,7 +1772,7 @@ class HipBackend:
                                         _p(values), _p(labels), _p(rs), _p(zr), _p(tie), self._stream()))
         return rs, zr, tie
 
-    # -- muon.tl.leiden / muon.tl.louvain (csrc/cluster.hip; muon_amd/_core/cluster.py tests for these with hasattr) -----
+    # -- muon.tl.leiden / muon.tl.louvain (csrc/cluster.hip) ---------------------------------------------------------
     def cluster_max_table(self) -> int:
         """Entries of a wave's community table in ``cluster_move``: the own community and the distinct neighbouring ones
         (a vertex with more makes the kernel report, and its level runs the tensor formulation)."""
@@ -1828,7 +1830,7 @@ class HipBackend:
             check(self.lib.mu_cluster_segsum_f64(n, nseg, w, _p(vals), _p(ptr), _p(out), self._stream()))
         return out
 
-    # -- muon.atac.tl.scan_sequences (csrc/motif.hip; muon_amd/_atac/motifs.py tests for motif_scan with hasattr) -------
+    # -- muon.atac.tl.scan_sequences (csrc/motif.hip) ----------------------------------------------------------------
     def motif_max_len(self) -> int:
         """The longest motif the kernel takes (longer ones: the tensor formulation)."""
         return int(self.lib.mu_motif_max_len())

@@ -72,6 +72,7 @@ import torch
 from scipy.sparse import csr_matrix
 
 from .._containers import is_anndata, is_mudata
+from .._operators import has
 
 _KERNEL_METHODS = ("cluster_move", "cluster_segsum", "cluster_max_table", "cluster_max_layers")
 MAX_SWEEPS = 50
@@ -99,7 +100,7 @@ def _ptr_of_counts(counts: torch.Tensor) -> torch.Tensor:
 
 def _segsum(be, vals: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     """``out[s] = sum(vals[ptr[s]:ptr[s + 1]])`` for f64 rows [n, w], in a fixed order."""
-    if hasattr(be, "cluster_segsum"):
+    if has(be, "cluster_segsum"):
         return be.cluster_segsum(vals.contiguous(), ptr)
     if vals.device.type != "cpu":  # (a device's index_add_ adds with atomics: no fixed order, no bit-equal repeats)
         raise RuntimeError("muon_amd.tl.leiden / louvain: a device backend must provide cluster_segsum")
@@ -334,7 +335,7 @@ def optimise(be, g0: _Graph, algorithm: str, rng, n_iterations: int = 1, diagnos
     """Membership [nv] (host int64, communities numbered by decreasing size), Q(final) and Q(singletons)."""
     nv0 = g0.nv
     dev = g0.P.device
-    can_kernel = all(hasattr(be, name) for name in _KERNEL_METHODS) and 1 <= g0.L <= be.cluster_max_layers()
+    can_kernel = has(be, *_KERNEL_METHODS) and 1 <= g0.L <= be.cluster_max_layers()
     levels = []
     member = torch.arange(nv0, dtype=torch.int32, device=dev)
     for _ in range(n_iterations):

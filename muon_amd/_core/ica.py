@@ -37,6 +37,8 @@ import numpy as np
 import torch
 from scipy import linalg
 
+from .._operators import has
+
 _FUNS = ("logcosh", "exp", "cube")
 
 
@@ -226,7 +228,7 @@ def _fastica_arrays(X, n_components=None, *, random_state=None, algorithm="paral
 
     lims = []
     if algorithm == "parallel":
-        kernel = (not force_tensor and hasattr(be, "ica_sweep") and hasattr(be, "ica_max_components")
+        kernel = (not force_tensor and has(be, "ica_sweep", "ica_max_components")
                   and k <= be.ica_max_components())
         W = _sym_decorrelation(w_init)
         p_ = float(n)

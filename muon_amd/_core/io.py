@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .._comm import default_comm
+from .._operators import has
 
 
 def shard_rows(n_rows: int, comm=None) -> Tuple[int, int]:
@@ -62,12 +63,9 @@ def device_csr_from_10x(matrix: Mapping, comm=None, backend=None, atac_only: boo
     ip = np.asarray(indptr[r0:r1 + 1]).astype(np.int64)
     p0, p1 = int(ip[0]), int(ip[-1])
     # only this rank's stored entries cross PCIe; index / value conversion happens on the way
-    try:
-        X = backend.upload_csr(ip - p0, matrix["indices"][p0:p1], matrix["data"][p0:p1], (r1 - r0, n_feat),
-                               values_dtype=values_dtype, slab_ptr=False)  # (made below, for the arrays that stay)
-    except TypeError:  # operator sets without the option (CPU tests)
-        X = backend.upload_csr(ip - p0, matrix["indices"][p0:p1], matrix["data"][p0:p1], (r1 - r0, n_feat),
-                               values_dtype=values_dtype)
+    kw = {"slab_ptr": False} if has(backend, "with_slab_ptr") else {}  # (made below, for the arrays that stay)
+    X = backend.upload_csr(ip - p0, matrix["indices"][p0:p1], matrix["data"][p0:p1], (r1 - r0, n_feat),
+                           values_dtype=values_dtype, **kw)
     keep = None
     if atac_only:
         ft = feature_types
@@ -82,7 +80,7 @@ def device_csr_from_10x(matrix: Mapping, comm=None, backend=None, atac_only: boo
                 keep = np.nonzero(mask)[0]
                 X = select_columns(backend, X, mask)
     X = canonicalize(backend, X)
-    if hasattr(backend, "with_slab_ptr"):
+    if has(backend, "with_slab_ptr"):
         # ingest is where the slab pointers of the final index arrays are searched, once (tfidf and lsi read them)
         X = backend.with_slab_ptr(X)
     return X, keep, (r0, r1)
@@ -201,8 +199,9 @@ def device_csr_from_csc(indptr, indices, data, shape, backend=None, values_dtype
         backend = get_backend()
     n, d = int(shape[0]), int(shape[1])
     Xt = backend.upload_csr(indptr, indices, data, (d, n), values_dtype=values_dtype)  # CSR of X^T
-    tr = getattr(backend, "transpose_csr", None) if Xt.values.dtype == torch.float32 else None
-    return (tr or backend.transpose)(Xt)
+    if Xt.values.dtype == torch.float32 and has(backend, "transpose_csr"):
+        return backend.transpose_csr(Xt)
+    return backend.transpose(Xt)
 
 
 def read_10x_arrays(matrix: Mapping, atac_only: bool = True, feature_types=None, barcodes=None,

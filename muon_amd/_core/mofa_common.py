@@ -29,9 +29,6 @@ LN_THETA0 = float(torch.digamma(torch.tensor(1.0, dtype=torch.float64)) - torch.
 def _can_ell16(be, X, wide: bool) -> bool:
     """The sliced-ELL kernels address both dense operands with 32-bit byte offsets (64-byte rows of an f32 block, 128-byte
     rows of an f64 one): X and X^T must both stay under 4 GiB of dense rows, else the row-stream path is taken."""
-    fn = getattr(be, "can_ell16", None)
-    if fn is not None:
-        return bool(fn(X, wide))
     row = 128 if wide else 64
     return max(X.shape) * row < (1 << 32)
 
@@ -73,7 +70,7 @@ class MofaDriver:
         """``groups``: int [N], this rank's samples.  ``graph``: the engine's switch for capturing an iteration."""
         self.be = backend
         self.comm = default_comm(comm)
-        self._hip = getattr(backend, "name", "") == "hip"
+        self._hip = backend.name == "hip"
         self.K = int(n_factors)
         self.M = int(n_views)
         groups = np.asarray(groups, dtype=np.int64)

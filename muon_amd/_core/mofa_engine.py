@@ -38,6 +38,7 @@ import numpy as np
 import torch
 from scipy.sparse import issparse
 
+from .._operators import has
 from .mofa_common import A0, B0, TH_A0, TH_B0, TOL, MofaDriver, _can_ell16  # noqa: F401  (the constants: importable from here)
 
 
@@ -107,9 +108,9 @@ class MofaEngine(MofaDriver):
         self._t_last = time.perf_counter()
         if not (1 <= int(n_factors) <= 32):
             raise NotImplementedError("1 <= n_factors <= 32")
-        for op in REQUIRED_OPS:
-            if not hasattr(backend, op):
-                raise NotImplementedError(f"MofaEngine needs the operator `{op}`, which {type(backend).__name__} lacks")
+        if not has(backend, *REQUIRED_OPS):
+            op = next(op for op in REQUIRED_OPS if not has(backend, op))
+            raise NotImplementedError(f"MofaEngine needs the operator `{op}`, which {type(backend).__name__} lacks")
         self.opts = dict(ard_weights=ard_weights, ard_factors=ard_factors,
                          spikeslab_weights=spikeslab_weights)
         # (one iteration is ~150 short launches: the single-process one is replayed as a HIP graph)
@@ -167,7 +168,7 @@ class MofaEngine(MofaDriver):
         view / group scaling (the scaled values are not exact in f32 either)."""
         be = self.be
         return (self.T == torch.float64 and not scale_views and not scale_groups and self.K <= 16
-                and getattr(be, "skinny_mixed", False) and hasattr(be, "skinny_nn")
+                and be.skinny_mixed and has(be, "skinny_nn")
                 and os.environ.get("MUON_AMD_MOFA_F32_STORAGE", "1") != "0")
 
     def _prepare_view(self, v, center_groups, scale_views, scale_groups):
@@ -184,7 +185,7 @@ class MofaEngine(MofaDriver):
             pres = np.ones(N, dtype=bool)
             if isinstance(v, DeviceCSR):
                 V.kind = "sparse"
-                if v.nnz >= 2 and hasattr(be, "lib"):
+                if v.nnz >= 2 and be.name == "hip":
                     # the operand layouts below rank an entry inside its (row, slab) by position: rows must be sorted
                     # by column (a caller's device-resident CSR is not canonicalised anywhere else - ADVICE r04)
                     from .io import canonicalize
@@ -236,7 +237,7 @@ class MofaEngine(MofaDriver):
         s1 = torch.zeros((G, D), dtype=T, device=V.pres.device)
         s2 = torch.zeros((G, D), dtype=T, device=V.pres.device)
         for g, (a, b) in enumerate(self.gslice):
-            if V.kind == "dense" and hasattr(be, "col_moments") and V.Y.is_contiguous():
+            if V.kind == "dense" and has(be, "col_moments") and V.Y.is_contiguous():
                 # one pass, f64 sums (csrc/mofa_stats.hip) - also over the f32-stored block of an f64 fit
                 if b > a:
                     m1, m2 = be.col_moments(V.Y, a, b)
@@ -249,7 +250,7 @@ class MofaEngine(MofaDriver):
             elif V.kind == "dense":
                 s1[g] = V.Y[a:b].sum(dim=0)
                 s2[g] = (V.Y[a:b] ** 2).sum(dim=0)
-            elif hasattr(be, "lib") and hasattr(be, "row_col_sums"):
+            elif be.name == "hip":
                 # the per-feature moments of a group's rows are column sums of the values and of their squares: the
                 # TF-IDF sum sweep (f64 sums in LDS bins) instead of two index_add_ over every entry (r04: 2 x 12.8 ms)
                 from .._backend import DeviceCSR
@@ -323,28 +324,28 @@ class MofaEngine(MofaDriver):
             for g, (a, b) in enumerate(self.gslice):
                 if b > a:
                     torch.addcmul(src[a:b], V.pres[a:b, None], mu[g][None, :], value=-1.0, out=V.Y[a:b])
-        elif (self.T == torch.float32 and hasattr(be, "ell16") and _pad_block(self.G * self.K) == 16
+        elif (self.T == torch.float32 and has(be, "ell16") and _pad_block(self.G * self.K) == 16
               and V.X.shape[0] > 0 and V.X.shape[1] > 0 and _can_ell16(be, V.X, wide=False)):
             # f32, factor blocks of <= 16 columns: the operand of both directions never changes during a fit - laid
             # out once as sliced ELL (csrc/spmm_ell.hip): no per-row protocol is left in the product
             # (the transposed operand through the tile-staged transposition, csrc/tpack4.hip: 3 ms where the general
             #  kernel behind `transpose` took 14)
-            V.Xt = be.ell16(be.transpose_csr(V.X) if hasattr(be, "transpose_csr") else be.transpose(V.X))
+            V.Xt = be.ell16(be.transpose_csr(V.X) if has(be, "transpose_csr") else be.transpose(V.X))
             V.Xs = be.ell16(V.X)
-        elif self.T == torch.float32 and hasattr(be, "can_stream") and be.can_stream(V.X, 16):
+        elif self.T == torch.float32 and has(be, "can_stream") and be.can_stream(V.X, 16):
             # f32: both directions read row streams, built once
             V.Xt = be.transpose_stream(V.X)
             V.Xs = be.stream(V.X)
-        elif (self.T == torch.float64 and hasattr(be, "ell16") and _pad_block(self.G * self.K) == 16
+        elif (self.T == torch.float64 and has(be, "ell16") and _pad_block(self.G * self.K) == 16
               and V.X.shape[0] > 0 and V.X.shape[1] > 0 and _can_ell16(be, V.X, wide=True)):
             # f64 (the reference's default precision), factor blocks of <= 16 columns: the same static layout with
             # f32 stored values - one operand when the data is exact in f32, hi + lo otherwise - against f64 blocks
-            if hasattr(be, "ell16_pair"):
+            if has(be, "ell16_pair"):
                 V.Xs, V.Xt = be.ell16_pair(V.X, wide=True)
             else:
                 V.Xt = be.ell16(be.transpose(V.X), wide=True)
                 V.Xs = be.ell16(V.X, wide=True)
-        elif (self.T == torch.float64 and hasattr(be, "split_streams") and _pad_block(self.G * self.K) <= 32
+        elif (self.T == torch.float64 and has(be, "split_streams") and _pad_block(self.G * self.K) <= 32
               and V.X.shape[0] > 0 and V.X.shape[1] > 0):
             # f64 (the reference's default precision): the same row streams with f32 stored values -
             # one stream when the data is exact in f32, hi + lo otherwise - against f64 blocks
@@ -382,13 +383,13 @@ class MofaEngine(MofaDriver):
             if V.kind == "sparse":
                 V.ld = _pad_block(G * K)
                 V.TWs = torch.zeros((V.D, V.ld), dtype=T, device=dev)
-            elif K <= 16 and hasattr(self.be, "skinny_tn"):
+            elif K <= 16 and has(self.be, "skinny_tn"):
                 V.ld = 16
                 # f32: the library GEMM for A = Y (tau o W) had been 3 % ahead of mu_skinny_nn; with the branch-free,
                 # asm-prefetching build of r04 (views of whole 128-byte tiles) the kernel is 2 % ahead of it
                 # (c4: 0.465 against 0.475 s with the library GEMM)
                 own_f32 = V.D % 32 == 0
-                if (T == torch.float64 or own_f32) and hasattr(self.be, "skinny_nn"):
+                if (T == torch.float64 or own_f32) and has(self.be, "skinny_nn"):
                     V.T16 = [torch.zeros((V.D, 16), dtype=T, device=dev) for _ in range(G)]
                 else:
                     V.TWt = [torch.zeros((K, V.D), dtype=T, device=dev) for _ in range(G)]

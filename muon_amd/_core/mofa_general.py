@@ -35,6 +35,7 @@ import numpy as np
 import torch
 from scipy.sparse import issparse
 
+from .._operators import has
 from .mofa_common import A0, B0, LN_THETA0, TH_A0, TH_B0, MofaDriver, _can_ell16
 
 LIKELIHOODS = ("gaussian", "poisson", "bernoulli")
@@ -115,14 +116,14 @@ class GeneralMofaEngine(MofaDriver):
         # the alpha / theta / factor-ARD nodes and their ELBO terms: the fused kernels of MofaEngine (csrc/mofa_elbo.hip -
         # the same equations; ~170 tensor launches per iteration otherwise) keep these nodes in the fit's type
         # (the fused factor nodes have no spike: with spikeslab_factors the small nodes run as tensor operations)
-        self._fused_small = (hasattr(backend, "mofa_w_elbo") and hasattr(backend, "mofa_z_elbo") and K <= 32
+        self._fused_small = (has(backend, "mofa_w_elbo", "mofa_z_elbo") and K <= 32
                              and not spikeslab_factors)
         self._init_nodes(self._draw_z0(seed, row_offset, n_total), dtype, dtype if self._fused_small else torch.float64)
         self.gamma_z = torch.ones_like(self.EZ)
         self.EZh2 = self.EZ2.clone()
         self.lthz = torch.full((G, K), LN_THETA0, dtype=torch.float64, device=self.dev)
         self.l1mthz = torch.full((G, K), LN_THETA0, dtype=torch.float64, device=self.dev)
-        self._elbo_work = backend.mofa_elbo_work(K) if hasattr(backend, "mofa_elbo_work") and K <= 32 else None
+        self._elbo_work = backend.mofa_elbo_work(K) if has(backend, "mofa_elbo_work") and K <= 32 else None
         if self._fused_small:
             self._zs = torch.zeros((G, 2, K), dtype=torch.float64, device=self.dev)
         self._Ng_dev = self.Ng.to(self.dev)  # (resident: an iteration has no host -> device copies)
@@ -208,18 +209,18 @@ class GeneralMofaEngine(MofaDriver):
         # a poisson view stored sparse with every sample present never needs a dense chunk: for y = 0 the pseudo-data
         # depend on (z_n, w_d) only - dense sweeps over the two factor blocks + corrections over the stored entries
         # (csrc/mofa_poisson.hip, r04)
-        V.fused = bool(lik == "poisson" and V.kind == "sparse" and hasattr(be, "mofa_poisson_pass") and self.K <= 32
+        V.fused = bool(lik == "poisson" and V.kind == "sparse" and has(be, "mofa_poisson_pass") and self.K <= 32
                        and V.X.values.dtype == T and pres.all())
         # a bernoulli view stored sparse with every sample present needs none either (r06, csrc/mofa_bernoulli.hip): the
         # data enter through R = y - 1/2 and the likelihood only - sparse products - and the Jaakkola precision depends on
         # the two factor blocks alone: one dense sweep per update
-        V.fusedb = bool(lik == "bernoulli" and V.kind == "sparse" and hasattr(be, "mofa_jaakkola_sweep")
-                        and hasattr(be, "mofa_softplus_sweep") and self.K <= 16 and V.X.values.dtype == T and pres.all())
+        V.fusedb = bool(lik == "bernoulli" and V.kind == "sparse" and has(be, "mofa_jaakkola_sweep", "mofa_softplus_sweep")
+                        and self.K <= 16 and V.X.values.dtype == T and pres.all())
         if V.fused or V.fusedb:
             V.Xt = be.transpose(V.X)
         # the three sparse products of a fused bernoulli view multiply by one 16-column block each: the sliced-ELL layout
         # of MofaEngine's sparse views (csrc/spmm_ell.hip: 0.24 -> ~0.08 ms per product at 3e7 entries), laid out once
-        if V.fusedb and hasattr(be, "ell16"):
+        if V.fusedb and has(be, "ell16"):
             wide = T == torch.float64
             if min(V.X.shape) > 0 and _can_ell16(be, V.X, wide):
                 # (f64 values go in as hi + lo parts, the second only when some value is not exact in f32)
@@ -260,7 +261,7 @@ class GeneralMofaEngine(MofaDriver):
                 M = V.mask[lo:hi] if V.mask is not None else None
             else:
                 X = V.X
-                if hasattr(self.be, "densify_rows") and X.values.dtype == self.T:
+                if has(self.be, "densify_rows") and X.values.dtype == self.T:
                     Y = self.be.densify_rows(X, lo, hi)
                     p0 = p1 = 0
                 else:
@@ -303,7 +304,7 @@ class GeneralMofaEngine(MofaDriver):
             return Om, Om * Y, None, None
         zeta = Zc @ Wm.EW.T
         if V.lik == "poisson":
-            if hasattr(self.be, "mofa_poisson_pseudo") and Y.is_contiguous():
+            if has(self.be, "mofa_poisson_pseudo") and Y.is_contiguous():
                 R = self.be.mofa_poisson_pseudo(zeta, Y, V.kappa.contiguous(), 0)  # one pass, in place of zeta
                 zeta = None  # (no caller needs the prediction of a poisson chunk)
             else:
@@ -312,7 +313,7 @@ class GeneralMofaEngine(MofaDriver):
             if M is not None:
                 return V.kappa[None, :] * M, R * M, zeta, None
             return None, R, zeta, V.kappa
-        if hasattr(self.be, "mofa_jaakkola"):
+        if has(self.be, "mofa_jaakkola"):
             Om = self.be.mofa_jaakkola(zeta, Z2c @ Wm.EW2.T, (Zc ** 2) @ (Wm.EW ** 2).T)  # one pass
         else:
             xi2 = zeta ** 2 + Z2c @ Wm.EW2.T - (Zc ** 2) @ (Wm.EW ** 2).T
@@ -416,7 +417,7 @@ class GeneralMofaEngine(MofaDriver):
         Tm, b = self._allreduce(Tm, b)
         Tm = Tm.reshape(V.D, K, K)
         aw64 = (Wm.alpha if self.opts["ard_weights"] else torch.ones_like(Wm.alpha)).to(torch.float64).contiguous()
-        if hasattr(self.be, "mofa_gs_update") and K <= 32:
+        if has(self.be, "mofa_gs_update") and K <= 32:
             # one Gauss-Seidel sweep over the factors per feature, a thread per feature (csrc/mofa_stats.hip)
             self.be.mofa_gs_update(Tm.contiguous(), b.contiguous(), aw64, Wm.lth.to(torch.float64).contiguous(),
                                    Wm.l1mth.to(torch.float64).contiguous(), self.opts["spikeslab_weights"], Wm.EW,
@@ -502,7 +503,7 @@ class GeneralMofaEngine(MofaDriver):
                         a[l2 - lo:h2 - lo] += R @ self.W[m].EW
                 S = S.reshape(hi - lo, K, K)
                 ssf = self.opts["spikeslab_factors"]
-                if hasattr(self.be, "mofa_gs_update") and K <= 32:
+                if has(self.be, "mofa_gs_update") and K <= 32:
                     # (row slices of contiguous [N, K] tensors are contiguous: updated in place)
                     if ssf:  # the W form of the sweep: (alpha, ln theta, ln(1 - theta)) of this group
                         self.be.mofa_gs_update(S.contiguous(), a.contiguous(), az[g].to(torch.float64).contiguous(),
@@ -544,7 +545,7 @@ class GeneralMofaEngine(MofaDriver):
         for m, (V, Wm) in enumerate(zip(self.views, self.W)):
             # a stats view's expected squared residuals in one kernel per group, its node in one more (csrc/mofa_elbo.hip:
             # ~35 tensor launches per view and iteration otherwise); the tensor forms below remain for the CPU operator set
-            fast_stats = bool(V.stats and self._elbo_work is not None and hasattr(self.be, "mofa_stats_resid")
+            fast_stats = bool(V.stats and self._elbo_work is not None and has(self.be, "mofa_stats_resid")
                               and Wm.EW.dtype == self.T)
             if not fast_stats:
                 S = torch.zeros((G, V.D), dtype=f64, device=self.dev)
@@ -552,7 +553,7 @@ class GeneralMofaEngine(MofaDriver):
             part = torch.zeros((), dtype=f64, device=self.dev) if V.lik != "gaussian" else None
             chunked = not (V.fused or V.fusedb or V.stats)
             W2, Wsq = (Wm.EW2, Wm.EW ** 2) if chunked else (None, None)
-            if V.fused and getattr(be, "mofa_poisson_lik_with_b", False):
+            if V.fused and be.mofa_poisson_lik_with_b:
                 # the likelihood term and the NEXT W update's b = R^T <Z> read the same predictions: one sweep (r05)
                 out = self.be.mofa_poisson_pass(3, Wm.EW.contiguous(), self.EZ.contiguous(), V.kappa.contiguous(), V.Xt, pads=self._pois_pads)
                 hit = self._bnext.get(m)
@@ -592,7 +593,7 @@ class GeneralMofaEngine(MofaDriver):
                             Ngd[g] += float(hi - lo)
                         S[g] += res.sum(dim=0).to(f64)
                     elif V.lik == "poisson":
-                        if hasattr(self.be, "mofa_poisson_pseudo") and Y.is_contiguous():
+                        if has(self.be, "mofa_poisson_pseudo") and Y.is_contiguous():
                             t = self.be.mofa_poisson_pseudo(zeta, Y, None, 1)
                         else:
                             rate = torch.nn.functional.softplus(zeta).clamp(min=1e-300 if self.T == f64 else 1e-30)

@@ -29,6 +29,7 @@ import torch
 from scipy.sparse import csr_matrix, issparse
 
 from .._containers import is_anndata, is_mudata
+from .._operators import has
 
 _METRICS = ("euclidean", "sqeuclidean", "cosine", "cityblock", "manhattan", "chebyshev")
 
@@ -296,7 +297,7 @@ def _candidates_filtered(be, Xn: torch.Tensor, sq: torch.Tensor, kc: int, chunk_
     cnt = torch.empty((n,), dtype=torch.int32, device=dev)
     slot = torch.arange(cap, device=dev)[None, :]
     c_lo = p0
-    fused = hasattr(be, "knn_merge") and kc + cap <= 1024
+    fused = has(be, "knn_merge") and kc + cap <= 1024
     thr = cur_d.amax(dim=1).contiguous()
     while c_lo < n:
         c_hi = min(n, 2 * c_lo)
@@ -345,7 +346,7 @@ def device_knn(X: torch.Tensor, k: int, metric: str = "euclidean", chunk_elems: 
     sq = (Xn * Xn).sum(dim=1)
     ar = torch.arange(n, device=X.device)
     cand_all = None
-    if (gemm and backend is not None and hasattr(backend, "knn_filter") and X.dtype == torch.float64
+    if (gemm and backend is not None and has(backend, "knn_filter") and X.dtype == torch.float64
             and n >= 8192 and 4 * kc <= n // 2 and -(-p // 4) * 4 <= _KNN_FILTER_MAX_P):
         cand_all, cand_d = _candidates_filtered(backend, Xn, sq, kc, chunk_elems)
         if indices_only:
@@ -387,15 +388,15 @@ def fuzzy_simplicial_set(knn_idx: torch.Tensor, knn_dist: torch.Tensor, n_obs: i
     d = knn_dist.to(torch.float32).to(torch.float64)  # umap works on float32 distances
     n, k = d.shape
     target = math.log2(n_neighbors)
-    if backend is not None and hasattr(backend, "umap_strengths") and n > 0:
+    if backend is not None and has(backend, "umap_strengths") and n > 0:
         # rho, the 64 bisection steps for sigma and the strengths: a thread per row (csrc/wnn.hip)
         val = backend.umap_strengths(d.contiguous(), knn_idx.to(torch.int64).contiguous(), target, float(d.mean()))
         return _symmetrise(knn_idx, val, n_obs)
     pos = torch.where(d > 0, d, torch.full_like(d, float("inf")))
-    has = torch.isfinite(pos).any(dim=1)
+    some = torch.isfinite(pos).any(dim=1)
     # rho: the first positive distance in storage order (local_connectivity = 1)
     first = torch.argmax((d > 0).to(torch.int8), dim=1)
-    rho = torch.where(has, torch.gather(d, 1, first[:, None]).squeeze(1), torch.zeros(n, dtype=d.dtype, device=d.device))
+    rho = torch.where(some, torch.gather(d, 1, first[:, None]).squeeze(1), torch.zeros(n, dtype=d.dtype, device=d.device))
     lo = torch.zeros(n, dtype=d.dtype, device=d.device)
     hi = torch.full((n,), float("inf"), dtype=d.dtype, device=d.device)
     mid = torch.ones(n, dtype=d.dtype, device=d.device)
@@ -506,7 +507,7 @@ def _mean_operator(be, G: csr_matrix, cols_present=None):
         vals = np.repeat(1.0 / cnt, cnt).astype(np.float32)
     # (kNN rows are stored by ascending distance: column order is restored on the device)
     Gd = canonicalize(be, be.upload_csr(indptr, G.indices[keep], vals, G.shape, values_dtype=np.float32))
-    can = hasattr(be, "can_stream")
+    can = has(be, "can_stream")
     return be.stream(Gd) if can and be.can_stream(Gd, 64) else Gd
 
 
@@ -533,7 +534,7 @@ def _bandwidths(be, X: torch.Tensor, G: csr_matrix, n_bandwidth_neighbors: int) 
     n = X.shape[0]
     G = G.tocsr()
     dev = X.device
-    if (hasattr(be, "wnn_bandwidth") and X.dtype == torch.float64 and X.shape[1] <= 256 and X.is_contiguous()
+    if (has(be, "wnn_bandwidth") and X.dtype == torch.float64 and X.shape[1] <= 256 and X.is_contiguous()
             and n_bandwidth_neighbors <= 64):
         # one wave per cell (csrc/wnn.hip): candidates from the reverse graph, sorted and counted in LDS
         R = G.T.tocsr()
@@ -827,11 +828,11 @@ def submatrix_device(backend, X, row_mask=None, col_mask=None):
         table[~col_mask] = -1
         n_cols = int(col_mask.sum())
     rows_d, table_d = backend.to_device(rows, np.int64), backend.to_device(table, np.int32)
-    if hasattr(backend, "csr_submatrix"):
+    if has(backend, "csr_submatrix"):
         Y = backend.csr_submatrix(X, rows_d, table_d, n_cols)
     else:
         Y = _submatrix_tensor(X, rows_d, table_d, n_cols)
-    if hasattr(backend, "with_slab_ptr"):
+    if has(backend, "with_slab_ptr"):
         Y = backend.with_slab_ptr(Y)  # (resident copies are canonical: sorted rows stay sorted)
     return Y
 
@@ -952,7 +953,7 @@ def qc_device(backend, X, comm=None):
     from .._comm import default_comm
 
     comm = default_comm(comm)
-    if hasattr(backend, "csr_qc"):
+    if has(backend, "csr_qc"):
         row_nnz, rowsum, col_nnz, colsum = backend.csr_qc(X)
     else:  # operator sets without the kernel: the same numbers as tensor operations
         n, d = X.shape

@@ -38,6 +38,8 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix, issparse
 
+from .._operators import has
+
 _SQRT_2PI = float(np.sqrt(2 * np.pi))
 _KERNEL_METHODS = ("snf_affinity", "snf_normalize", "snf_topk", "snf_p_scale", "snf_diffuse")
 
@@ -288,9 +290,9 @@ def snf(mdata, n_neighbors: int = 20, neighbor_keys: Optional[Union[str, Dict[st
 
     diag = {} if diagnostics is None else diagnostics
     diag["distances"] = [kind for kind, _ in sources]
-    kernel = all(hasattr(be, name) for name in _KERNEL_METHODS)
+    kernel = has(be, *_KERNEL_METHODS)
     diag["path"] = "kernel" if kernel else "tensor"
-    if hasattr(be, "free_memory"):
+    if has(be, "free_memory"):
         need, free = _need_bytes(n, M, k), int(be.free_memory())
         if need > free:
             raise MemoryError(f"muon_amd.tl.snf: {M} modalities of {n} observations need {need} bytes on the device "

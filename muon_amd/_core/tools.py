@@ -156,7 +156,7 @@ def _needs_general_engine(backend, views, lik, groups, n_factors, spikeslab_fact
              or bool(spikeslab_factors))
     if comm.world_size > 1:
         t = torch.tensor([n_groups, int(local)], dtype=torch.int64)
-        if getattr(backend, "name", "") == "hip":
+        if backend.name == "hip":
             t = t.to(backend.device)
         n_groups, local = (int(x) for x in comm.all_reduce_max(t).tolist())
     wide = n_groups * K > 64 and any(issparse(v) for v in views)

@@ -1,5 +1,8 @@
 """ctypes binding of libmuon_amd.so (the C-ABI declared in include/muon_amd.h).
 
+The header is the only declaration of the C-ABI: ``SIGNATURES`` (name -> restype, argtypes) is parsed from it at
+import (``parse_header``), and a prototype the parser does not recognise is an error at import, not a guess.
+
 The shared object is built in-tree by ``muon_amd/csrc/build.py`` (hipcc, gfx950).  There is
 no fallback: if the library is missing, or no MI355X-class device is visible when a kernel
 is requested, the product path raises ``MuonAmdError``.
@@ -13,10 +16,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmuon_amd.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "muon_amd.h")
 
 F32, F64 = 0, 1
 TFIDF_LOG_TF, TFIDF_LOG_IDF, TFIDF_LOG_TFIDF = 1, 2, 4
@@ -29,164 +34,46 @@ class MuonAmdError(RuntimeError):
 _lib = None
 _lock = threading.Lock()
 
-_i64, _i32, _dbl, _vp, _sz, _u64 = C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_uint64
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "size_t": C.c_size_t,
+            "uint64_t": C.c_uint64, "mu_status": C.c_int}
+_PROTOTYPE = re.compile(r"([\w\s\*]+?)\b(mu_\w+)\s*\(([^()]*)\)")
 
-# name -> (restype, argtypes); mirrors include/muon_amd.h one to one
-SIGNATURES = {
-    "mu_version": (C.c_int, []),
-    "mu_last_error": (C.c_char_p, []),
-    "mu_device_count": (C.c_int, [C.POINTER(C.c_int)]),
-    "mu_set_device": (C.c_int, [_i32]),
-    "mu_device_info": (C.c_int, [_i32, C.c_char_p, _i32, C.POINTER(C.c_int), C.POINTER(_sz)]),
-    "mu_malloc": (C.c_int, [C.POINTER(_vp), _sz]),
-    "mu_free": (C.c_int, [_vp]),
-    "mu_memcpy_h2d": (C.c_int, [_vp, _vp, _sz, _vp]),
-    "mu_memcpy_d2h": (C.c_int, [_vp, _vp, _sz, _vp]),
-    "mu_memset": (C.c_int, [_vp, _i32, _sz, _vp]),
-    "mu_stream_sync": (C.c_int, [_vp]),
-    "mu_host_hash64": (C.c_int, [_vp, _sz, _i32, _u64, C.POINTER(_u64)]),
-    "mu_csr_row_col_sums_worksize": (_sz, [_i64, _i64]),
-    "mu_csr_row_col_sums": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_tfidf_idf": (C.c_int, [_i32, _i64, _dbl, _vp, _i32, _vp, _vp]),
-    "mu_tfidf_scale": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _vp]),
-    "mu_tfidf_scale_sweep": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _vp,
-                                       _sz, _i32, _vp]),
-    "mu_csr_count_nonzero": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp]),
-    "mu_csr_compact_nonzero": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_exclusive_scan_i64": (C.c_int, [_i64, _vp, _vp, _vp]),
-    "mu_binarize_values": (C.c_int, [_i32, _i64, _vp, _vp]),
-    "mu_csr_qc_worksize": (_sz, [_i64, _i64]),
-    "mu_csr_qc": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "mu_csr_submatrix_count": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_csr_submatrix_fill": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_frag_chunk": (C.c_int, []),
-    "mu_frag_ranges": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "mu_frag_overlap_count": (C.c_int, [_i64, _i64] + [_vp] * 9 + [_i64, _i64, _vp, _vp]),
-    "mu_frag_overlap_emit": (C.c_int, [_i64, _i64] + [_vp] * 10 + [_i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_frag_pileup": (C.c_int, [_i64, _i64] + [_vp] * 10 + [_i64, _i64, _i64, _vp, _vp]),
-    "mu_frag_pileup_scan": (C.c_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "mu_frag_length_classes": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
-    "mu_csr_transpose_worksize": (_sz, [_i64, _i64, _i64]),
-    "mu_csr_transpose": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_spmm_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
-    "mu_spmm_stream_k": (C.c_int, [_i64]),
-    "mu_tfidf_scale_sweep_stream": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _vp, _sz, _i32,
-                                              _vp, _vp, _vp, _vp]),
-    "mu_csr_slab_ptr": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_csr_slab_ptr_width": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_csr_row_col_sums_sp": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "mu_tfidf_scale_sweep_sp": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _vp, _vp]),
-    "mu_tpack4_supported": (C.c_int, [_i64, _i64, _i64]),
-    "mu_tpack4_geometry": (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "mu_tpack4_worksize": (_sz, [_i64, _i64, _i64]),
-    "mu_tpack4_count": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "mu_tpack4_fill_stream": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_tpack4_fill_csr": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_tpack4_status": (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_int)]),
-    "mu_tpack4_err_offset": (_sz, [_i64, _i64, _i64]),
-    "mu_tpack4_phase_cycles": (C.c_int, [_vp, _i32]),
-    "mu_csr_stream_len": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "mu_csr_stream_fill": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_spmm_stream_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
-    "mu_spmm_stream_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp]),
-    "mu_csr_slice_stream": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_spmm_stream_ranges_f32": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp]),
-    "mu_spmm_stream_slab_ok": (C.c_int, [_i32, _i32, _i32]),
-    "mu_spmm_stream_slab_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp]),
-    "mu_spmm_stream_ranges_slab_f32": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
-    "mu_tpack4_cnt_offset": (_sz, [_i64, _i64, _i64]),
-    "mu_tperm_stage_pairs": (C.c_int, []),
-    "mu_tperm_plan": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_tperm_fill": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_spmm_ell16_waves": (C.c_int, [_i64]),
-    "mu_dense_col_moments_chunks": (C.c_int, [_i64, _i64]),
-    "mu_dense_col_moments": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
-    "mu_ell16_fill": (C.c_int, [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_spmm_ell16_f32": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_spmm_ell16_f64": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
-    "mu_spmm_ell16_parts": (C.c_int, [_i64, _i64, _i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "mu_spmm_ell16_parts_f32": (C.c_int, [_i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mu_spmm_ell16_parts_f64": (C.c_int, [_i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mu_tune_set": (C.c_int, [C.c_char_p, _i32]),
-    "mu_tune_get": (C.c_int, [C.c_char_p]),
-    "mu_spmm_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
-    "mu_gram_worksize": (_sz, [_i64, _i32]),
-    "mu_gram_f32": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_gram_cross_f32": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_dense_apply_f32": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "mu_dense_project_out_f32": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp]),
-    "mu_chol_rinv_f64": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp]),
-    "mu_randn_f32": (C.c_int, [_i64, _u64, _vp, _vp]),
-    "mu_skinny_tn_worksize": (_sz, [_i32, _i64, _i64]),
-    "mu_skinny_nn": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_skinny_tn": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_skinny_nn_f64_f32": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_skinny_tn_f64_f32": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mu_mofa_update_w": (C.c_int, [_i32, _i64, _i32, _i32] + [_vp] * 7 + [_i32] + [_vp] * 6),
-    "mu_mofa_update_z": (C.c_int, [_i32, _i64, _i32, _i32, _i32] + [_vp] * 11),
-    "mu_mofa_rowstats_work_doubles": (_sz, [_i32]),
-    "mu_mofa_rowstats": (C.c_int, [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64,
-                                   _vp, _vp, _vp, _vp, _vp]),
-    "mu_umap_strengths_f64": (C.c_int, [_i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp]),
-    "mu_wnn_bandwidth_f64": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _vp, _vp, _vp]),
-    "mu_knn_filter_f64": (C.c_int, [_i64, _i64, _i64, _i32] + [_vp] * 6 + [_i32] + [_vp] * 4),
-    "mu_knn_merge_f64": (C.c_int, [_i64, _i32, _i32] + [_vp] * 9),
-    "mu_csr_densify_rows": (C.c_int, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_jaakkola": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_poisson_pseudo": (C.c_int, [_i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_poisson_blocks": (_i64, [_i64, _i64]),
-    "mu_mofa_poisson_blocks_for": (_i64, [_i32, _i32, _i32, _i64, _i64]),
-    "mu_mofa_poisson_dense": (C.c_int, [_i32, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_poisson_sparse": (C.c_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_poisson_dense_ld": (C.c_int, [_i32, _i32, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_poisson_sparse_ld": (C.c_int, [_i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mu_mofa_jaakkola_cols": (C.c_int, [_i32]),
-    "mu_mofa_pack_moments": (C.c_int, [_i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "mu_mofa_jaakkola_blocks": (_i64, [_i32, _i32, _i64, _i64]),
-    "mu_mofa_jaakkola_sweep": (C.c_int, [_i32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
-    "mu_mofa_gs_update": (C.c_int, [_i32, _i64, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
-    "mu_mofa_elbo_work_doubles": (_sz, [_i32]),
-    "mu_mofa_tau_elbo": (C.c_int, [_i32, _i64, _i32, _i32] + [_vp] * 7 + [_dbl, _dbl] + [_vp] * 5),
-    "mu_mofa_stats_resid": (C.c_int, [_i32, _i64, _i32, _i64] + [_vp] * 7),
-    "mu_mofa_tau_finish": (C.c_int, [_i32, _i64, _vp, _vp, _dbl, _dbl] + [_vp] * 5),
-    "mu_mofa_w_elbo": (C.c_int, [_i32, _i64, _i32, _i32, _i32] + [_vp] * 3 + [_dbl] * 5 + [_vp] * 7),
-    "mu_mofa_z_sums": (C.c_int, [_i32, _i64, _i64, _i32] + [_vp] * 5),
-    "mu_mofa_z_elbo": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _dbl, _dbl] + [_vp] * 4),
-    "mu_prot_max_proteins": (C.c_int, []),
-    "mu_prot_moments_worksize": (_sz, [_i64, _i64]),
-    "mu_prot_log_moments_csr": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
-    "mu_prot_log_moments_dense": (C.c_int, [_i32, _i64, _i64, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
-    "mu_prot_dsb_fit": (C.c_int, [_i32, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
-                                  _vp, _vp]),
-    "mu_ica_max_components": (C.c_int, []),
-    "mu_ica_worksize": (_sz, [_i64, _i32, _i32]),
-    "mu_ica_sweep_f64": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _i32, _dbl, _vp, _vp, _vp, _sz, _i32, _vp]),
-    "mu_group_moments_max_groups": (C.c_int, []),
-    "mu_rank_row_cap": (C.c_int, []),
-    "mu_group_moments": (C.c_int, [_i32, _i64, _i64, _i64, _i32] + [_vp] * 8),
-    "mu_rank_sums": (C.c_int, [_i32, _i64, _i64, _i64, _i32, _i64] + [_vp] * 8),
-    "mu_cluster_max_table": (C.c_int, []),
-    "mu_cluster_max_layers": (C.c_int, []),
-    "mu_cluster_move_f64": (C.c_int, [_i64, _vp, _i64, _i64] + [_vp] * 6 + [_i32, _vp, _vp, C.POINTER(_dbl), _i32, _vp, _vp,
-                                      _vp, _vp]),
-    "mu_cluster_segsum_f64": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp]),
-    "mu_motif_max_len": (C.c_int, []),
-    "mu_motif_tile": (C.c_int, []),
-    "mu_motif_group": (C.c_int, []),
-    "mu_motif_room": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
-    "mu_motif_count": (C.c_int, [_i64, _i64, _i32] + [_vp] * 8),
-    "mu_motif_write": (C.c_int, [_i64, _i64, _i32] + [_vp] * 10 + [_i64] + [_vp] * 5),
-    "mu_snf_max_k": (C.c_int, []),
-    "mu_snf_affinity_max_k": (C.c_int, []),
-    "mu_snf_max_terms": (C.c_int, []),
-    "mu_snf_affinity_f64": (C.c_int, [_i64, _i32, _i64, _vp, _i64, _vp, _dbl, _dbl, _vp, _vp]),
-    "mu_snf_normalize_f64": (C.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp]),
-    "mu_snf_topk_f64": (C.c_int, [_i64, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "mu_snf_p_scale_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mu_snf_diffuse_f64": (C.c_int, [_i64, _i32, C.POINTER(_vp), _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "mu_synth_row_nnz": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp]),
-    "mu_synth_fill": (C.c_int, [_i64, _i64, _i64, _i32, _dbl, _u64, _vp, _vp, _vp, _vp]),
-}
+
+def _ctype(text: str, decl: str):
+    """``const char*`` and ``char*`` are c_char_p; every other pointer is c_void_p, which takes an address, None,
+    ``byref(...)`` and ctypes arrays - host pointers (``int* count``) as well as device pointers."""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return C.c_char_p if words[0] == "char" else C.c_void_p
+    if words and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    raise MuonAmdError(f"include/muon_amd.h: `{text.strip()}` in `{decl}` is no type the ctypes table knows")
+
+
+def parse_header(src: str) -> dict:
+    """name -> (restype, argtypes) of every prototype in the text of include/muon_amd.h.  Whatever is left after the
+    comments, the preprocessor lines, the ``mu_status`` enum and the ``extern "C"`` braces must be a prototype of known
+    types: anything else raises, with the declaration in the message."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
+    src = re.sub(r"typedef\s+enum\s*\{[^}]*\}\s*mu_status\s*;", " ", src)
+    src = re.sub(r'extern\s+"C"\s*\{|\}', " ", src)
+    table = {}
+    for decl in (" ".join(d.split()) for d in src.split(";")):
+        if not decl:
+            continue
+        m = _PROTOTYPE.fullmatch(decl)
+        if m is None:
+            raise MuonAmdError(f"include/muon_amd.h: `{decl}` is no prototype the ctypes table understands")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        table[name] = (_ctype(ret, decl), [_ctype(p, decl) for p in params])
+    return table
+
+
+# name -> (restype, argtypes): include/muon_amd.h is the one declaration of the C-ABI
+with open(HEADER_PATH) as _f:
+    SIGNATURES = parse_header(_f.read())
 
 
 def lib():

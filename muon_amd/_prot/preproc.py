@@ -32,6 +32,7 @@ from scipy.sparse import issparse
 
 from .._backend import DeviceCSR
 from .._containers import is_anndata, is_mudata
+from .._operators import has
 
 _REG_COVAR = 1e-6
 _TOL = 1e-3
@@ -64,7 +65,7 @@ def _to_device(be, X):
         if not (m.has_canonical_format and m.has_sorted_indices):
             m = m.copy()
             m.sum_duplicates()
-        kw = {"slab_ptr": False} if hasattr(be, "with_slab_ptr") else {}  # (no sweep of tfidf / lsi follows)
+        kw = {"slab_ptr": False} if has(be, "with_slab_ptr") else {}  # (no sweep of tfidf / lsi follows)
         return be.upload_csr(m.indptr, m.indices, m.data, m.shape, values_dtype=_value_dtype(m.dtype), **kw)
     a = np.asarray(X)
     return be.to_device(a, _value_dtype(a.dtype))
@@ -230,9 +231,9 @@ def _dsb_arrays(cells_X, empty_X, *, pseudocount=10, denoise_counts=True, ctrl_i
     pc = float(pseudocount)
     Xc, Xe = _to_device(be, cells_X), _to_device(be, empty_X)
     n, d = (int(s) for s in Xc.shape)
-    limit = be.prot_max_proteins() if hasattr(be, "prot_max_proteins") else 0
+    limit = be.prot_max_proteins() if has(be, "prot_max_proteins") else 0
     kernels = not force_tensor and d <= limit
-    if kernels and hasattr(be, "prot_log_moments") and pc > 0 and Xe.shape[0] >= 1:
+    if kernels and has(be, "prot_log_moments") and pc > 0 and Xe.shape[0] >= 1:
         mean, std = be.prot_log_moments(Xe, pc)
     else:  # (also pseudocount == 0: log(0) makes the closed form for the zeros invalid; numpy's non-finite results)
         mean, std = _log_moments_torch(Xe, pc)
@@ -246,7 +247,7 @@ def _dsb_arrays(cells_X, empty_X, *, pseudocount=10, denoise_counts=True, ctrl_i
             # scikit-learn's validate_data(ensure_min_samples=2): a cell's proteins are the samples of its mixture
             raise ValueError(f"Found array with {d} sample(s) (shape=({d}, 1)) while a minimum of 2 is required by "
                              "GaussianMixture.")
-        use_fit = kernels and hasattr(be, "prot_dsb_fit")
+        use_fit = kernels and has(be, "prot_dsb_fit")
         parts = []
         for lo, hi, u in _resp_chunks(random_state, n, d):
             resp = be.to_device(u, np.float64)
@@ -494,7 +495,7 @@ def clr(adata, inplace: bool = True, axis: int = 0, flavor: str = "seurat", *, b
         # the three arrays of a CSC matrix are the CSR of its transpose: `major` = the compressed axis
         major = 0 if x.format == "csr" else 1
         shape = (x.shape[major], x.shape[1 - major])
-        kw = {"slab_ptr": False} if hasattr(be, "with_slab_ptr") else {}
+        kw = {"slab_ptr": False} if has(be, "with_slab_ptr") else {}
         X = be.upload_csr(x.indptr, x.indices, x.data, shape, values_dtype=np.float64, **kw)
         lv = torch.log1p(X.values)
         major_sum, minor_sum = be.row_col_sums(DeviceCSR(X.indptr, X.indices, lv, X.shape))

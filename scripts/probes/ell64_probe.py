@@ -3,9 +3,8 @@ row-stream kernel, 125 000 x 200 000.  The layout is built here with tensor oper
 usage: python scripts/probes/ell64_probe.py [cells] [peaks]
 ARCHIVED with its kernel (scripts/probes/spmm_ell64.hip is not compiled into the library: the experiment was a no-go,
 DESIGN.md 4.4, profiles/r04_ell64_probe.txt).  To run it again: copy the .hip into muon_amd/csrc/, add it to
-csrc/build.py SOURCES with EXTRA ["-Wno-inline-asm", "-std=c++20"], declare
-    "mu_spmm_ell64_f32": (C.c_int, [_i32, _i32, _i64, _i64] + [_vp] * 8)
-in muon_amd/_ffi.py SIGNATURES (and the prototype at the end of the .hip in include/muon_amd.h), rebuild."""
+csrc/build.py SOURCES with EXTRA ["-Wno-inline-asm", "-std=c++20"], put the prototype at the end of the .hip into
+include/muon_amd.h (muon_amd/_ffi.py reads its ctypes table from there), rebuild."""
 import sys
 import time
 

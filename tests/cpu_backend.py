@@ -12,9 +12,10 @@ import torch
 
 from muon_amd._backend import DeviceCSR
 from muon_amd._ffi import TFIDF_LOG_IDF, TFIDF_LOG_TF, TFIDF_LOG_TFIDF
+from muon_amd._operators import OperatorSet
 
 
-class CpuTestBackend:
+class CpuTestBackend(OperatorSet):
     name = "cpu-test"
     device = torch.device("cpu")
 
@@ -42,7 +43,8 @@ class CpuTestBackend:
 
         return _Done()
 
-    def upload_csr(self, indptr, indices, values, shape, values_dtype=None):
+    def upload_csr(self, indptr, indices, values, shape, values_dtype=None, slab_ptr=True):
+        # (slab_ptr: ignored - this set keeps no derived tables, `with_slab_ptr` is not among its operators)
         return DeviceCSR(self.to_device(indptr, np.int64), self.to_device(indices, np.int32),
                          self.to_device(values, values_dtype), (int(shape[0]), int(shape[1])))
 
@@ -50,7 +52,8 @@ class CpuTestBackend:
     def _sp(X):
         return sp.csr_matrix((X.values.numpy(), X.indices.numpy(), X.indptr.numpy()), shape=X.shape)
 
-    def row_col_sums(self, X):
+    def row_col_sums(self, X, keep_work=False):
+        assert not keep_work  # (the hand-off of the HIP sweeps: asked for behind `slab_ptr_from_work` only)
         m = self._sp(X).astype(np.float64)
         return (torch.from_numpy(np.asarray(m.sum(axis=1)).reshape(-1).copy()),
                 torch.from_numpy(np.asarray(m.sum(axis=0)).reshape(-1).copy()))
@@ -63,7 +66,8 @@ class CpuTestBackend:
             v = torch.log1p(v)
         return v
 
-    def tfidf_scale(self, X, rowsum, idf, scale, flags, out=None):
+    def tfidf_scale(self, X, rowsum, idf, scale, flags, out=None, emit=None, work=None, gather=False):
+        assert emit is None and work is None and not gather  # (the HIP sweep's stream target and hand-offs)
         T = X.values.dtype
         rows = torch.repeat_interleave(torch.arange(X.shape[0]), X.indptr[1:] - X.indptr[:-1])
         inv = (1.0 / rowsum.to(T))[rows]
@@ -98,9 +102,12 @@ class CpuTestBackend:
         return DeviceCSR(torch.from_numpy(t.indptr.astype(np.int64)), torch.from_numpy(t.indices.astype(np.int32)),
                          torch.from_numpy(t.data.copy()), (X.shape[1], X.shape[0]))
 
-    def spmm(self, X, Q, out=None):
+    def spmm(self, X, Q, out=None, accumulate=False):
         dt = Q.numpy().dtype
         y = torch.from_numpy((self._sp(X).astype(dt) @ Q.numpy()).astype(dt))
+        if accumulate:
+            out += y
+            return out
         if out is not None:
             out.copy_(y)
             return out

@@ -14,6 +14,7 @@ import torch
 from scipy.spatial.distance import cdist
 
 from muon_amd._core import preproc as pp
+from muon_amd._operators import has
 from oracle import wnn_oracle
 
 
@@ -38,8 +39,8 @@ class CountingBackend:
         self.overflowed_panels = 0
 
     def __getattr__(self, name):
-        f = getattr(self._be, name)  # (AttributeError where the backend lacks it: `hasattr` answers as for the backend)
-        if name == "knn_merge":
+        f = getattr(self._be, name)  # (AttributeError where the backend lacks it: `has` answers as for the backend)
+        if name == "knn_merge" and f is not None:  # (None: declared, not implemented by this backend)
             def counted(*a):
                 self.calls[name] += 1
                 return f(*a)
@@ -217,7 +218,7 @@ def _run_candidates(be, X, kc, cap):
         n_panels, c = n_panels + 1, 2 * c
     assert proxy.calls["knn_filter"] == n_panels
     cap = cap or 3 * kc + 64
-    if hasattr(be, "knn_merge"):  # the fused merge runs exactly where list and buffer fit the kernel's LDS
+    if has(be, "knn_merge"):  # the fused merge runs exactly where list and buffer fit the kernel's LDS
         assert proxy.calls["knn_merge"] == (n_panels if kc + cap <= 1024 else 0)
     return got_i.cpu().numpy(), got_d.cpu().numpy(), proxy
 

@@ -17,6 +17,7 @@ import muon_amd as mu
 from muon_amd._atac.preproc import DEVICE_ATTR, attach_device, resident
 from muon_amd._core import io as mio
 from muon_amd._core.preproc import _submatrix_tensor, submatrix_device
+from muon_amd._operators import has
 from tests.cpu_backend import CpuTestBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -424,8 +425,8 @@ def test_qc_metrics_two_row_shards_gloo():
 
 
 def test_tensor_fallback_is_what_the_backend_would_be_asked_for():
-    """the operator set of the CPU tests has no csr_submatrix / csr_qc: the tensor forms serve (the hasattr pattern)"""
-    assert not hasattr(BE, "csr_submatrix") and not hasattr(BE, "csr_qc")
+    """the operator set of the CPU tests has no csr_submatrix / csr_qc: the tensor forms serve (`_operators.has`)"""
+    assert not has(BE, "csr_submatrix") and not has(BE, "csr_qc")
     m = _counts(10, 8, seed=4)
     X = BE.upload_csr(m.indptr, m.indices, m.data, m.shape)
     Y = _submatrix_tensor(X, torch.tensor([1, 4, 9]), torch.tensor([0, -1, 1, -1, 2, 3, -1, 4], dtype=torch.int32), 5)

@@ -1,6 +1,7 @@
 """Repository contracts that need no GPU: the C-ABI library loads and exports every symbol
-include/muon_amd.h declares, the ctypes table covers them, and the product package never
-touches the oracle (which is test infrastructure)."""
+include/muon_amd.h declares, the ctypes table derived from it covers them, the operator set is
+declared once (muon_amd/_operators.py) and both backends keep to it, and the product package
+never touches the oracle (which is test infrastructure)."""
 import ctypes
 import os
 import re
@@ -32,6 +33,136 @@ def test_ffi_table_matches_header():
 
     assert sorted(_ffi.SIGNATURES) == _declared()
     _ffi.lib()  # loads and binds every entry
+
+
+def test_ffi_table_entries_written_out_by_hand():
+    """the parser of muon_amd/_ffi.py pinned by something that is not itself: whole entries, typed in from the header"""
+    from ctypes import c_char_p, c_double, c_int, c_int64, c_size_t, c_uint64, c_void_p
+
+    from muon_amd import _ffi
+
+    i32, i64, dbl, vp, sz, u64 = c_int, c_int64, c_double, c_void_p, c_size_t, c_uint64
+    want = {
+        "mu_version": (i32, []),
+        "mu_last_error": (c_char_p, []),
+        "mu_device_info": (i32, [i32, c_char_p, i32, vp, vp]),
+        "mu_host_hash64": (i32, [vp, sz, i32, u64, vp]),
+        "mu_csr_row_col_sums_worksize": (sz, [i64, i64]),
+        "mu_spmm_f32": (i32, [i64, i64, vp, vp, vp, vp, i32, vp, i32, vp]),
+        "mu_tpack4_geometry": (i32, [i64, i64, i64, vp, vp, vp]),
+        "mu_tune_set": (i32, [c_char_p, i32]),
+        "mu_mofa_poisson_blocks": (i64, [i64, i64]),
+        "mu_snf_affinity_f64": (i32, [i64, i32, i64, vp, i64, vp, dbl, dbl, vp, vp]),
+        "mu_cluster_move_f64": (i32, [i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    }
+    for name, sig in want.items():
+        assert _ffi.SIGNATURES[name] == sig, name
+    assert len(_ffi.SIGNATURES) == len(_declared())
+
+
+def test_ffi_parser_refuses_what_it_does_not_recognise():
+    from muon_amd import _ffi
+
+    ok = "/* c */ int mu_a(int64_t n, const float* d_x, void* stream);\nsize_t mu_b(void);"
+    assert _ffi.parse_header(ok) == {"mu_a": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+                                     "mu_b": (ctypes.c_size_t, [])}
+    for bad, word in (("int mu_a(unsigned n);", "unsigned"), ("int mu_a(float x);", "float"),
+                      ("long mu_a(int n);", "long"), ("int mu_a(int n) { return n; }", "mu_a"),
+                      ("struct mu_s { int a; };", "mu_s"), ("int other(int n);", "other")):
+        with pytest.raises(_ffi.MuonAmdError, match=word):
+            _ffi.parse_header(bad)
+
+
+def test_host_pointers_pass_through_the_derived_table():
+    """`int* count`, `int64_t* rows_per_block`, `uint64_t* h_out`, `const double* h_coef`: c_void_p in the table,
+    given as byref(...) or a ctypes array by the callers"""
+    import numpy as np
+
+    from muon_amd import _ffi
+
+    lib = _ffi.lib()
+    n = ctypes.c_int(-7)
+    assert lib.mu_device_count(ctypes.byref(n)) in (0, -3) and n.value >= 0  # (-3: MU_ERR_NO_DEVICE, count written 0)
+    rpb, G, Ct = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+    assert lib.mu_tpack4_geometry(1000, 9000, 5000, ctypes.byref(rpb), ctypes.byref(G), ctypes.byref(Ct)) == 0
+    assert rpb.value * (G.value - 1) < 1000 <= rpb.value * G.value and Ct.value > 0  # (the row blocks cover the rows)
+    ct = ctypes.c_int(0)
+    assert lib.mu_tpack4_geometry(1000, 9000, 5000, None, None, ctypes.byref(ct)) == 0 and ct.value == Ct.value
+    b = np.arange(64, dtype=np.uint8)
+    out, again = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    assert lib.mu_host_hash64(b.ctypes.data, b.size, 1, 0, ctypes.byref(out)) == 0
+    assert lib.mu_host_hash64(b.ctypes.data, b.size, 2, 0, ctypes.byref(again)) == 0 and out.value == again.value != 0
+    coef = (ctypes.c_double * 4)(1, 1, 1, 1)
+    assert lib.mu_cluster_move_f64(0, None, 4, 4, None, None, None, None, None, None, 9, None, None, coef, 0, None, None,
+                                   None, None) == -1 and lib.mu_last_error()
+
+
+def _public(cls):
+    """the public callables a class defines itself, read without an instance"""
+    return {n for n, v in vars(cls).items() if not n.startswith("_") and callable(getattr(cls, n))}
+
+
+def _optional():
+    from muon_amd._operators import OperatorSet
+
+    return {n for n, v in vars(OperatorSet).items() if not n.startswith("_") and v is None}
+
+
+def test_operator_set_partitions_the_hip_backend_exactly():
+    from muon_amd import _operators
+    from muon_amd._backend import HipBackend
+    from muon_amd._operators import OperatorSet
+
+    required, optional = set(OperatorSet.REQUIRED), _optional()
+    assert len(required) == len(OperatorSet.REQUIRED) and not (required & optional)
+    assert not any(hasattr(OperatorSet, n) for n in required)  # (declared, not stubbed)
+    assert _public(OperatorSet) == set() and _operators.DECLARED == required | optional
+    hip = _public(HipBackend)
+    assert optional - hip == set(), "declared optional, but HipBackend has no such operator"
+    assert hip == optional | required, sorted(hip ^ (optional | required))
+    # the flags: declared with the defaults of a set that says nothing
+    assert (OperatorSet.name, OperatorSet.skinny_mixed, OperatorSet.mofa_poisson_lik_with_b) == ("", False, False)
+    assert (HipBackend.name, HipBackend.skinny_mixed, HipBackend.mofa_poisson_lik_with_b) == ("hip", True, True)
+
+
+def test_cpu_test_backend_is_inside_the_contract():
+    import inspect
+
+    from muon_amd._backend import HipBackend
+    from muon_amd._operators import OperatorSet
+    from tests.cpu_backend import CpuTestBackend
+
+    cpu = _public(CpuTestBackend)
+    assert cpu <= _optional() | set(OperatorSet.REQUIRED), sorted(cpu - _optional() - set(OperatorSet.REQUIRED))
+    assert set(OperatorSet.REQUIRED) <= cpu, sorted(set(OperatorSet.REQUIRED) - cpu)
+    assert issubclass(CpuTestBackend, OperatorSet) and issubclass(HipBackend, OperatorSet)
+    for name in sorted(cpu & _public(HipBackend)):
+        a, b = (inspect.signature(getattr(c, name)).parameters for c in (HipBackend, CpuTestBackend))
+        assert [(p.name, p.default, p.kind) for p in a.values()] == [(p.name, p.default, p.kind) for p in b.values()], name
+
+
+def test_has_fails_loudly_on_an_undeclared_name():
+    from muon_amd._backend import HipBackend
+    from muon_amd._operators import OperatorSet, has
+    from tests.cpu_backend import CpuTestBackend
+
+    class Forwarding:  # (a double that hides one operator and forwards the rest, as the GPU tests build them)
+        def __getattr__(self, name):
+            if name == "chol_rinv":
+                raise AttributeError(name)
+            return getattr(be, name)
+
+    be = CpuTestBackend()
+    for ops in (OperatorSet(), be, HipBackend, Forwarding(), object()):
+        with pytest.raises(AttributeError):
+            has(ops, "no_such_operator")
+        with pytest.raises(AttributeError):
+            has(ops, "spmm", "can_ell16")
+    for name in sorted(_optional()):
+        assert has(OperatorSet(), name) is False and has(HipBackend, name) is True, name
+    assert has(HipBackend, *OperatorSet.REQUIRED, *sorted(_optional()))
+    assert has(be) and has(be, "spmm", "chol_rinv") and not has(be, "spmm", "csr_qc") and not has(be, "csr_qc", "spmm")
+    assert has(Forwarding(), "spmm", "skinny_nn") and not has(Forwarding(), "chol_rinv") and not has(object(), "spmm")
 
 
 def test_error_reporting_without_gpu_calls():
