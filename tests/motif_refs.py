@@ -1,6 +1,8 @@
 """TEST INFRASTRUCTURE: the brute-force restatement of the motif arithmetic, independent of
 muon_amd/_atac/motifs.py: log-odds, the threshold by the dynamic programme, the same tail by enumerating all 4^L
-words (matrices of up to 8 columns), and the scan as a numpy sliding window, j-ascending in f64."""
+words (matrices of up to 8 columns), and the scan as a numpy sliding window, j-ascending in f64: ``scan`` sequence by
+sequence with the hits appended one at a time (small fixtures), ``scan_stream`` over a whole code stream at once (the
+streams of tests/test_gpu_motif_edges.py, up to a few hundred thousand positions)."""
 import itertools
 import math
 
@@ -130,3 +132,57 @@ def scan(sequences, matrices, thresholds):
             for pos in np.nonzero(ok & (score >= thresholds[mi]))[0]:
                 rows.append((si, mi, int(pos), float(score[pos])))
     return rows, margin
+
+
+def stream_room(codes, offsets):
+    """int64 per stream position: the distance to the next code >= 4 or to the end of its sequence, whichever comes
+    first (0 at an invalid code), uncapped.  A plain loop over the runs of valid codes of every sequence."""
+    codes = np.asarray(codes)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    room = np.zeros(codes.size, dtype=np.int64)
+    for s in range(offsets.size - 1):
+        a, b = int(offsets[s]), int(offsets[s + 1])
+        stops = np.append(a + np.flatnonzero(codes[a:b] >= 4), b)  # where a run ends: an invalid code or the end
+        first = a
+        for stop in stops.tolist():
+            room[first:stop] = np.arange(stop - first, 0, -1)
+            first = stop + 1
+    return room
+
+
+def stream_scores(codes, room, M):
+    """(score f64 [total - L + 1], admissible bool) of one motif at every stream position that leaves it L codes: the
+    j-ascending sliding-window sum (an invalid code adds 0), admissible iff the room holds the motif"""
+    L = M.shape[1]
+    n = codes.size - L + 1
+    if n <= 0:
+        return np.zeros(0), np.zeros(0, dtype=bool)
+    M5 = np.vstack([np.asarray(M, dtype=np.float64), np.zeros((1, L))])
+    score = np.zeros(n)
+    for j in range(L):
+        score = score + M5[:, j].take(codes[j:j + n])
+    return score, room[:n] >= L
+
+
+def scan_stream(codes, offsets, matrices, thresholds):
+    """The scan of a whole code stream (0..3 = A C G T, anything else invalid; ``offsets`` int64 [n + 1]) at once:
+    for every motif the j-ascending f64 sliding-window sum over the stream, a window admissible iff the room at its
+    first position holds the motif.  Returns the hits as arrays ``(sequence int64, motif int64, position int64, score
+    f64)`` in the reference's loop order: sequence, motif, position."""
+    codes = np.minimum(np.asarray(codes), 4).astype(np.intp)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    room = stream_room(codes, offsets)
+    gpos, mot, sc = [], [], []
+    for mi, M in enumerate(matrices):
+        score, ok = stream_scores(codes, room, M)
+        hit = np.flatnonzero(ok & (score >= thresholds[mi]))
+        gpos.append(hit)
+        mot.append(np.full(hit.size, mi, dtype=np.int64))
+        sc.append(score[hit])
+    if not gpos:
+        e = np.zeros(0, dtype=np.int64)
+        return e, e.copy(), e.copy(), np.zeros(0)
+    gpos, mot, sc = np.concatenate(gpos), np.concatenate(mot), np.concatenate(sc)
+    seq = np.searchsorted(offsets, gpos, side="right") - 1  # (empty sequences own no position)
+    order = np.lexsort((gpos, mot, seq))
+    return seq[order], mot[order], (gpos - offsets[seq])[order], sc[order]

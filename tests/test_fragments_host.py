@@ -15,6 +15,7 @@ from muon_amd import atac as ac
 from muon_amd._atac import fragments as fr
 from muon_amd._atac.preproc import resident
 from tests import frag_fixture as fx
+from tests import frag_refs
 from tests.cpu_backend import CpuTestBackend
 
 BE = CpuTestBackend()
@@ -315,3 +316,95 @@ def test_candidate_ranges_hit_the_lane_and_chunk_edges(g):
     seg = torch.from_numpy(table.chrom_ptr)
     c = wchrom[:-1].long()
     assert bool((lo[:-1] >= seg[c]).all()) and bool((lo[:-1] + ln[:-1] <= seg[c + 1]).all())
+
+
+# -- tests/frag_refs.py (brute force) against the tensor forms, and the inputs of tests/test_gpu_fragments_stride.py ----
+def _ref_equals_tensor_forms(table, cell_of, n_obs, wchrom, wlo, whi, width):
+    """every pass of tests/frag_refs.py against the package's tensor form on one table and one set of windows"""
+    col = {k: getattr(table, k).numpy() for k in ("chrom", "start", "end", "barcode", "score")}
+    w = [t.numpy() for t in (wchrom, wlo, whi)]
+    cells = torch.from_numpy(cell_of)
+    n_feat = int(wlo.numel())
+    rlo, rln = fr.ranges_tensor(table, wchrom, wlo, whi)
+    ln = frag_refs.range_lengths(col["chrom"], col["start"], *w, table.max_len)
+    assert np.array_equal(rln.numpy(), ln)
+    for use_score in (True, False):
+        keys, vals = fr.overlap_tensor(table, cells, wlo, whi, rlo, rln, n_feat, use_score)
+        rkeys, rvals = frag_refs.overlap(col["chrom"], col["start"], col["end"], col["barcode"],
+                                         col["score"] if use_score else None, cell_of, n_obs, *w, n_feat)
+        assert keys.numel() > 0 and np.array_equal(keys.numpy(), rkeys) and np.array_equal(vals.numpy(), rvals)
+    if width is not None:
+        diff = fr.pileup_tensor(table, cells, n_obs, wlo, whi, rlo, rln, width)
+        rdiff = frag_refs.pileup_diff(col["chrom"], col["start"], col["end"], col["barcode"], col["score"], cell_of,
+                                      n_obs, *w, width)
+        assert np.array_equal(diff.numpy(), rdiff) and int(np.abs(rdiff).sum()) > 0 and int(rdiff.sum()) == 0
+        cd = (width - 1001) // 2
+        pile, rsums = frag_refs.pileup_scan(rdiff, 100, cd)
+        sums = fr.scan_tensor(diff, 100, cd)
+        assert np.array_equal(diff[:, :width].numpy(), pile) and np.array_equal(sums.numpy(), rsums)
+    for n_take in (len(table), len(table) // 3, 0):
+        cls = fr.length_classes_tensor(table, cells, n_obs, n_take, 147, 294)
+        assert np.array_equal(cls.numpy(), frag_refs.length_classes(col["start"], col["end"], col["barcode"], cell_of,
+                                                                     n_obs, n_take, 147, 294))
+    return ln
+
+
+def test_frag_refs_equal_the_tensor_forms_on_the_engineered_table(g):
+    a = fx.adata(g, BE)
+    table = a.uns["files"]["fragments"]
+    feats = fx.features(g, True)
+    cell_of = fr.cell_table(a, table)
+    genes = fr._windows(table, feats.Chromosome.values, feats.Start.values - 2000, feats.End.values)
+    ln = _ref_equals_tensor_forms(table, cell_of, a.n_obs, *genes, None)
+    assert {0, 1, 63, 64, 65, 255, 256, 257} <= set(ln.tolist())
+    s = feats.Start.values.astype(np.int64)
+    _ref_equals_tensor_forms(table, cell_of, a.n_obs, *fr._windows(table, feats.Chromosome.values, s - 1000, s + 1000), 2001)
+
+
+def test_stride_table_on_the_tensor_forms():
+    """the table and the windows of tests/test_gpu_fragments_stride.py: at the size of a 16-CU part through every
+    tensor form, and at the size of a 256-CU part the properties the GPU case asserts"""
+    df, obs = fx.stride_table()
+    table = fr.make_table(df.chrom.values, df.start.values, df.end.values, df.barcode.values, df.score.values, backend=BE)
+    cell_of = pd.Index(obs).get_indexer(table.barcodes).astype(np.int32)
+    assert table.contigs == ["a", "b"] and (cell_of == -1).sum() == 13 and len(obs) == 25
+    names, lo, hi = fx.stride_windows(2 * fx.wave_grid(16) + 1)
+    ln = _ref_equals_tensor_forms(table, cell_of, len(obs), *fr._windows(table, names, lo, hi), 1201)
+    assert int((-(-ln // fx.CHUNK)).sum()) >= 2 * fx.wave_grid(16) + 1
+    # a 256-CU part: 2 * 64 * 256 + 1 chunks from about 20 000 windows
+    names, lo, hi = fx.stride_windows(2 * fx.wave_grid(256) + 1)
+    wchrom, wlo, whi = (t.numpy() for t in fr._windows(table, names, lo, hi))
+    ln = frag_refs.range_lengths(table.chrom.numpy(), table.start.numpy(), wchrom, wlo, whi, table.max_len)
+    assert int((-(-ln // fx.CHUNK)).sum()) >= 2 * 64 * 256 + 1 and 18_000 < len(names) < 26_000
+    assert {0, 1, 255, 256, 257} <= set(ln.tolist()) and ln.max() >= 700
+    assert (wchrom == -1).any() and (wlo < 0).any()
+    empty = ln == 0
+    assert (empty[1:-1] & empty[2:] & ~empty[:-2]).any() and not empty[0]
+
+
+def test_scan_and_length_class_inputs_on_the_tensor_forms():
+    n = 0
+    for diff, flank, centre in fx.scan_cases():
+        W = diff.shape[1] - 1
+        pile, sums = frag_refs.pileup_scan(diff, flank, centre)
+        d = torch.from_numpy(diff.copy())
+        assert np.array_equal(fr.scan_tensor(d, flank, centre).numpy(), sums)
+        assert np.array_equal(d[:, :W].numpy(), pile) and np.array_equal(d[:, W].numpy(), diff[:, W])
+        assert np.abs(diff).max() <= 50 and diff.shape[0] == 5
+        n += 1
+    assert n == 4 * len(fx.SCAN_WIDTHS) - 3 and fx.SCAN_WIDTHS == (1, 63, 64, 65, 129, 2001)
+    # the raw columns: the tensor form takes neither an out-of-range barcode nor a cell past n_obs, so both are first
+    # mapped to "no cell" by hand; the restatement takes the columns as they are
+    assert fx.thread_grid(256) == 16 * 256 * 256
+    n = 2 * fx.thread_grid(4) + 123
+    start, end, barcode, cell_of, n_obs = fx.length_class_columns(n)
+    assert (barcode < 0).any() and (barcode >= cell_of.size).any() and (cell_of < 0).any() and (cell_of >= n_obs).any()
+    assert {146, 147, 293, 294} <= set((end.astype(np.int64) - start).tolist())
+    tame_cells = np.append(np.where(cell_of >= n_obs, -1, cell_of), -1).astype(np.int32)
+    tame = np.where((barcode < 0) | (barcode >= cell_of.size), cell_of.size, barcode).astype(np.int32)
+    table = type("Columns", (), {"start": torch.from_numpy(start), "end": torch.from_numpy(end),
+                                 "barcode": torch.from_numpy(tame), "__len__": lambda self: n})()
+    for n_take in (n, n // 3, fx.thread_grid(4) + 1):
+        want = frag_refs.length_classes(start, end, barcode, cell_of, n_obs, n_take, 147, 294)
+        got = fr.length_classes_tensor(table, torch.from_numpy(tame_cells), n_obs, n_take, 147, 294)
+        assert np.array_equal(got.numpy(), want) and (want.sum(axis=0) > 0).all()

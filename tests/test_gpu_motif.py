@@ -4,11 +4,16 @@ tests/motif_refs.py.
 
 Asked: the hit rows identical to the restatement's, in order; scores to atol 1e-12 (at most 33 additions of partial
 sums below 33 * 14: 33 * 462 * 2^-53 = 1.7e-12 worst case for the 33-column motif, 9e-13 for the 24 columns of the
-longest kernel motif - and both paths add in the restatement's order, so equality is what is expected); a second call
+longest kernel motif of THIS fixture - and both paths add in the restatement's order, so equality is what is expected); a second call
 byte-equal; the kernel path and the tensor formulation identical.  A window whose exact score lies within 1e-9 of its
 threshold could legitimately differ: the restatement's margin over every admissible window of the fixture is asserted
 to be larger, so no case is left out.  Measured on the CPU for the whole fixture (hand-built cases included): 20 hits
-at 1e-4 and 1 435 at 1e-2; smallest |score - threshold| 6.9e-4 and 4.8e-4."""
+at 1e-4 and 1 435 at 1e-2; smallest |score - threshold| 6.9e-4 and 4.8e-4.
+
+Not here but in tests/test_gpu_motif_edges.py, on exact (dyadic) banks and with ==: kernel motifs of 25 to 32 columns
+and of one column (the kernel takes up to ``motif_max_len()`` = 32), thresholds a score attains exactly, position tiles
+in which every window is a hit, and streams with more position tiles than the grid has workgroups (this fixture's 40
+position tiles never make a workgroup take a second one)."""
 import numpy as np
 import pytest
 import torch

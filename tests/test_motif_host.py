@@ -273,3 +273,79 @@ def test_entry_points():
     assert lib.mu_motif_count(8, 1, 1, *[None] * 8) == -1 and b"null pointer" in lib.mu_last_error()
     assert lib.mu_motif_write(8, 1, 1, *[None] * 10, -1, *[None] * 5) == -1 and b"negative hit count" in lib.mu_last_error()
     assert lib.mu_motif_write(8, 1, 1, *[None] * 10, 4, *[None] * 5) == -1 and b"null pointer" in lib.mu_last_error()
+
+
+# ---- the vectorised restatement and the cases of tests/test_gpu_motif_edges.py, without a GPU ---------------------
+@pytest.mark.parametrize("pvalue", F.PVALUES)
+def test_scan_stream_is_the_row_by_row_restatement(pvalue):
+    """motif_refs.scan_stream (one sliding window over the whole stream, admissibility from the room) against
+    motif_refs.scan (sequence by sequence) on the fixture: rows equal, scores bit for bit"""
+    ids, mats = F.bank()
+    seqs = list(F.sequences())
+    rows, _ = F.expected(pvalue)
+    codes = np.concatenate([motif_refs.encode(s) for s in seqs]).astype(np.uint8)
+    offsets = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    seq, mot, pos, score = motif_refs.scan_stream(codes, offsets, mats, F.thresholds(pvalue))
+    assert list(zip(seq.tolist(), mot.tolist(), pos.tolist())) == [r[:3] for r in rows] and len(rows) > 0
+    assert score.tobytes() == np.array([r[3] for r in rows], dtype=np.float64).tobytes()
+    room = motif_refs.stream_room(codes, offsets)
+    assert room.tolist() == Mo._room_tensor(torch.from_numpy(codes), torch.from_numpy(offsets)).tolist()
+
+
+def _tensor_scan_equals(case):
+    """the tensor formulation on the CPU operator set against the restatement, exactly"""
+    scanner = Mo.MotifScanner(BE, case.matrices, case.thresholds)
+    assert scanner.bank is None
+    got = [t.numpy() for t in Mo.scan_sequences_device((case.codes, case.offsets), scanner)]
+    for a, b in zip(got, case.want()):
+        assert np.array_equal(a, b)
+    return len(got[0])
+
+
+def test_dyadic_banks_are_exact():
+    for M in F.dyadic_bank([1, 7, 32], 0):
+        q = M * 64
+        assert np.array_equal(q, np.round(q)) and M.min() >= -8 and M.max() <= 2
+        assert all(np.sum(M[:, j] == M[:, j].max()) == 1 for j in range(M.shape[1]))
+    # 32 columns of multiples of 1/64 up to 8 in magnitude: every partial sum fits in 15 bits, whatever the order
+    assert 32 * 8 * 64 < 2 ** 53
+
+
+def test_edge_cases_on_the_tensor_formulation():
+    """every case of tests/test_gpu_motif_edges.py that needs no large stream: the properties each exists for, asserted
+    from the restatement, and the tensor formulation equal to the restatement"""
+    case = F.case_every_length()
+    assert sorted(case.lengths.tolist()) == list(range(1, F.CAP + 1))
+    assert np.diff(case.offsets).tolist() == F.EDGE_LENGTHS and int(np.sum(case.codes == 4)) == 7
+    F.assert_every_motif_hits_and_misses(case)
+    assert set(F.tile_of_motif(case.lengths).tolist()) == {0, 1}
+    assert _tensor_scan_equals(case) > 0
+    for L in (32, 25):
+        halo = F.case_halo(L)
+        F.assert_halo_plants(halo)
+        assert _tensor_scan_equals(halo) > 0
+    for L in (1, 16, 32):
+        at, above = F.case_equality(L)
+        F.assert_equality_pair(at, above)
+        assert _tensor_scan_equals(at) > _tensor_scan_equals(above)
+    for alternate in (False, True):
+        dense = F.case_density(alternate)
+        F.assert_density(dense, alternate)
+        assert _tensor_scan_equals(dense) == F.pair_counts(dense).sum()
+
+
+def test_stride_cases_cross_the_grid_of_a_256_cu_part():
+    case = F.case_scan_stride(256)
+    assert (case.grid_x, case.n_ptiles, case.total) == (683, 1407, 360115)
+    assert -(-case.total // F.TILE) >= 2 * F.scan_grid_x(256, 3) + 1 and len(case.matrices) == 33
+    assert sorted(set(case.lengths.tolist())) == list(range(4, 13)) and F.tile_of_motif(case.lengths).max() == 2
+    seq_len = np.diff(case.offsets)
+    assert (seq_len == 0).sum() > 100 and len(set(seq_len.tolist())) > 100
+    assert 0.001 < np.mean(case.codes == 4) < 0.003
+    F.assert_stride_mixture(case)
+    head = case.head(200)  # the tensor formulation on the first 200 sequences
+    assert head.total > 20 * F.TILE and _tensor_scan_equals(head) > 0
+    codes, offsets = F.room_stride_stream(256)
+    assert codes.size == 2 * 16 * 256 * 256 + 300
+    room = Mo._room_tensor(torch.from_numpy(codes), torch.from_numpy(offsets))
+    assert np.array_equal(room.numpy(), motif_refs.stream_room(codes, offsets))
