@@ -850,6 +850,25 @@ int mu_cluster_move_f64(int64_t nverts, const int32_t* d_verts, int64_t nv, int6
 int mu_cluster_segsum_f64(int64_t n, int64_t nseg, int w, const double* d_vals, const int64_t* d_ptr, double* d_out,
                           void* stream);
 
+/* ---- muon.tl.umap: the layout optimiser of the multimodal UMAP (/root/reference/muon/_core/tools.py:1209-1362; csrc/umap.hip,
+ * C-ABI v807; the optimiser is stated in muon_amd/_core/umap.py and DESIGN.md 9.12) -----------------------------------------
+ * All arithmetic f64, columns int32, offsets and periods int64.  No atomics: two calls agree bit for bit.  Arguments are
+ * checked before any HIP call.
+ *   mu_umap_epoch_f64: epoch `epoch` (1 .. n_epochs <= 2^20) as one Jacobi step, d_Y_out = d_Y_in + alpha_e F(d_Y_in), both
+ *     [n][n_components] row-major and two different buffers; n_components is 2 or 3 (mu_umap_max_components() = 3).  The
+ *     graph is the CSR (d_indptr [n + 1], d_cols [nnz]) with d_E [nnz] the entries' periods in units of 2^-16 epochs
+ *     (E >= 2^16; a smaller one is never active).  With t = epoch 2^16 and c = floor(t / E), entry j of row v is active iff
+ *     t mod E < 2^16; it then adds to F_v clip(-2ab d2^(b-1) / (1 + a d2^b) (y_v - y_u)) (u its column, d2 = |y_v - y_u|^2,
+ *     nothing when d2 == 0, clip to +-4 per coordinate), and for s = 0 .. floor(t rate / E) - floor(p 2^16 rate / E) - 1 with
+ *     p = ceil((c - 1) E / 2^16): clip(2 gamma b / ((0.001 + d2)(1 + a d2^b)) (y_v - y_k)), k = ((h >> 32) n) >> 32 of h =
+ *     splitmix64(splitmix64(splitmix64(seed + epoch) ^ j) + s), nothing when k == v or d2 == 0.  0 <= rate <= 1024.  d2^b is
+ *     one pow; a group of 16 lanes per vertex, lane g adds the entries g, g + 16, ... in order (an entry: its attraction,
+ *     then its negatives in order), then the xor butterfly over offsets 8, 4, 2, 1.  One launch, no synchronisation. */
+int mu_umap_max_components(void);
+int mu_umap_epoch_f64(int64_t n, int64_t nnz, const int64_t* d_indptr, const int32_t* d_cols, const int64_t* d_E,
+                      int n_components, int epoch, int n_epochs, int rate, double a, double b, double gamma,
+                      double alpha_e, uint64_t seed, const double* d_Y_in, double* d_Y_out, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -22,8 +22,10 @@ Drop-in namespaces for the three hot-path entry points of the reference
 
     muon_amd.tl.leiden / muon_amd.tl.louvain  <->  muon.tl.leiden / muon.tl.louvain  (multiplex clustering over the
                              modalities' graphs: a wave per vertex groups its neighbours' communities in an LDS table)
+    muon_amd.tl.umap         <->  muon.tl.umap        (the layout of the multimodal neighbourhood graph: a Jacobi epoch
+                             per launch, sixteen lanes per vertex, an integer schedule and counter-based negatives)
 
-Everything else of muon (I/O, plotting, UMAP, ...) is out of scope; see DESIGN.md.
+Everything else of muon (I/O, plotting, ...) is out of scope; see DESIGN.md.
 """
 from ._containers import AnnData, MuData  # duck-typed stand-ins when anndata/mudata are absent
 from . import atac  # noqa: F401

@@ -1830,6 +1830,37 @@ class HipBackend(OperatorSet):
             check(self.lib.mu_cluster_segsum_f64(n, nseg, w, _p(vals), _p(ptr), _p(out), self._stream()))
         return out
 
+    # -- muon.tl.umap (csrc/umap.hip) -----------------------------------------------------------------------------------
+    def umap_max_components(self) -> int:
+        """The most embedding dimensions ``umap_epoch`` has an instance for (2 and 3; others: the tensor formulation)."""
+        return int(self.lib.mu_umap_max_components())
+
+    def umap_epoch(self, indptr, cols, E, epoch: int, n_epochs: int, rate: int, a: float, b: float, gamma: float,
+                   alpha_e: float, seed: int, Y_in, Y_out):
+        """One epoch of the layout as a Jacobi step (include/muon_amd.h): ``Y_out = Y_in + alpha_e F(Y_in)`` over the CSR
+        (``indptr`` int64 [n + 1], ``cols`` int32, ``E`` int64 periods in 2^-16 epochs); ``seed`` is taken modulo 2^64."""
+        if Y_in.dim() != 2 or Y_in.shape != Y_out.shape:
+            raise ValueError("Y_in and Y_out: two [n, n_components] tensors of one shape")
+        n, dim = int(Y_in.shape[0]), int(Y_in.shape[1])
+        for name, t in (("Y_in", Y_in), ("Y_out", Y_out)):
+            if t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError(f"{name}: a contiguous float64 tensor")
+        if n and Y_in.data_ptr() == Y_out.data_ptr():
+            raise ValueError("Y_in and Y_out: two buffers")
+        if indptr.dtype != torch.int64 or not indptr.is_contiguous() or int(indptr.numel()) != n + 1:
+            raise TypeError("indptr: a contiguous int64 tensor of n + 1 offsets")
+        if cols.dtype != torch.int32 or not cols.is_contiguous():
+            raise TypeError("cols: a contiguous int32 tensor")
+        if E.dtype != torch.int64 or not E.is_contiguous():
+            raise TypeError("E: a contiguous int64 tensor")
+        if cols.numel() != E.numel():
+            raise ValueError("cols and E: one entry each per edge")
+        with self._dev_ctx():
+            check(self.lib.mu_umap_epoch_f64(n, int(cols.numel()), _p(indptr), _p(cols), _p(E), dim, int(epoch),
+                                             int(n_epochs), int(rate), float(a), float(b), float(gamma), float(alpha_e),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, _p(Y_in), _p(Y_out), self._stream()))
+        return Y_out
+
     # -- muon.atac.tl.scan_sequences (csrc/motif.hip) ----------------------------------------------------------------
     def motif_max_len(self) -> int:
         """The longest motif the kernel takes (longer ones: the tensor formulation)."""

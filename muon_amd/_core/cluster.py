@@ -103,7 +103,7 @@ def _segsum(be, vals: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     if has(be, "cluster_segsum"):
         return be.cluster_segsum(vals.contiguous(), ptr)
     if vals.device.type != "cpu":  # (a device's index_add_ adds with atomics: no fixed order, no bit-equal repeats)
-        raise RuntimeError("muon_amd.tl.leiden / louvain: a device backend must provide cluster_segsum")
+        raise RuntimeError("muon_amd.tl.leiden / louvain / umap: a device backend must provide cluster_segsum")
     nseg = int(ptr.numel()) - 1
     out = torch.zeros((nseg, int(vals.shape[1])), dtype=torch.float64, device=vals.device)
     ids = torch.repeat_interleave(torch.arange(nseg, device=vals.device), ptr[1:] - ptr[:-1])

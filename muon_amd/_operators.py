@@ -62,6 +62,8 @@ class OperatorSet:
     group_moments_max_groups = rank_row_cap = group_moments = rank_sums = None
     # muon.tl.leiden / muon.tl.louvain (cluster.hip): asked for together
     cluster_max_table = cluster_max_layers = cluster_move = cluster_segsum = None
+    # muon.tl.umap (umap.hip)
+    umap_max_components = umap_epoch = None
     # muon.atac.tl.scan_sequences (motif.hip): behind motif_scan
     motif_max_len = motif_tile = motif_group = motif_room = motif_scan = None
     # synthetic counts of the benchmark and the tests (synth.hip)
