@@ -333,6 +333,14 @@ int mu_tperm_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_
 int mu_tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
                   const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
                   const int32_t* d_tiles, const uint32_t* d_cont, const uint16_t* d_slots, void* d_ent, void* stream);
+/* mu_tperm_fill through the PHASE ACCOUNTING instance of its kernel (probes: scripts/probes/tperm_phases.py): the same
+ * bytes in d_ent, and d_phases[16 n_blocks][8] <- per (row block, wave) the shader cycles spent in the six phases of a
+ * tile, summed over the block's tiles - [0] top wait, [1] header scan, [2] staging, [3] retire + window issue,
+ * [4] barrier, [5] write-out - then [6] the block's tiles and [7] 0.  The stamps cost cycles of their own. */
+int mu_tperm_fill_phases(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
+                         const int64_t* d_x_row_dst, const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt,
+                         const int64_t* d_tile_off, const int32_t* d_tiles, const uint32_t* d_cont,
+                         const uint16_t* d_slots, void* d_ent, unsigned long long* d_phases, void* stream);
 int mu_csr_stream_len(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr, int64_t* d_len,
                       void* stream);
 int mu_csr_stream_fill(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr,

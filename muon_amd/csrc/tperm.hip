@@ -8,9 +8,11 @@
 //   * per (tile, wave) the (up to two) rows that need a CONTINUATION window;
 //   * per stored entry, in the order of X's row stream, its 16-bit STAGING SLOT inside its (row block, tile).
 // The per-step kernel `k_tperm_move` only moves data: windows of (column, value) pairs as in tpack4 (circular: pair p of
-// the stream lives in lane p % 32 of its row's half) plus the same entries' slots, `stage[slot] = (cell, value)`, ONE
-// barrier per tile (the staging buffer and the run tables are double buffered in the LDS the bitmap no longer needs), then
-// the coalesced write-out of the column runs.  Same bytes out as `k_t4_fill`: same tiles of work per (row block, column),
+// the stream lives in lane p % 32 of its row's half) plus the same entries' slots, `stage[slot] = (where, value)` with
+// where = cell | column << 16 inside the (row block, tile), ONE barrier per tile (the staging buffer and the run tables
+// are double buffered in the LDS the bitmap no longer needs), then the FLAT write-out: the staged pairs lie in (column, cell) order, lane i takes pair i of the tile and finds its run
+// through the column the staged word names - no loop over columns, every lane stores.  Same bytes out as `k_t4_fill`
+// (which keeps the write-out by column and is the independent reference): same tiles of work per (row block, column),
 // runs sorted by (column, cell).
 #include <type_traits>
 #include <utility>
@@ -293,16 +295,21 @@ __device__ __forceinline__ void tp_for(F&& f) {
 // (amdgpu_num_vgpr counts in the units this hipcc allocates in for a 1024-thread workgroup - TWO registers: 36 keeps the
 //  compiler below v72 = kH0, exactly as tpack4's 44 keeps it below v88.  Without it hipcc parks temporaries in the
 //  asm-owned registers between two asm statements; tests/test_tperm_isa.py audits the result.)
-__global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tperm_move(
+//
+// ACCT = true is the PHASE ACCOUNTING instance (`k_tperm_phases`, mu_tperm_fill_phases): the same tile loop with an
+// s_memtime stamp at every phase boundary, summed per wave in scalar registers and written to `acct` at the end.  Every
+// stamp sits behind `if constexpr (ACCT)`: the production kernel holds none of it.
+constexpr int kPhases = 6;  // top wait, header scan, staging, retire + window issue, barrier, write-out
+template <bool ACCT>
+__device__ __forceinline__ void tperm_move_body(
     int64_t n_rows, int64_t n_cols, int rw, int G, const int64_t* __restrict__ indptr,
     const int64_t* __restrict__ row_dst, const unsigned long long* __restrict__ xent,
     const int64_t* __restrict__ cdst, const uint32_t* __restrict__ base, const int64_t* __restrict__ toff,
     const int32_t* __restrict__ tiles, const uint32_t* __restrict__ cont, const uint16_t* __restrict__ slots,
-    unsigned long long* __restrict__ out) {
+    unsigned long long* __restrict__ out, unsigned long long* __restrict__ acct) {
   __shared__ unsigned long long stage[2][kCap];  // 144 KiB
-  __shared__ uint32_t lrun[2][kMaxC];            // per column of a tile: pairs << 16 | first staging slot
-  __shared__ int64_t gdst[2][kMaxC];             // ... and where its run goes
-  __shared__ uint32_t wsum[2][kNW];
+  __shared__ int64_t dcol[2][kMaxC];             // per column of a tile: where its run goes - its first staging slot
+  __shared__ __attribute__((aligned(16))) uint32_t wsum[2][kNW];
   int g = blockIdx.x;
   if (G > 0) {  // XCD-aware order (see k_t4_fill)
     const int per = (G + 7) / 8;
@@ -394,45 +401,56 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
     }
     if (lane == 63) wsum[set][wave] = incl;
   };
-  auto finish_header = [&](int W, int set) {  // (behind a barrier: every wave's sum is there)
-    uint32_t wpre = 0;
+  // (behind a barrier: every wave's sum is there)  The staging buffer holds a tile's pairs in (column, cell) order, a
+  // column's first slot is the prefix of the counts: pair i of the tile goes to out[dcol[column] + i].  Returns the
+  // tile's pairs.
+  auto finish_header = [&](int W, int set) {
+    const uint4* ws4 = reinterpret_cast<const uint4*>(wsum[set]);
+    uint32_t wpre = 0, total = 0;
 #pragma unroll
-    for (int w = 0; w < kNW; ++w) {
-      const uint32_t u = wsum[set][w];
-      if (w < wave) wpre += u;
+    for (int q = 0; q < kNW / 4; ++q) {
+      const uint4 u4 = ws4[q];
+      const uint32_t u[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        total += u[k];
+        wpre += u[k] & (uint32_t)-(int)(4 * q + k < wave);  // (a mask, not a branch per wave)
+      }
     }
-    if (tid < W) {
-      lrun[set][tid] = (mine << 16) | (wpre + incl - mine);
-      gdst[set][tid] = gd;
-    }
+    if (tid < W) dcol[set][tid] = gd - (int64_t)(wpre + incl - mine);
+    return uniform32((int)total);
   };
-  // write-out: one 16-lane group per column, consecutive lanes = consecutive pairs of the run, four columns at a time
-  auto write_out = [&](int set, int ncol) {
+  // write-out, FLAT: one staged pair per lane whatever column it belongs to, every lane busy up to the tile's last
+  // pair; the staged low word names the pair's column and cell inside the tile (see the staging below)
+  auto write_out = [&](int set, int total) {
     const unsigned long long* stg = stage[set];
-    const int grp = tid >> 4, s16 = tid & 15;
-    for (int c0 = grp; c0 < ncol; c0 += 4 * (kT / 16)) {
-      uint32_t lr[4];
-      int64_t gq[4];
-      unsigned long long e[4];
+    const int64_t* dc = dcol[set];
+    // N whole rounds of the workgroup from pair i on: the reads of all N, then their stores
+    auto rounds = [&](auto nc, int i) {
+      constexpr int N = decltype(nc)::value;
+      unsigned long long e[N];
+      int64_t q[N];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int cl = c0 + u * (kT / 16);
-        const bool in = cl < ncol;
-        lr[u] = in ? lrun[set][in ? cl : 0] : 0u;
-        gq[u] = gdst[set][in ? cl : 0];
-      }
+      for (int u = 0; u < N; ++u) e[u] = stg[i + u * kT];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t L = lr[u] >> 16, src = lr[u] & 0xffffu;
-        e[u] = stg[(uint32_t)s16 < L ? src + s16 : 0];
-      }
+      for (int u = 0; u < N; ++u) q[u] = dc[((unsigned)e[u] >> 16) & (unsigned)(kMaxC - 1)];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t L = lr[u] >> 16, src = lr[u] & 0xffffu;
-        if ((uint32_t)s16 < L) out[gq[u] + s16] = e[u];
-        for (uint32_t i = 16 + s16; i < L; i += 16) out[gq[u] + i] = stg[src + i];
-      }
+      for (int u = 0; u < N; ++u)
+        out[q[u] + (i + u * kT)] =
+            (e[u] & 0xffffffff00000000ull) | (unsigned long long)((unsigned)r0 + ((unsigned)e[u] & 0xffffu));
+    };
+    const int whole = total / kT;  // (uniform: the rounds in which every thread has a pair)
+    int r = 0;
+    for (; r + 4 <= whole; r += 4) rounds(std::integral_constant<int, 4>{}, tid + r * kT);
+    if ((whole - r) & 2) {
+      rounds(std::integral_constant<int, 2>{}, tid + r * kT);
+      r += 2;
     }
+    if ((whole - r) & 1) {
+      rounds(std::integral_constant<int, 1>{}, tid + r * kT);
+      r += 1;
+    }
+    if (tid + r * kT < total) rounds(std::integral_constant<int, 1>{}, tid + r * kT);
   };
 
   auto tile_at = [&](int t) { return uniform32(tiles[tb + (t < nt ? t : nt)]); };
@@ -444,7 +462,19 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
   issue_all(pw);
   issue_header(c1);
   __syncthreads();
-  finish_header(c1 - c0, 0);
+  int tot = finish_header(c1 - c0, 0);  // pairs of tile t
+
+  // (ACCT) cycles of this wave per phase: a stamp closes the phase named by its index
+  unsigned long long ph[kPhases] = {}, t_prev = 0;
+  if constexpr (ACCT) t_prev = __builtin_amdgcn_s_memtime();
+  auto stamp = [&](auto kc) {
+    if constexpr (ACCT) {
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      ph[decltype(kc)::value] += now - t_prev;
+      t_prev = now;
+    }
+  };
+  using std::integral_constant;
 
   for (int t = 0; t < nt; ++t) {
     const int set = t & 1;
@@ -453,9 +483,15 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
     asm volatile("" : "+v"(hf));  // (per-slot constants made from `half` are recomputed, not kept in registers)
     const int pw_next = cont_of(t + 1);
     tp_wait_all();
+    stamp(integral_constant<int, 0>{});
     take_header(c2 - c1, set ^ 1);
-    // every entry of the tile to its slot, straight from the window registers
+    stamp(integral_constant<int, 1>{});
+    // every entry of the tile to its slot, straight from the window registers.  The staged low word is
+    // cell_local | col_local << 16: the row inside the block (wave * rw + row of the wave, <= 511) and the column
+    // inside the tile (c - c0, <= 511) - what the flat write-out needs to find the pair's run and to rebuild its cell.
+    // (c << 16 wraps; the difference to c0 << 16 does not)
     unsigned long long* stg = stage[set];
+    const unsigned wbase = (unsigned)(wave * rw) - ((unsigned)c0 << 16);
     int cntv = 0;  // lane r < 32: pairs of row r consumed by this tile
     tp_for<16>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
@@ -463,7 +499,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
       const unsigned v = tp_reg<kW0 + 2 * J + 1>(), s = tp_reg<kS0 + J>();
       const bool valid = c < cend;  // sorted rows: a run of each half; padding lanes hold INT_MAX
       const unsigned long long m = __ballot(valid);
-      if (valid) stg[s] = (unsigned long long)(unsigned)(wr0 + 2 * J + hf) | ((unsigned long long)v << 32);
+      if (valid) stg[s] = (unsigned long long)(((unsigned)c << 16) + (wbase + 2 * J + hf)) | ((unsigned long long)v << 32);
       cntv = tp_writelane_c<2 * J>(cntv, __popc((unsigned)m));
       cntv = tp_writelane_c<2 * J + 1>(cntv, __popc((unsigned)(m >> 32)));
     });
@@ -474,10 +510,11 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
       const unsigned v = tp_reg<kW0 + 2 * kSlotP + 1>(), s = tp_reg<kS0 + kSlotP>();
       const bool valid = c < cend;
       const unsigned long long m = __ballot(valid);
-      if (valid) stg[s] = (unsigned long long)(unsigned)(wr0 + (hf ? lb : pa)) | ((unsigned long long)v << 32);
+      if (valid) stg[s] = (unsigned long long)(((unsigned)c << 16) + (wbase + (hf ? lb : pa))) | ((unsigned long long)v << 32);
       cntv = tp_writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pa) + __popc((unsigned)m), pa);
       if (pb != kNone) cntv = tp_writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pb) + __popc((unsigned)(m >> 32)), pb);
     }
+    stamp(integral_constant<int, 2>{});
     // the cursors move on, the consumed lanes are free, the next windows are requested
     {
       int padv = 0x7fffffff;
@@ -493,14 +530,45 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tpe
     issue_all(pw);
     issue_header(c2);
     const int c3 = tile_at(t + 3);
+    stamp(integral_constant<int, 3>{});
     __syncthreads();
-    finish_header(c2 - c1, set ^ 1);
-    write_out(set, c1 - c0);
+    stamp(integral_constant<int, 4>{});
+    const int tot_next = finish_header(c2 - c1, set ^ 1);
+    write_out(set, tot);
+    tot = tot_next;
+    stamp(integral_constant<int, 5>{});
     c0 = c1;
     c1 = c2;
     c2 = c3;
   }
   tp_wait_all();  // (windows and a header requested for a tile that does not exist)
+  if constexpr (ACCT) {
+    // row (block, wave) of acct: the six phase sums, the block's tiles, 0
+    if (lane == 0) {
+      unsigned long long* row = acct + ((int64_t)g * kNW + wave) * (kPhases + 2);
+#pragma unroll
+      for (int k = 0; k < kPhases; ++k) row[k] = ph[k];
+      row[kPhases] = (unsigned long long)nt;
+      row[kPhases + 1] = 0ull;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tperm_move(
+    int64_t n_rows, int64_t n_cols, int rw, int G, const int64_t* __restrict__ indptr,
+    const int64_t* __restrict__ row_dst, const unsigned long long* __restrict__ xent,
+    const int64_t* __restrict__ cdst, const uint32_t* __restrict__ base, const int64_t* __restrict__ toff,
+    const int32_t* __restrict__ tiles, const uint32_t* __restrict__ cont, const uint16_t* __restrict__ slots,
+    unsigned long long* __restrict__ out) {
+  tperm_move_body<false>(n_rows, n_cols, rw, G, indptr, row_dst, xent, cdst, base, toff, tiles, cont, slots, out, nullptr);
+}
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(36))) void k_tperm_phases(
+    int64_t n_rows, int64_t n_cols, int rw, int G, const int64_t* __restrict__ indptr,
+    const int64_t* __restrict__ row_dst, const unsigned long long* __restrict__ xent,
+    const int64_t* __restrict__ cdst, const uint32_t* __restrict__ base, const int64_t* __restrict__ toff,
+    const int32_t* __restrict__ tiles, const uint32_t* __restrict__ cont, const uint16_t* __restrict__ slots,
+    unsigned long long* __restrict__ out, unsigned long long* __restrict__ acct) {
+  tperm_move_body<true>(n_rows, n_cols, rw, G, indptr, row_dst, xent, cdst, base, toff, tiles, cont, slots, out, acct);
 }
 
 }  // namespace
@@ -532,9 +600,11 @@ int mu_tperm_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_
   return MU_OK;
 }
 
-int mu_tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
-                  const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
-                  const int32_t* d_tiles, const uint32_t* d_cont, const uint16_t* d_slots, void* d_ent, void* stream) {
+// d_phases = nullptr: the production kernel; given: the accounting instance
+static int tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
+                      const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
+                      const int32_t* d_tiles, const uint32_t* d_cont, const uint16_t* d_slots, void* d_ent,
+                      unsigned long long* d_phases, void* stream) {
   MU_REQUIRE(mu_tpack4_supported(n_rows, n_cols, nnz), "shape out of range (mu_tpack4_supported)");
   MU_REQUIRE(d_indptr && d_x_row_dst && d_x_ent && d_cdst && d_cnt && d_tile_off && d_tiles && d_cont && d_slots && d_ent,
              "null pointer");
@@ -545,11 +615,32 @@ int mu_tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_
   const int rw = (int)(rpb / kNW);
   const bool xcd = mu_tune_get("tpack4_plain") != 1;
   const unsigned grid = xcd ? (unsigned)(8 * ((G + 7) / 8)) : (unsigned)G;
-  hipLaunchKernelGGL(k_tperm_move, dim3(grid), dim3(kT), 0, (hipStream_t)stream, n_rows, n_cols, rw, xcd ? G : -G,
-                     d_indptr, d_x_row_dst, (const unsigned long long*)d_x_ent, d_cdst, (const uint32_t*)d_cnt, d_tile_off,
-                     d_tiles, d_cont, d_slots, (unsigned long long*)d_ent);
+  if (d_phases)
+    hipLaunchKernelGGL(k_tperm_phases, dim3(grid), dim3(kT), 0, (hipStream_t)stream, n_rows, n_cols, rw, xcd ? G : -G,
+                       d_indptr, d_x_row_dst, (const unsigned long long*)d_x_ent, d_cdst, (const uint32_t*)d_cnt,
+                       d_tile_off, d_tiles, d_cont, d_slots, (unsigned long long*)d_ent, d_phases);
+  else
+    hipLaunchKernelGGL(k_tperm_move, dim3(grid), dim3(kT), 0, (hipStream_t)stream, n_rows, n_cols, rw, xcd ? G : -G,
+                       d_indptr, d_x_row_dst, (const unsigned long long*)d_x_ent, d_cdst, (const uint32_t*)d_cnt,
+                       d_tile_off, d_tiles, d_cont, d_slots, (unsigned long long*)d_ent);
   MU_CHECK_LAUNCH();
   return MU_OK;
+}
+
+int mu_tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
+                  const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
+                  const int32_t* d_tiles, const uint32_t* d_cont, const uint16_t* d_slots, void* d_ent, void* stream) {
+  return tperm_fill(n_rows, n_cols, nnz, d_indptr, d_x_row_dst, d_x_ent, d_cdst, d_cnt, d_tile_off, d_tiles, d_cont,
+                    d_slots, d_ent, nullptr, stream);
+}
+
+int mu_tperm_fill_phases(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
+                         const int64_t* d_x_row_dst, const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt,
+                         const int64_t* d_tile_off, const int32_t* d_tiles, const uint32_t* d_cont,
+                         const uint16_t* d_slots, void* d_ent, unsigned long long* d_phases, void* stream) {
+  MU_REQUIRE(d_phases, "null pointer");
+  return tperm_fill(n_rows, n_cols, nnz, d_indptr, d_x_row_dst, d_x_ent, d_cdst, d_cnt, d_tile_off, d_tiles, d_cont,
+                    d_slots, d_ent, d_phases, stream);
 }
 
 }  // extern "C"
