@@ -59,6 +59,13 @@ def _compiler_id():
         return ""
 
 
+def device_asm(source_name, out_path):
+    """Write the gfx950 assembly of one of SOURCES, compiled with the flags the library is built with."""
+    subprocess.check_call([_hipcc()] + FLAGS + EXTRA.get(source_name, []) +
+                          ["-S", "--cuda-device-only", "-w", os.path.join(HERE, source_name), "-o", str(out_path)])
+    return out_path
+
+
 def build(force=False, verbose=True):
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     hdrs = [h if os.path.isabs(h) else os.path.join(HERE, h) for h in HEADERS]

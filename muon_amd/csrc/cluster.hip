@@ -35,12 +35,6 @@ struct ClusterCoef {
   double c[kClusterMaxLayers];
 };
 
-// what one lane wrote to the wave's table is what another lane reads afterwards (the wave's LDS accesses issue in order)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 template <int L>
 __global__ __launch_bounds__(256) void k_cluster_move(int64_t nverts, const int32_t* __restrict__ verts, int nv, int64_t nnz,
                                                       const int64_t* __restrict__ indptr, const int32_t* __restrict__ cols,

@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+#include <utility>
+
 #include "muon_amd.h"
 
 void mu_set_error(const char* fmt, ...);
@@ -31,6 +35,19 @@ constexpr int kWave = 64;
 // number of CUs of the current device (cached per device id)
 int mu_num_cus();
 
+// grid of a kernel that gives every item (a row, a chunk) one wave: `waves_per_block` items per block, capped at
+// `blocks_per_cu` blocks per CU - the kernel walks the rest grid-stride - and never empty
+static inline unsigned wave_grid(int64_t items, int waves_per_block, int blocks_per_cu) {
+  int64_t blocks = (items + waves_per_block - 1) / waves_per_block;
+  const int64_t cap = (int64_t)mu_num_cus() * blocks_per_cu;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+// carving a work buffer: every piece starts on a 256-byte boundary
+static inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 // tell the compiler a value is wave-uniform (it cannot see that threadIdx.x >> 6 is)
@@ -54,6 +71,126 @@ __device__ __forceinline__ T wave_sum_all(T v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;  // valid in every lane
 }
+
+// LDS written by one lane and read by another of the SAME wave: the wave's LDS accesses issue in order, so no
+// workgroup barrier is needed - but the compiler has to be told.  The fence scope is exactly "wavefront": it emits no
+// instruction and only keeps the compiler from moving LDS accesses across it; a wider scope adds waits for the
+// memory operations in flight, and without the fence the barrier alone orders nothing.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a template argument of
+// what the body calls (a register number in an asm statement, a counted wait)
+template <int... I, class F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
+}
+
+// lane `l` of a 64-bit value, as two 32-bit readlanes (l wave-uniform)
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// lane `L` of v <- the wave-uniform x (this clang has no writelane builtin)
+template <int L>
+__device__ __forceinline__ int writelane_c(int v, int x) {
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(x), "n"(L));
+  return v;
+}
+// the same with a wave-uniform lane number.  The lane select goes through M0 (one SGPR operand per instruction) and M0
+// is CLOBBERED: nothing that keeps a value in M0 (dma_piece's LDS address, an LDS-direct load) may span a call.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // ("clobber list contains reserved registers: m0": meant)
+__device__ __forceinline__ int writelane_s(int v, int x, int l) {
+  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");
+  return v;
+}
+#pragma clang diagnostic pop
+
+// One LDS-DMA piece: 64 lanes x 16 B land contiguously at the wave-uniform LDS byte address `lds_dst`; the source is
+// base (scalar) + a 32-bit byte offset per lane (64-bit per-lane addresses cost four registers and a 64-bit clamp per
+// piece; callers keep the operand under 4 GiB and check it on the host).  The destination travels in M0, which the
+// compiler also uses: it is saved and restored inside the one asm statement (early-clobber `keep`), and the s_nop
+// covers the hazard between the write of M0 and the load that reads it.
+__device__ __forceinline__ void dma_piece(const void* base, unsigned byte_off, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(byte_off), "s"(base), "s"(lds_dst)
+      : "memory");
+}
+
+// The (column, value) pair at ib + off / vb + off (byte offset), issued from asm and NOT waited for: the caller's
+// counted wait (pipe_wait, sf_wait: each file's own, it names the registers of its own pipeline) takes c and v as
+// read-write operands, so every use is ordered behind it.  Early-clobber outputs: the second load still reads `off`
+// after the first has been given its destination.
+__device__ __forceinline__ void load_pair(const int32_t* ib, const float* vb, unsigned off, int32_t& c, float& v) {
+  asm volatile("global_load_dword %0, %2, %3\n\tglobal_load_dword %1, %2, %4"
+               : "=&v"(c), "=&v"(v)
+               : "v"(off), "s"(ib), "s"(vb)
+               : "memory");
+}
+
+// The pieces of a wave's strip of rows walked as ONE flat sequence of iterations: row l's piece is [lo_l, hi_l) of
+// lane l, `step` entries at a time, then the next row's.  Start with {-1, 0, 0, rows, step}.
+struct FlatWalk {
+  int l, pb, hi, nrow, step;
+  // the next iteration: false when the strip is through (wave-uniform: every member lives in scalar registers)
+  __device__ __forceinline__ bool advance(int lo_l, int hi_l) {
+    pb += step;
+    while (pb >= hi) {
+      if (++l >= nrow) return false;
+      pb = __builtin_amdgcn_readlane(lo_l, l);
+      hi = __builtin_amdgcn_readlane(hi_l, l);
+    }
+    return true;
+  }
+};
+
+// v_mfma_{f32,f64}_16x16x4: A operand lane l = A[i = l & 15][k = l >> 4], B operand lane l = B[k = l >> 4][j = l & 15],
+// C/D register r of lane l = C[row(l >> 4, r)][col = l & 15] - the one place where the two instructions differ.
+template <typename T> struct Mfma16x16x4;
+template <> struct Mfma16x16x4<float> {
+  typedef float acc_t __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
+};
+template <> struct Mfma16x16x4<double> {
+  typedef double acc_t __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }
+};
+
+// transcendentals in the storage type: the hardware's exp / log for an f32 model, libm's for f64 (and for log1p)
+__device__ __forceinline__ float mu_exp(float x) { return __expf(x); }
+__device__ __forceinline__ double mu_exp(double x) { return exp(x); }
+__device__ __forceinline__ float mu_log(float x) { return __logf(x); }
+__device__ __forceinline__ double mu_log(double x) { return log(x); }
+__device__ __forceinline__ float mu_log1p(float x) { return log1pf(x); }
+__device__ __forceinline__ double mu_log1p(double x) { return log1p(x); }
 
 // first index i in [lo, hi) with a[i] >= key (a ascending)
 __device__ __forceinline__ int64_t lower_bound_i64(const int64_t* a, int64_t lo, int64_t hi,

@@ -336,11 +336,6 @@ constexpr int kCholNb = 16;  // block size of the blocked factorisation
 // 118 us.  What is left is the serial chain of wave 0 - 64 pivots, each a sqrt, a divide and three LDS round
 // trips.  L^-1: diagonal blocks from the factorisation, the blocks below
 // them block column by block column, one wave per block column, no barriers in between.
-__device__ __forceinline__ void chol_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(kCholT) void k_chol_rinv(int B, int w, const double* __restrict__ G,
                                                       float* __restrict__ M, int* __restrict__ flag) {
   constexpr int NB = kCholNb;
@@ -375,18 +370,18 @@ __global__ __launch_bounds__(kCholT) void k_chol_rinv(int B, int w, const double
         if (bad) piv = tiny;
         if (bad && lane == 0) s_bad = 1;
         const double r = sqrt(piv);
-        chol_wave_sync();  // (every lane has read the pivot before lane s overwrites it)
+        wave_lds_sync();  // (every lane has read the pivot before lane s overwrites it)
         if (lane < NB) {
           const int i = k0 + lane;
           if (lane == s) A[k][k] = r;
           else if (lane > s) A[i][k] = A[i][k] / r;
         }
-        chol_wave_sync();
+        wave_lds_sync();
         for (int e = lane; e < NB * NB; e += 64) {
           const int i = k0 + e / NB, j = k0 + e % NB;
           if (j > k && j <= i) A[i][j] -= A[i][k] * A[j][k];
         }
-        chol_wave_sync();
+        wave_lds_sync();
       }
       // its inverse, column by column: lane c solves D x = e_c by forward substitution
       if (lane < NB) {
@@ -441,14 +436,14 @@ __global__ __launch_bounds__(kCholT) void k_chol_rinv(int B, int w, const double
           for (int j = 0; j < NB; ++j) v += A[ib * NB + r][jb * NB + j] * X[jb * NB + j][kb * NB + c];
         Tm[wave][r][c] = v;
       }
-      chol_wave_sync();
+      wave_lds_sync();
       for (int e = lane; e < NB * NB; e += 64) {
         const int r = e / NB, c = e % NB;
         double v = 0.0;
         for (int j = 0; j <= r; ++j) v += X[ib * NB + r][ib * NB + j] * Tm[wave][j][c];
         X[ib * NB + r][kb * NB + c] = -v;
       }
-      chol_wave_sync();
+      wave_lds_sync();
     }
   }
   __syncthreads();

@@ -207,17 +207,6 @@ __global__ __launch_bounds__(256) void k_submatrix_fill(int64_t n_rows, int64_t 
   }
 }
 
-// one wave per row, 4 waves per block, capped at 16 blocks per CU (grid-stride beyond)
-static inline unsigned sub_grid(int64_t n_keep) {
-  int64_t blocks = (n_keep + 3) / 4;
-  const int64_t cap = (int64_t)mu_num_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" {
 
 size_t mu_csr_qc_worksize(int64_t n_rows, int64_t n_cols) {
@@ -283,7 +272,7 @@ int mu_csr_submatrix_count(int64_t n_rows, int64_t n_cols, int64_t n_keep, const
   if (n_keep == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_rows && d_new_row_nnz, "null pointer");
   MU_REQUIRE(n_cols == 0 || d_col_table, "null pointer");
-  hipLaunchKernelGGL(k_submatrix_count, dim3(sub_grid(n_keep)), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols,
+  hipLaunchKernelGGL(k_submatrix_count, dim3(wave_grid(n_keep, 4, 16)), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols,
                      n_keep, d_indptr, d_indices, d_rows, d_col_table, d_new_row_nnz);
   MU_CHECK_LAUNCH();
   return MU_OK;
@@ -300,7 +289,7 @@ int mu_csr_submatrix_fill(int dtype, int64_t n_rows, int64_t n_cols, int64_t n_k
   if (n_keep == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_rows && d_new_indptr, "null pointer");
   MU_REQUIRE(n_cols == 0 || d_col_table, "null pointer");
-  const unsigned grid = sub_grid(n_keep);
+  const unsigned grid = wave_grid(n_keep, 4, 16);
   if (dtype == MU_DTYPE_F32)
     hipLaunchKernelGGL(k_submatrix_fill<uint32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols,
                        n_keep, d_indptr, d_indices, (const uint32_t*)d_values, d_rows, d_col_table, d_new_indptr,

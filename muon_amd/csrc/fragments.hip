@@ -224,15 +224,6 @@ __global__ __launch_bounds__(256) void k_frag_length_classes(int64_t n_take, con
   }
 }
 
-// a wave per work item, 4 waves per block, capped at 16 blocks per CU (grid-stride beyond)
-static inline unsigned frag_wave_grid(int64_t n_items) {
-  int64_t blocks = (n_items + 3) / 4;
-  const int64_t cap = (int64_t)mu_num_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
 extern "C" {
 
 int mu_frag_chunk(void) { return kFragChunk; }
@@ -257,7 +248,7 @@ int mu_frag_overlap_count(int64_t n_win, int64_t n_chunks, const int64_t* d_chun
   if (n_chunks == 0) return MU_OK;
   MU_REQUIRE(d_chunk_ptr && d_rng_lo && d_rng_len && d_wlo && d_whi && d_start && d_end && d_barcode && d_cell_of &&
                  d_chunk_cnt, "null pointer");
-  hipLaunchKernelGGL(k_frag_overlap_count, dim3(frag_wave_grid(n_chunks)), dim3(256), 0, (hipStream_t)stream, n_win,
+  hipLaunchKernelGGL(k_frag_overlap_count, dim3(wave_grid(n_chunks, 4, 16)), dim3(256), 0, (hipStream_t)stream, n_win,
                      n_chunks, d_chunk_ptr, d_rng_lo, d_rng_len, d_wlo, d_whi, d_start, d_end, d_barcode, d_cell_of,
                      n_barcodes, n_obs, d_chunk_cnt);
   MU_CHECK_LAUNCH();
@@ -274,7 +265,7 @@ int mu_frag_overlap_emit(int64_t n_win, int64_t n_chunks, const int64_t* d_chunk
   if (n_chunks == 0) return MU_OK;
   MU_REQUIRE(d_chunk_ptr && d_rng_lo && d_rng_len && d_wlo && d_whi && d_start && d_end && d_barcode && d_cell_of &&
                  d_chunk_off, "null pointer");
-  hipLaunchKernelGGL(k_frag_overlap_emit, dim3(frag_wave_grid(n_chunks)), dim3(256), 0, (hipStream_t)stream, n_win,
+  hipLaunchKernelGGL(k_frag_overlap_emit, dim3(wave_grid(n_chunks, 4, 16)), dim3(256), 0, (hipStream_t)stream, n_win,
                      n_chunks, d_chunk_ptr, d_rng_lo, d_rng_len, d_wlo, d_whi, d_start, d_end, d_barcode, d_score,
                      d_cell_of, n_barcodes, n_obs, n_features, d_chunk_off, d_keys, d_vals);
   MU_CHECK_LAUNCH();
@@ -290,7 +281,7 @@ int mu_frag_pileup(int64_t n_win, int64_t n_chunks, const int64_t* d_chunk_ptr, 
   if (n_chunks == 0 || n_obs == 0) return MU_OK;
   MU_REQUIRE(d_chunk_ptr && d_rng_lo && d_rng_len && d_wlo && d_whi && d_start && d_end && d_barcode && d_cell_of &&
                  d_diff, "null pointer");
-  hipLaunchKernelGGL(k_frag_pileup, dim3(frag_wave_grid(n_chunks)), dim3(256), 0, (hipStream_t)stream, n_win, n_chunks,
+  hipLaunchKernelGGL(k_frag_pileup, dim3(wave_grid(n_chunks, 4, 16)), dim3(256), 0, (hipStream_t)stream, n_win, n_chunks,
                      d_chunk_ptr, d_rng_lo, d_rng_len, d_wlo, d_whi, d_start, d_end, d_barcode, d_score, d_cell_of,
                      n_barcodes, n_obs, (int)width, d_diff);
   MU_CHECK_LAUNCH();
@@ -305,7 +296,7 @@ int mu_frag_pileup_scan(int64_t n_obs, int64_t width, int64_t flank_size, int64_
   MU_REQUIRE(center_dist >= 0 && 2 * center_dist <= width, "centre is empty");
   if (n_obs == 0) return MU_OK;
   MU_REQUIRE(d_diff && d_sums, "null pointer");
-  hipLaunchKernelGGL(k_frag_pileup_scan, dim3(frag_wave_grid(n_obs)), dim3(256), 0, (hipStream_t)stream, n_obs,
+  hipLaunchKernelGGL(k_frag_pileup_scan, dim3(wave_grid(n_obs, 4, 16)), dim3(256), 0, (hipStream_t)stream, n_obs,
                      (int)width, (int)flank_size, (int)(width - flank_size), (int)center_dist,
                      (int)(width - center_dist), d_diff, d_sums);
   MU_CHECK_LAUNCH();

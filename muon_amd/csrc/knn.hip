@@ -129,11 +129,6 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_filter(
 constexpr int kMergeWaves = 4;
 constexpr int kMergeMax = 1024;  // kc + cap must fit
 
-__device__ __forceinline__ void merge_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(64 * kMergeWaves) void k_knn_merge(int64_t n_q, int kc, int cap,
                                                                 const double* __restrict__ cur_d,
                                                                 const int64_t* __restrict__ cur_p,
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(64 * kMergeWaves) void k_knn_merge(int64_t n_q, int
     K[t] = d;
     V[t] = v;
   }
-  merge_sync();
+  wave_lds_sync();
   for (int k = 2; k <= P; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int t = lane; t < P; t += 64) {
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(64 * kMergeWaves) void k_knn_merge(int64_t n_q, int
           }
         }
       }
-      merge_sync();
+      wave_lds_sync();
     }
   }
   for (int t = lane; t < kc; t += 64) {

@@ -31,12 +31,7 @@
 namespace {
 
 template <typename T> struct BjMap;
-template <> struct BjMap<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
-  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
+template <> struct BjMap<float> : Mfma16x16x4<float> {
   // 2 lambda(xi) from xi^2: hardware sqrt / exp2 / rcp (1 ulp each); the series where 1 - e^-xi would cancel
   static __device__ __forceinline__ float omega(float x2) {
     x2 = fmaxf(x2, 0.f);
@@ -47,12 +42,7 @@ template <> struct BjMap<float> {
     return x2 < 0.04f ? small : big;
   }
 };
-template <> struct BjMap<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }
-  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
+template <> struct BjMap<double> : Mfma16x16x4<double> {
   static __device__ __forceinline__ double omega(double x2) {
     x2 = x2 > 0.0 ? x2 : 0.0;
     if (x2 < 1e-4)  // (xi < 0.01: the next term of the series is 4e-20)

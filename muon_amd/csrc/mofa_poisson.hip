@@ -26,19 +26,13 @@
 
 namespace {
 
-__device__ __forceinline__ float pz_exp(float x) { return __expf(x); }
-__device__ __forceinline__ double pz_exp(double x) { return exp(x); }
-__device__ __forceinline__ float pz_log(float x) { return __logf(x); }
-__device__ __forceinline__ double pz_log(double x) { return log(x); }
-__device__ __forceinline__ float pz_log1p(float x) { return log1pf(x); }
-__device__ __forceinline__ double pz_log1p(double x) { return log1p(x); }
 template <typename T> __device__ __forceinline__ T pz_tiny();
 template <> __device__ __forceinline__ float pz_tiny<float>() { return 1e-30f; }
 template <> __device__ __forceinline__ double pz_tiny<double>() { return 1e-300; }
 
 template <typename T>
 __device__ __forceinline__ T pz_softplus(T z) {  // as torch computes it (threshold 20), clamped away from zero
-  T r = z > (T)20 ? z : pz_log1p(pz_exp(z));
+  T r = z > (T)20 ? z : mu_log1p(mu_exp(z));
   return r > pz_tiny<T>() ? r : pz_tiny<T>();
 }
 // The dense sweep of the likelihood term SUMS softplus over all (n, d): in f32 the hardware exp / log pair is enough
@@ -49,7 +43,7 @@ __device__ __forceinline__ float pz_softplus_sum(float z) {
 }
 __device__ __forceinline__ double pz_softplus_sum(double z) { return pz_softplus(z); }
 template <typename T>
-__device__ __forceinline__ T pz_sigmoid(T z) { return (T)1 / ((T)1 + pz_exp(-z)); }
+__device__ __forceinline__ T pz_sigmoid(T z) { return (T)1 / ((T)1 + mu_exp(-z)); }
 
 // The stored entries of an f32 model (k_pois_sparse): rate, sigmoid and ln(rate) of a prediction on the hardware exp2 /
 // log2 / rcp (r06; libm's log1pf + __logf and two IEEE divisions were ~110 of the ~170 vector instructions per 64
@@ -74,7 +68,7 @@ __device__ __forceinline__ PzEntryD pz_entry(double z) {
   PzEntryD r;
   r.rate = pz_softplus(z);
   r.sig = pz_sigmoid(z);
-  r.lnrate = pz_log(r.rate);
+  r.lnrate = mu_log(r.rate);
   return r;
 }
 // sum over the 64 lanes in six DPP additions, the total in lane 63 (wave_sum's __shfl_down is an LDS permute plus its
@@ -186,13 +180,8 @@ __global__ __launch_bounds__(kPzThreads) void k_pois_dense(int64_t n_own, int64_
 // (lane >> 4) + 4 r instead of 4 (lane >> 4) + r, so the reduction index of step 3 is walked as row(j, s) of the
 // instruction's own map (PmMap<T>::row; csrc/mofa_bernoulli.hip does the same) and the transform is libm's in f64.
 template <typename T> struct PmMap;
-template <> struct PmMap<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
+template <> struct PmMap<float> : Mfma16x16x4<float> {
   static constexpr int OWN = 4;  // 16-row own tiles per wave
-  static __device__ __forceinline__ int row(int q, int r) { return 4 * q + r; }
-  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
   // sigmoid and softplus of a prediction; softplus in units of `unit()`, a padding row (zeta = 0) adds `pad()` units
   static __device__ __forceinline__ void transform(float z, bool clamp, float& sig, float& sp) {
     float a = z * -1.4426950408889634f;
@@ -204,13 +193,8 @@ template <> struct PmMap<float> {
   static __device__ __forceinline__ float unit() { return 0.6931471805599453f; }
   static __device__ __forceinline__ float pad() { return 1.0f; }
 };
-template <> struct PmMap<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
+template <> struct PmMap<double> : Mfma16x16x4<double> {
   static constexpr int OWN = 2;
-  static __device__ __forceinline__ int row(int q, int r) { return q + 4 * r; }
-  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
   static __device__ __forceinline__ void transform(double z, bool, double& sig, double& sp) {
     sig = pz_sigmoid(z);
     sp = pz_softplus(z);

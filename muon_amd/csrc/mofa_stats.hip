@@ -243,13 +243,6 @@ extern "C" int mu_mofa_gs_update(int dtype, int64_t n, int K, const void* d_T, c
 // As tensor operations each was eight passes over the N x D chunk.  Arithmetic in the storage type.
 namespace {
 
-__device__ __forceinline__ float pp_exp(float x) { return __expf(x); }
-__device__ __forceinline__ double pp_exp(double x) { return exp(x); }
-__device__ __forceinline__ float pp_log(float x) { return __logf(x); }
-__device__ __forceinline__ double pp_log(double x) { return log(x); }
-__device__ __forceinline__ float pp_log1p(float x) { return log1pf(x); }
-__device__ __forceinline__ double pp_log1p(double x) { return log1p(x); }
-
 // (arithmetic in the storage type, as the tensor operations it replaces: f64 transcendentals on an f32 model made
 //  this kernel 41 % of an iteration - 1.05 ms per 1.3e8-element chunk)
 template <typename T>
@@ -259,14 +252,14 @@ __global__ __launch_bounds__(256) void k_poisson_pseudo(int64_t n, int64_t D, in
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const T z = zeta[i], y = Y[i];
     // softplus as torch computes it (threshold 20), clamped away from zero
-    T rate = z > (T)20 ? z : pp_log1p(pp_exp(z));
+    T rate = z > (T)20 ? z : mu_log1p(mu_exp(z));
     rate = rate > tiny ? rate : tiny;
     T r;
     if (mode == 0) {
-      const T sg = (T)1 / ((T)1 + pp_exp(-z));
+      const T sg = (T)1 / ((T)1 + mu_exp(-z));
       r = kappa[i % D] * z - sg * ((T)1 - y / rate);
     } else {
-      r = y * pp_log(rate) - rate;
+      r = y * mu_log(rate) - rate;
     }
     out[i] = r;
   }

@@ -29,11 +29,6 @@ constexpr int kMomWaves = 2;      // waves per workgroup of the CSR moments kern
 constexpr int kMomMaxParts = 2048;
 constexpr int kFitWaves = 4;
 
-__device__ __forceinline__ void prot_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // log(v + pc); F32: what numpy computes for a float32 matrix (the sum and the logarithm rounded to f32)
 template <typename T>
 __device__ __forceinline__ double prot_log(T v, double pc) {
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_prot_moments_csr(int64_t n, 
   double* a1 = mom_lds + (size_t)wave * 2 * d;
   double* a2 = a1 + d;
   for (int c = lane; c < d; c += 64) a1[c] = 0.0, a2[c] = 0.0;
-  prot_sync();
+  wave_lds_sync();
   for (int64_t r = r0; r < r1; ++r) {
     const int64_t e0 = uniform64(indptr[r]), e1 = uniform64(indptr[r + 1]);
     for (int64_t e = e0 + lane; e < e1; e += 64) {
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_prot_moments_csr(int64_t n, 
         a2[c] += t * t;
       }
     }
-    prot_sync();  // (rows longer than 64 entries and the next row come after this row's updates)
+    wave_lds_sync();  // (rows longer than 64 entries and the next row come after this row's updates)
   }
   double* out = part + (size_t)g * 2 * d;
   for (int c = lane; c < d; c += 64) out[c] = a1[c], out[d + c] = a2[c];
@@ -179,13 +174,13 @@ __global__ __launch_bounds__(64 * kFitWaves) void k_prot_dsb_fit(
     double* row = rowbuf[wave];
 #pragma unroll
     for (int s = 0; s < NPL; ++s) row[s * 64 + lane] = 0.0;
-    prot_sync();
+    wave_lds_sync();
     const int64_t e0 = uniform64(indptr[cell]), e1 = uniform64(indptr[cell + 1]);
     for (int64_t e = e0 + lane; e < e1; e += 64) {
       const int c = indices[e];
       if (c >= 0 && c < d) row[c] = (double)values[e];
     }
-    prot_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int s = 0; s < NPL; ++s) {
       const int j = s * 64 + lane;

@@ -31,12 +31,6 @@ struct RankStage {  // one staged entry, read by every lane at once (an LDS broa
   int32_t nz;  // value != 0: the moments' count (the rank walk stages non-zero entries only and leaves it alone)
 };
 
-// LDS written by one lane and read by another of the same wave
-__device__ __forceinline__ void rank_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // entries [lo, hi) of a row cut into kRankWaves contiguous pieces of a multiple of 64 entries
 __device__ __forceinline__ void rank_piece(int64_t lo, int64_t hi, int w, int64_t& plo, int64_t& phi) {
   const int64_t len = hi - lo;
@@ -75,7 +69,7 @@ __device__ __forceinline__ void moments_piece(int64_t lo, int64_t hi, int64_t n_
     st[lane].v = v;
     st[lane].lab = lab;
     st[lane].nz = (v != 0.0) ? 1 : 0;  // NaN counts; an explicitly stored zero does not
-    rank_wave_sync();
+    wave_lds_sync();
     const int cnt = (hi - p0) < 64 ? (int)(hi - p0) : 64;  // wave-uniform
     for (int i = 0; i < cnt; ++i) {
       const RankStage e = st[i];
@@ -85,7 +79,7 @@ __device__ __forceinline__ void moments_piece(int64_t lo, int64_t hi, int64_t n_
       ss = fma(x, x, ss);
       c += mine ? e.nz : 0;
     }
-    rank_wave_sync();
+    wave_lds_sync();
   }
 }
 
@@ -201,7 +195,7 @@ __device__ __forceinline__ void ranks_piece(int64_t lo, int64_t hi, int64_t n_ce
       st[at].v = v;
       st[at].lab = lab;
     }
-    rank_wave_sync();
+    wave_lds_sync();
     const int cnt = __popcll(m);  // wave-uniform
     for (int i = 0; i < cnt; ++i) {
       const double ev = st[i].v;
@@ -229,7 +223,7 @@ __device__ __forceinline__ void ranks_piece(int64_t lo, int64_t hi, int64_t n_ce
       run.cnt += (el == lane) ? 1 : 0;
       ++run.pos;
     }
-    rank_wave_sync();
+    wave_lds_sync();
   }
   out->rs[lane] = rs;
   out->closed[lane] = closed;
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_sums(int64_t d, int64_t n
         rank_row_range(indptr, row, nnz, lo, hi);
         if (hi - lo <= kRankCap) {
           ranks_piece<T>(lo, hi, n_cells, cells, values, labels, stage[wave], &pieces[wave], lane);
-          rank_wave_sync();
+          wave_lds_sync();
           ranks_combine(&pieces[wave], 1, n_kept, row, B, lane, out_ranksum, out_zero_rank, out_tie);
         }
       }
@@ -355,15 +349,6 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_sums(int64_t d, int64_t n
       __syncthreads();
     }
   }
-}
-
-// four rows per workgroup, at most 8 workgroups per CU (grid-stride beyond)
-static inline unsigned rank_grid(int64_t d) {
-  int64_t blocks = (d + kRankWaves - 1) / kRankWaves;
-  const int64_t cap = (int64_t)mu_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
 }
 
 extern "C" {
@@ -392,10 +377,10 @@ int mu_group_moments(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_b
   MU_REQUIRE(d_sum && d_sumsq && d_nnz, "null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_group_moments<float>, dim3(rank_grid(d)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
+    hipLaunchKernelGGL(k_group_moments<float>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
                        n_buckets, d_indptr, d_cells, (const float*)d_values, d_labels, d_sum, d_sumsq, d_nnz);
   else
-    hipLaunchKernelGGL(k_group_moments<double>, dim3(rank_grid(d)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
+    hipLaunchKernelGGL(k_group_moments<double>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
                        n_buckets, d_indptr, d_cells, (const double*)d_values, d_labels, d_sum, d_sumsq, d_nnz);
   MU_CHECK_LAUNCH();
   return MU_OK;
@@ -411,10 +396,10 @@ int mu_rank_sums(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_bucke
   MU_REQUIRE(d_ranksum && d_zero_rank && d_tie, "null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_rank_sums<float>, dim3(rank_grid(d)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
+    hipLaunchKernelGGL(k_rank_sums<float>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
                        n_kept, d_indptr, d_cells, (const float*)d_values, d_labels, d_ranksum, d_zero_rank, d_tie);
   else
-    hipLaunchKernelGGL(k_rank_sums<double>, dim3(rank_grid(d)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
+    hipLaunchKernelGGL(k_rank_sums<double>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
                        n_kept, d_indptr, d_cells, (const double*)d_values, d_labels, d_ranksum, d_zero_rank, d_tie);
   MU_CHECK_LAUNCH();
   return MU_OK;

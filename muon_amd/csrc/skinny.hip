@@ -16,24 +16,7 @@
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Mma;
-template <> struct Mma<double> {
-  typedef d4 acc_t;
-  static __device__ __forceinline__ acc_t fma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lr, int r) { return lr + 4 * r; }
-};
-template <> struct Mma<float> {
-  typedef f4 acc_t;
-  static __device__ __forceinline__ acc_t fma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lr, int r) { return 4 * lr + r; }
-};
 
 // ---- nn: out[n x 16] = Y[n x D] * Tm[D x 16] --------------------------------------------------
 // MFMA roles i = row, j = output column, k = d: the A operand wants 16 ROWS x 4 consecutive d per
@@ -60,7 +43,7 @@ template <typename T, typename TY = T, bool FAST = false>
 __global__ __launch_bounds__(256) void k_skinny_nn(int64_t n_rows, int64_t D, int64_t ldY,
                                                    const TY* __restrict__ Y, const T* __restrict__ Tm,
                                                    T* __restrict__ out, int quarters) {
-  typedef typename Mma<T>::acc_t acc_t;
+  typedef typename Mfma16x16x4<T>::acc_t acc_t;
   constexpr int CW = 128 / (int)sizeof(TY);  // columns per tile: 32 (f32 storage) / 16 (f64)
   constexpr int PE = 16 / (int)sizeof(TY);   // elements per 16-byte piece: 4 / 2
   constexpr int RS = 144;                    // LDS row stride in bytes
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(256) void k_skinny_nn(int64_t n_rows, int64_t D, in
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
           const T a = (T)*reinterpret_cast<const TY*>(&my_tiles[(q * 16 + lc) * RS + (4 * u + lr) * (int)sizeof(TY)]);
-          acc[q] = Mma<T>::fma(a, b[u], acc[q]);
+          acc[q] = Mfma16x16x4<T>::mfma(a, b[u], acc[q]);
         }
     }
     // the four quarters, added in wave order
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(256) void k_skinny_nn(int64_t n_rows, int64_t D, in
     for (int q = 0; q < kSub; ++q)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        red[((wave * kSub + q) * 16 + Mma<T>::row(lr, r)) * 16 + lc] = acc[q][r];
+        red[((wave * kSub + q) * 16 + Mfma16x16x4<T>::row(lr, r)) * 16 + lc] = acc[q][r];
     __syncthreads();
     for (int e = threadIdx.x; e < kSub * 16 * 16; e += 256) {
       const int64_t orow = r0 + e / 16;
@@ -198,7 +181,7 @@ __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64
                                                            const TY* __restrict__ Y,
                                                            const T* __restrict__ Z, int n_splits,
                                                            T* __restrict__ partial) {
-  typedef typename Mma<T>::acc_t acc_t;
+  typedef typename Mfma16x16x4<T>::acc_t acc_t;
   __shared__ T red[16 * kCT * 16];
   const int lane = threadIdx.x & 63;
   // (wave-uniform, and known to be: a loop whose trip count hangs on a per-lane `wave` is a divergent loop to the
@@ -242,7 +225,7 @@ __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64
   };
   auto mma = [&](const TY (&x)[kCT], T z) {
 #pragma unroll
-    for (int t = 0; t < kCT; ++t) acc[t] = Mma<T>::fma((T)x[t], z, acc[t]);
+    for (int t = 0; t < kCT; ++t) acc[t] = Mfma16x16x4<T>::mfma((T)x[t], z, acc[t]);
   };
   int64_t grp = g0 + wave;
   if constexpr (!PIPE) {
@@ -271,7 +254,7 @@ __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64
 #pragma unroll
       for (int t = 0; t < kCT; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) red[(16 * t + Mma<T>::row(lr, r)) * 16 + lc] += acc[t][r];
+        for (int r = 0; r < 4; ++r) red[(16 * t + Mfma16x16x4<T>::row(lr, r)) * 16 + lc] += acc[t][r];
     }
     __syncthreads();
   }

@@ -20,10 +20,7 @@ __device__ __forceinline__ float readlane_t<float>(float v, int src) {
 }
 template <>
 __device__ __forceinline__ double readlane_t<double>(double v, int src) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+  return readlane_f64(v, src);
 }
 
 template <typename T, int B>

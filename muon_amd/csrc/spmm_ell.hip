@@ -50,19 +50,6 @@ constexpr int kEWin = 384;                // bytes of a window: value[64] f32 | 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void e_dma_piece(const void* base, unsigned byte_off, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(byte_off), "s"(base), "s"(lds_dst)
-      : "memory");
-}
-
 // The window ring: slot D = a[2 D], a[2 D + 1] = (LDS offset, value bits) of this lane's slot.  Loads from asm,
 // exact counted waits (hipcc answers a register ring reloaded inside a loop with `s_waitcnt vmcnt(0)`), registers
 // the compiler does not know about except through the clobber lists (which make the kernel descriptor count them).
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(64 * (kEMaxWaves + 1)) void k_spmm_ell16(int64_t n_
       for (int piece = 0; piece < ((MODE & 2) ? 1 : kESlabBytes / 1024); ++piece) {
         unsigned o = (unsigned)s * (unsigned)kESlabBytes + (unsigned)(piece * 1024 + lane * 16);
         o = o < q_last ? o : q_last;  // past the end: never consumed
-        e_dma_piece(Q, o, lds0 + (unsigned)b * (unsigned)kESlabBytes + (unsigned)piece * 1024u);
+        dma_piece(Q, o, lds0 + (unsigned)b * (unsigned)kESlabBytes + (unsigned)piece * 1024u);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };

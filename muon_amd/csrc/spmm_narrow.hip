@@ -42,29 +42,6 @@ constexpr int kNW = 16;                  // waves per workgroup
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
 
-template <int... I, class F>
-__device__ __forceinline__ void n_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void n_static_for(F&& f) {
-  n_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
-// one LDS-DMA piece: 64 lanes x 16 B land contiguously at the wave-uniform LDS byte address
-__device__ __forceinline__ void n_dma_piece(const void* base, unsigned byte_off, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(byte_off), "s"(base), "s"(lds_dst)
-      : "memory");
-}
-
 // The four 16-lane rows of a register, each replicated into all four rows:
 // x[w] in lane 16 c + e  =  the input's lane 16 w + e.
 struct Rows4 { unsigned x[4]; };
@@ -141,7 +118,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
     const int cq = (lane & 3) ^ ((j >> 2) & 3);                   // the logical quad that belongs there
     unsigned off = (unsigned)s0 * 64u + (unsigned)(j * 64 + cq * 16);
     off = off < q_last ? off : q_last;  // tail / past the end: clamp (never consumed)
-    n_dma_piece(Q, off, qs_lds + (unsigned)buf * (unsigned)kNSlabBytes + (unsigned)piece * 1024u);
+    dma_piece(Q, off, qs_lds + (unsigned)buf * (unsigned)kNSlabBytes + (unsigned)piece * 1024u);
   };
   const char* __restrict__ entb = reinterpret_cast<const char*>(entw);
   const unsigned lane8 = (unsigned)lane * 8u, last8 = wg_last * 8u;
@@ -178,7 +155,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
         curv = (unsigned)(sptr[p] - wg0);
         endv = (unsigned)(sptr[p + 1] - wg0);
       }
-      n_static_for<RW>([&](auto rc) {
+      static_for<RW>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         cur[r] = (unsigned)__builtin_amdgcn_readlane((int)curv, r);
         end[r] = (unsigned)__builtin_amdgcn_readlane((int)endv, r);
@@ -187,7 +164,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
     f4 acc[RW];
     int wcol[RW];
     float wval[RW];
-    n_static_for<RW>([&](auto rc) {
+    static_for<RW>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
       acc[r] = (f4)(0.f);
       request(cur[r], wcol[r], wval[r]);
@@ -337,7 +314,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
         int en, on;
         dma_one(s0 + kNSlab, buf ^ 1, 0);  // the next slab (the last slab's pieces are never read)
         front(std::integral_constant<int, 0>{}, ea0, ea1, ea2, ea3, ev0, ev1, ev2, ev3, en);
-        n_static_for<RW>([&](auto rc) {
+        static_for<RW>([&](auto rc) {
           constexpr int r = decltype(rc)::value;
           constexpr bool kPipe3 = (ABL == 0) && !STAGE;
           f4 q0, q1, q2, q3;
@@ -362,7 +339,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
       while (again) {  // rows with 64 and more entries in one slab (uniform, rare)
         const unsigned pend = again;
         again = 0;
-        n_static_for<RW>([&](auto rc) {
+        static_for<RW>([&](auto rc) {
           if (pend & (1u << decltype(rc)::value)) {
             unsigned a0, a1, a2, a3;
             float v0, v1, v2, v3;
@@ -382,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
     }
 
     // slot partial sums -> row sums in a fixed order; lanes e == 0 store
-    n_static_for<RW>([&](auto rc) {
+    static_for<RW>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
       f4 v = acc[r];
 #pragma unroll

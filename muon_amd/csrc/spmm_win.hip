@@ -126,22 +126,6 @@ __device__ __forceinline__ void pair_fma(const Pair<NB, DT>& r, float v, typenam
   for (int c = 0; c < NB; ++c) acc[c] = mu_fma(v1, r.q1[c], acc[c]);
 }
 
-// one LDS-DMA piece: 64 lanes x 16 B land contiguously at the wave-uniform LDS byte address; the source
-// is base (scalar) + a 32-bit byte offset per lane (r03: the 64-bit per-lane addresses of r02 cost four
-// registers and a 64-bit clamp per piece; the dense operand is < 4 GiB, checked on the host)
-__device__ __forceinline__ void dma_piece(const void* base, unsigned byte_off, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(byte_off), "s"(base), "s"(lds_dst)
-      : "memory");
-}
-
 // The window of every (row-set k, group) that is in flight lives in v[kNX + 2k] (column) and
 // v[kNX + 2k + 1] (value bits).  These registers are written by the asm loads while the wave keeps
 // running, so they must never be visible to hipcc as values: a compiler-made copy of a register
@@ -192,15 +176,6 @@ __device__ __forceinline__ void set_window(int col, int valbits) {
       :
       : "v"(col), "v"(valbits), "i"(kNX + 2 * k), "i"(kNX + 2 * k + 1)
       : MU_WIN_CLOB);
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
 // r06 - RANGED launches (the warm start's products on a cell slice): a workgroup walks a LIST of column
@@ -783,12 +758,6 @@ __global__ __launch_bounds__(256) void k_stream_fill(int64_t n_pos, const int32_
 // 256 entries.  Here the loads are unconditional (a lane past the row's end re-reads the row's last entry and stores it
 // again: same address, same bits), issued from asm, two iterations in flight per wave; the wait for a set leaves
 // the next set's eight loads outstanding.  Same bytes out.
-__device__ __forceinline__ void sf_load(const int32_t* ib, const float* vb, unsigned off, int32_t& c, float& v) {
-  asm volatile("global_load_dword %0, %2, %3\n\tglobal_load_dword %1, %2, %4"
-               : "=&v"(c), "=&v"(v)
-               : "v"(off), "s"(ib), "s"(vb)
-               : "memory");
-}
 template <int N>
 __device__ __forceinline__ void sf_wait(int32_t (&c)[4], float (&v)[4]) {
   asm volatile("s_waitcnt vmcnt(%8)"
@@ -829,7 +798,7 @@ __global__ __launch_bounds__(256) void k_stream_fill_pipe(int64_t n_pos, const i
       for (int u = 0; u < 4; ++u) {
         int q = j0 + lane + 64 * u;
         q = q < len ? q : len - 1;
-        sf_load(ib, vb, (unsigned)q * 4u, c[u], v[u]);
+        load_pair(ib, vb, (unsigned)q * 4u, c[u], v[u]);
       }
     };
     auto store = [&](int32_t (&c)[4], float (&v)[4], int j0) {

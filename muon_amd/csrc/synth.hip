@@ -102,13 +102,6 @@ __global__ __launch_bounds__(256) void k_synth(int64_t row0, int64_t n_rows, int
   }
 }
 
-static inline unsigned synth_blocks(int64_t n_rows) {
-  int64_t blocks = (n_rows + 3) / 4;
-  const int64_t cap = (int64_t)mu_num_cus() * 32;
-  if (blocks > cap) blocks = cap;
-  return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
 extern "C" {
 
 int mu_synth_row_nnz(int64_t row0, int64_t n_rows, int64_t n_cols, int n_topics, double density,
@@ -116,7 +109,7 @@ int mu_synth_row_nnz(int64_t row0, int64_t n_rows, int64_t n_cols, int n_topics,
   MU_REQUIRE(n_rows >= 0 && n_cols > 0 && n_topics >= 0 && density > 0, "bad arguments");
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_row_nnz, "null pointer");
-  hipLaunchKernelGGL(k_synth<false>, dim3(synth_blocks(n_rows)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_synth<false>, dim3(wave_grid(n_rows, 4, 32)), dim3(256), 0, (hipStream_t)stream,
                      row0, n_rows, n_cols, n_topics, density, seed, d_row_nnz, nullptr, nullptr,
                      nullptr);
   MU_CHECK_LAUNCH();
@@ -129,7 +122,7 @@ int mu_synth_fill(int64_t row0, int64_t n_rows, int64_t n_cols, int n_topics, do
   MU_REQUIRE(n_rows >= 0 && n_cols > 0 && n_topics >= 0 && density > 0, "bad arguments");
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_indices && d_values, "null pointer");
-  hipLaunchKernelGGL(k_synth<true>, dim3(synth_blocks(n_rows)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_synth<true>, dim3(wave_grid(n_rows, 4, 32)), dim3(256), 0, (hipStream_t)stream,
                      row0, n_rows, n_cols, n_topics, density, seed, nullptr, d_indptr, d_indices,
                      d_values);
   MU_CHECK_LAUNCH();

@@ -7,15 +7,6 @@
 
 #include "sweep.hpp"
 
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
 // ---------------------------------------------------------------------------------
 // slab pointers
 // ---------------------------------------------------------------------------------
@@ -156,12 +147,7 @@ __global__ __launch_bounds__(kSweepThreads, sizeof(T) == 4 ? 8 : 4) void k_row_c
 // in chunk order; the wait for chunk u of a set allows the loads issued after it - the rest of its own set and the
 // whole next set - to be outstanding: 2 (CH - 1 - u) + 2 CH.  (Stores of the scale sweep issued in between only
 // make the wait stricter.)  Offsets are 32-bit byte offsets from the row block's first entry (host: < 2^30 entries).
-__device__ __forceinline__ void pipe_load(const int32_t* ib, const float* vb, unsigned off, int32_t& c, float& v) {
-  asm volatile("global_load_dword %0, %2, %3\n\tglobal_load_dword %1, %2, %4"
-               : "=&v"(c), "=&v"(v)
-               : "v"(off), "s"(ib), "s"(vb)
-               : "memory");
-}
+// (The loads themselves: common.hpp's load_pair.)
 template <int N>
 __device__ __forceinline__ void pipe_wait(int32_t& c, float& v) {
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(c), "+v"(v) : "n"(N) : "memory");
@@ -176,20 +162,6 @@ __device__ __forceinline__ void pipe_drain(A (&c0)[4], B (&v0)[4], A (&c1)[4], B
                :
                : "memory");
 }
-
-struct FlatWalk {
-  int l, pb, hi, nrow, step;
-  // the next iteration: false when the strip is through (wave-uniform: every member lives in scalar registers)
-  __device__ __forceinline__ bool advance(int lo_l, int hi_l) {
-    pb += step;
-    while (pb >= hi) {
-      if (++l >= nrow) return false;
-      pb = __builtin_amdgcn_readlane(lo_l, l);
-      hi = __builtin_amdgcn_readlane(hi_l, l);
-    }
-    return true;
-  }
-};
 
 // ABL (timing ablations, wrong results; tune "tfidf_abl"): 1 no LDS atomics, 2 f32 atomics
 // M: bins of M x 8192 columns (M = 2: 128 KiB, one workgroup per CU - pieces of a row twice as long: 14.3 -> 13.1 ms
@@ -237,7 +209,7 @@ __global__ __launch_bounds__(kSweepThreads, (sizeof(T) == 4 && M == 1) ? 8 : 4) 
           int q = pb + lane + 64 * u;
           q = q < hi ? q : hi - 1;
           if constexpr (kAsm) {
-            pipe_load(ib, vb, (unsigned)q * 4u, c[u], v[u]);
+            load_pair(ib, vb, (unsigned)q * 4u, c[u], v[u]);
           } else {
             c[u] = ib[q];
             v[u] = vb[q];
@@ -600,7 +572,7 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_tfidf_scale_sweep_pipe(
         for (int u = 0; u < CH; ++u) {
           int q = pb + lane + 64 * u;
           q = q < hi ? q : hi - 1;
-          pipe_load(ib, vb, (unsigned)q * 4u, c[u], x[u]);
+          load_pair(ib, vb, (unsigned)q * 4u, c[u], x[u]);
         }
       };
       auto work = [&](int32_t (&c)[CH], float (&x)[CH], int pb, int hi, int l) {
@@ -810,15 +782,6 @@ __global__ __launch_bounds__(256) void k_binarize(int64_t n, T* __restrict__ v) 
     if (v[i] != (T)0) v[i] = (T)1;  // preproc.py:150
 }
 
-static inline unsigned grid_for_rows(int64_t n_rows) {
-  // one wave per row, 4 waves per block, capped at 16 blocks per CU (grid-stride beyond)
-  int64_t blocks = (n_rows + 3) / 4;
-  const int64_t cap = (int64_t)mu_num_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
 extern "C" {
 
 size_t mu_csr_row_col_sums_worksize(int64_t n_rows, int64_t n_cols) {
@@ -896,7 +859,7 @@ static int row_col_sums_impl(int dtype, int64_t n_rows, int64_t n_cols, const in
   const int64_t S = num_slabs(n_cols);
   const int G = sweep_grid();
   const int64_t* sp = d_slab_ptr ? d_slab_ptr : (const int64_t*)d_work;
-  size_t off = ((size_t)(n_rows * (S + 1)) * sizeof(int64_t) + 255) & ~(size_t)255;
+  size_t off = align256((size_t)(n_rows * (S + 1)) * sizeof(int64_t));
   double* partial = (double*)((char*)d_work + off);
   // software-pipelined walk (r04); tune "tfidf_pipe" = 1: the kernels of before, for comparison.  f32 matrices of
   // 100 000 rows and more: 16 384-column bins, one workgroup per CU (tune "tfidf_sum_m" = 1: never, 2: whatever
@@ -963,7 +926,7 @@ int mu_tfidf_scale(int dtype, int64_t n_rows, const int64_t* d_indptr, const int
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_rowsum && d_idf && d_out, "null pointer");
   const int use_scale = !(scale == 0.0 || scale == 1.0);  // preproc.py:101
-  const unsigned blocks = grid_for_rows(n_rows);
+  const unsigned blocks = wave_grid(n_rows, 4, 16);
   if (dtype == MU_DTYPE_F32)
     hipLaunchKernelGGL(k_tfidf_scale<float>, dim3(blocks), dim3(256), 0, st, n_rows, d_indptr,
                        d_indices, (const float*)d_values, d_rowsum, (const float*)d_idf,
@@ -1090,7 +1053,7 @@ int mu_csr_count_nonzero(int dtype, int64_t n_rows, const int64_t* d_indptr, con
   MU_REQUIRE(dtype == MU_DTYPE_F32 || dtype == MU_DTYPE_F64, "dtype must be f32 or f64");
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_row_nnz, "null pointer");
-  const unsigned blocks = grid_for_rows(n_rows);
+  const unsigned blocks = wave_grid(n_rows, 4, 16);
   if (dtype == MU_DTYPE_F32)
     hipLaunchKernelGGL(k_count_nonzero<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        n_rows, d_indptr, (const float*)d_values, d_row_nnz);
@@ -1108,7 +1071,7 @@ int mu_csr_compact_nonzero(int dtype, int64_t n_rows, const int64_t* d_indptr,
   MU_REQUIRE(dtype == MU_DTYPE_F32 || dtype == MU_DTYPE_F64, "dtype must be f32 or f64");
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_new_indptr, "null pointer");
-  const unsigned blocks = grid_for_rows(n_rows);
+  const unsigned blocks = wave_grid(n_rows, 4, 16);
   if (dtype == MU_DTYPE_F32)
     hipLaunchKernelGGL(k_compact_nonzero<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        n_rows, d_indptr, d_indices, (const float*)d_values, d_new_indptr,

@@ -58,38 +58,9 @@ __device__ __forceinline__ void t4_store(const T4Out& o, int64_t pos, unsigned l
   }
 }
 
-// lane `L` of v <- the wave-uniform x (this clang has no writelane builtin)
-template <int L>
-__device__ __forceinline__ int writelane_c(int v, int x) {
-  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(x), "n"(L));
-  return v;
-}
-__device__ __forceinline__ int writelane_s(int v, int x, int l) {  // (lane select in M0: one SGPR operand per instruction)
-  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");
-  return v;
-}
-
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // ---- count: entries per (row block, column), row blocks of `rpb` consecutive rows ------------------------------------
 // (the r04 pipelined count sweep with fixed row blocks: the pieces of a wave's strip of rows as one flat sequence of
 //  iterations, unconditional clamped loads from asm, two iterations in flight, bins of M x 8192 columns)
-struct T4Walk {
-  int l, pb, hi, nrow, step;
-  __device__ __forceinline__ bool advance(int lo_l, int hi_l) {
-    pb += step;
-    while (pb >= hi) {
-      if (++l >= nrow) return false;
-      pb = __builtin_amdgcn_readlane(lo_l, l);
-      hi = __builtin_amdgcn_readlane(hi_l, l);
-    }
-    return true;
-  }
-};
 template <int N>
 __device__ __forceinline__ void t4c_wait(int32_t (&c)[4]) {
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]) : "n"(N) : "memory");
@@ -120,7 +91,7 @@ __global__ __launch_bounds__(kT) void k_t4_count(int64_t n_rows, int64_t n_cols,
       }
       asm volatile("" ::"v"(lo_l), "v"(hi_l));  // (the compiler's wait for these loads: here, not inside the walk)
       const int64_t left = (r1 - strip + kNW - 1) / kNW;
-      T4Walk w{-1, 0, 0, left < 64 ? (int)left : 64, 256};
+      FlatWalk w{-1, 0, 0, left < 64 ? (int)left : 64, 256};
       int32_t ca[4], cb[4];
       auto load = [&](int32_t (&c)[4], int pb, int hi) {
 #pragma unroll
@@ -315,15 +286,6 @@ __device__ __forceinline__ void t4_take_header(uint32_t& b0, uint32_t& b1, int64
   cd = (int64_t)(((unsigned long long)hi << 32) | lo);
 }
 
-template <int... I, class F>
-__device__ __forceinline__ void t4_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void t4_for(F&& f) {
-  t4_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
 __device__ unsigned long long g_t4_phase[8];  // tune tpack_dbg: cycles of header / phase 1 / 2 / 3 / write-out / retries
 
 // PAIRS: the source is the row stream of X (src0 = ent, row_dst[row] = pair index of the row's first pair);
@@ -386,7 +348,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
   const unsigned subo = (unsigned)sub * (PAIRS ? 8u : 4u);
   int pa = -1, pb = -1;  // rows (of this wave) whose continuation window the next issue prefetches into slot kSlotP
   int ld = 0;            // CIRC, lane l < 32: pairs of row l behind its cursor that sit in its window already
-  if constexpr (CIRC) t4_for<16>([&](auto jc) { t4_pad_slot<decltype(jc)::value>(); });
+  if constexpr (CIRC) static_for<16>([&](auto jc) { t4_pad_slot<decltype(jc)::value>(); });
   auto issue_all = [&]() {
     const int remc = rem < 32 ? rem : 32;  // (rem >= 0 always)
     if constexpr (CIRC) {
@@ -396,7 +358,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
       const unsigned rot = __builtin_rotateleft32((unsigned)((1ull << nn) - 1ull), s5);
       const uint64_t b256 = st & ~255ull;
       ld = remc;
-      t4_for<16>([&](auto jc) {
+      static_for<16>([&](auto jc) {
         constexpr int J = decltype(jc)::value;
         t4_issue_circ<J>(readlane_u64(b256, 2 * J), readlane_u64(b256, 2 * J + 1),
                          (unsigned)__builtin_amdgcn_readlane((int)s5, 2 * J), (unsigned)__builtin_amdgcn_readlane((int)s5, 2 * J + 1),
@@ -404,7 +366,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
                          (unsigned)sub, subo, subo + 256u);
       });
     } else {
-    t4_for<16>([&](auto jc) {
+    static_for<16>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       const int n0 = __builtin_amdgcn_readlane(remc, 2 * J), n1 = __builtin_amdgcn_readlane(remc, 2 * J + 1);
       if constexpr (PAIRS)
@@ -533,7 +495,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
 
     // ---- phase 1: the tile's entries set their row's bit in word (wave, column) ---------------------------------------
     int cntv = 0;          // lane r < 32: entries of row r consumed by this tile
-    t4_for<16>([&](auto jc) {
+    static_for<16>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       const int c = t4_col<J>();
       const bool valid = c < cend;  // sorted rows: a prefix of each half; padding lanes hold INT_MAX
@@ -687,10 +649,10 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
     };
     {
       Ent fs[8];
-      t4_for<8>([&](auto jc) { fs[decltype(jc)::value] = fetch(jc); });
-      t4_for<8>([&](auto jc) { place(fs[decltype(jc)::value], 2 * decltype(jc)::value, 2 * decltype(jc)::value + 1); });
-      t4_for<8>([&](auto jc) { fs[decltype(jc)::value] = fetch(std::integral_constant<int, 8 + decltype(jc)::value>{}); });
-      t4_for<8>([&](auto jc) {
+      static_for<8>([&](auto jc) { fs[decltype(jc)::value] = fetch(jc); });
+      static_for<8>([&](auto jc) { place(fs[decltype(jc)::value], 2 * decltype(jc)::value, 2 * decltype(jc)::value + 1); });
+      static_for<8>([&](auto jc) { fs[decltype(jc)::value] = fetch(std::integral_constant<int, 8 + decltype(jc)::value>{}); });
+      static_for<8>([&](auto jc) {
         constexpr int J = 8 + decltype(jc)::value;
         place(fs[decltype(jc)::value], 2 * J, 2 * J + 1);
       });
@@ -709,7 +671,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
     if constexpr (CIRC) {
       int padv = 0x7fffffff;
       asm volatile("" : "+v"(padv));
-      t4_for<16>([&](auto jc) { t4_retire_slot<decltype(jc)::value>(cend, padv); });
+      static_for<16>([&](auto jc) { t4_retire_slot<decltype(jc)::value>(cend, padv); });
     }
     if (half == 0) {
       A += (uint64_t)(unsigned)cntv * (PAIRS ? 8u : 4u);
@@ -740,7 +702,6 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
     for (int i = 0; i < 6; ++i) atomicAdd(&g_t4_phase[i], ph[i]);
 }
 
-inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 struct T4Geo {
   int rw;        // rows of a wave
   int64_t rpb;   // rows of a block
@@ -786,8 +747,8 @@ struct T4Work {
 inline size_t t4_worksize(int64_t n_rows, int64_t n_cols, int64_t nnz) {
   const int64_t S = (n_cols + kCountSlab - 1) / kCountSlab;
   const T4Geo q = t4_geometry(n_rows, n_cols, nnz);
-  return al((size_t)(n_rows * (S + 1)) * sizeof(int64_t)) + al((size_t)(q.G + 1) * (size_t)n_cols * sizeof(uint32_t)) +
-         2 * al((size_t)n_cols * sizeof(int64_t)) + 256 + 256;
+  return align256((size_t)(n_rows * (S + 1)) * sizeof(int64_t)) + align256((size_t)(q.G + 1) * (size_t)n_cols * sizeof(uint32_t)) +
+         2 * align256((size_t)n_cols * sizeof(int64_t)) + 256 + 256;
 }
 struct T4Off {  // byte offsets of the pieces inside the work buffer
   size_t cnt, coltot, cdst, err;
@@ -796,10 +757,10 @@ inline T4Off t4_offsets(int64_t n_rows, int64_t n_cols, int64_t nnz) {
   const int64_t S = (n_cols + kCountSlab - 1) / kCountSlab;
   const T4Geo q = t4_geometry(n_rows, n_cols, nnz);
   T4Off o;
-  o.cnt = al((size_t)(n_rows * (S + 1)) * sizeof(int64_t));
-  o.coltot = o.cnt + al((size_t)(q.G + 1) * (size_t)n_cols * sizeof(uint32_t));
-  o.cdst = o.coltot + al((size_t)n_cols * sizeof(int64_t));
-  o.err = o.cdst + al((size_t)n_cols * sizeof(int64_t));
+  o.cnt = align256((size_t)(n_rows * (S + 1)) * sizeof(int64_t));
+  o.coltot = o.cnt + align256((size_t)(q.G + 1) * (size_t)n_cols * sizeof(uint32_t));
+  o.cdst = o.coltot + align256((size_t)n_cols * sizeof(int64_t));
+  o.err = o.cdst + align256((size_t)n_cols * sizeof(int64_t));
   return o;
 }
 inline T4Work t4_carve(void* work, int64_t n_rows, int64_t n_cols, int64_t nnz) {

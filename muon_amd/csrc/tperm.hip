@@ -37,20 +37,6 @@ constexpr int kNone = 0xff;         // "no row" in a continuation word
       "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117",    \
       "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127"
 
-template <int L>
-__device__ __forceinline__ int tp_writelane_c(int v, int x) {
-  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(x), "n"(L));
-  return v;
-}
-__device__ __forceinline__ int tp_writelane_s(int v, int x, int l) {
-  asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");
-  return v;
-}
-__device__ __forceinline__ uint64_t tp_readlane_u64(uint64_t v, int l) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ int tp_wave_min(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -277,15 +263,6 @@ __device__ __forceinline__ void tp_issue_header(const uint32_t* bg, const uint32
       : MU_TP_CLOB, "memory");
 }
 
-template <int... I, class F>
-__device__ __forceinline__ void tp_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void tp_for(F&& f) {
-  tp_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
 // ---- the per-step fill ---------------------------------------------------------------------------------------------
 // Tile t of a block: [top] wait for everything in flight (windows of t, header of t + 1, the write-out's stores) - the
 // header of t + 1 is scanned (per-wave sums into wsum) - every entry of t goes to stage[t & 1][slot] - the windows of
@@ -340,7 +317,7 @@ __device__ __forceinline__ void tperm_move_body(
   const int nt = (int)(uniform64(toff[g + 1]) - uniform64(toff[g]));
   const uint32_t* cw = cont + (tb - g) * kNW + wave;     // this wave's continuation word of tile t: cw[t * kNW]
   const unsigned subo = (unsigned)sub * 8u, sub2 = (unsigned)sub * 2u;
-  tp_for<16>([&](auto jc) { tp_pad_slot<decltype(jc)::value>(); });
+  static_for<16>([&](auto jc) { tp_pad_slot<decltype(jc)::value>(); });
 
   // windows of tile `t` (the cursors stand at its first pairs)
   auto cont_of = [&](int t) { return t < nt ? uniform32((int)cw[(int64_t)t * kNW]) : (kNone | (kNone << 8)); };
@@ -353,10 +330,10 @@ __device__ __forceinline__ void tperm_move_body(
     const uint64_t b256 = st & ~255ull;
     const uint64_t tb64 = (uint64_t)slots + ((b256 - (uint64_t)xent) >> 2);
     ld = remc;
-    tp_for<16>([&](auto jc) {
+    static_for<16>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
-      tp_issue_circ<J>(tp_readlane_u64(b256, 2 * J), tp_readlane_u64(b256, 2 * J + 1), tp_readlane_u64(tb64, 2 * J),
-                       tp_readlane_u64(tb64, 2 * J + 1), (unsigned)__builtin_amdgcn_readlane((int)s5, 2 * J),
+      tp_issue_circ<J>(readlane_u64(b256, 2 * J), readlane_u64(b256, 2 * J + 1), readlane_u64(tb64, 2 * J),
+                       readlane_u64(tb64, 2 * J + 1), (unsigned)__builtin_amdgcn_readlane((int)s5, 2 * J),
                        (unsigned)__builtin_amdgcn_readlane((int)s5, 2 * J + 1),
                        (unsigned)__builtin_amdgcn_readlane((int)rot, 2 * J),
                        (unsigned)__builtin_amdgcn_readlane((int)rot, 2 * J + 1), (unsigned)sub, subo, subo + 256u, sub2,
@@ -368,7 +345,7 @@ __device__ __forceinline__ void tperm_move_body(
       int na = __builtin_amdgcn_readlane(rem, pa) - 32, nb = pb != kNone ? __builtin_amdgcn_readlane(rem, pb) - 32 : 0;
       na = __builtin_amdgcn_readfirstlane(na < 0 ? 0 : (na > 32 ? 32 : na));
       nb = __builtin_amdgcn_readfirstlane(nb < 0 ? 0 : (nb > 32 ? 32 : nb));
-      const uint64_t a0 = tp_readlane_u64(A, pa) + 256u, a1 = tp_readlane_u64(A, lb) + 256u;
+      const uint64_t a0 = readlane_u64(A, pa) + 256u, a1 = readlane_u64(A, lb) + 256u;
       tp_issue_cont(a0, a1, (uint64_t)slots + ((a0 - (uint64_t)xent) >> 2), (uint64_t)slots + ((a1 - (uint64_t)xent) >> 2),
                     na, nb, subo, sub2);
     }
@@ -493,15 +470,15 @@ __device__ __forceinline__ void tperm_move_body(
     unsigned long long* stg = stage[set];
     const unsigned wbase = (unsigned)(wave * rw) - ((unsigned)c0 << 16);
     int cntv = 0;  // lane r < 32: pairs of row r consumed by this tile
-    tp_for<16>([&](auto jc) {
+    static_for<16>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       const int c = (int)tp_reg<kW0 + 2 * J>();
       const unsigned v = tp_reg<kW0 + 2 * J + 1>(), s = tp_reg<kS0 + J>();
       const bool valid = c < cend;  // sorted rows: a run of each half; padding lanes hold INT_MAX
       const unsigned long long m = __ballot(valid);
       if (valid) stg[s] = (unsigned long long)(((unsigned)c << 16) + (wbase + 2 * J + hf)) | ((unsigned long long)v << 32);
-      cntv = tp_writelane_c<2 * J>(cntv, __popc((unsigned)m));
-      cntv = tp_writelane_c<2 * J + 1>(cntv, __popc((unsigned)(m >> 32)));
+      cntv = writelane_c<2 * J>(cntv, __popc((unsigned)m));
+      cntv = writelane_c<2 * J + 1>(cntv, __popc((unsigned)(m >> 32)));
     });
     const int pa = pw & 0xff, pb = pw >> 8;
     if (pa != kNone) {  // the rows the plan gave a continuation window
@@ -511,15 +488,15 @@ __device__ __forceinline__ void tperm_move_body(
       const bool valid = c < cend;
       const unsigned long long m = __ballot(valid);
       if (valid) stg[s] = (unsigned long long)(((unsigned)c << 16) + (wbase + (hf ? lb : pa))) | ((unsigned long long)v << 32);
-      cntv = tp_writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pa) + __popc((unsigned)m), pa);
-      if (pb != kNone) cntv = tp_writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pb) + __popc((unsigned)(m >> 32)), pb);
+      cntv = writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pa) + __popc((unsigned)m), pa);
+      if (pb != kNone) cntv = writelane_s(cntv, __builtin_amdgcn_readlane(cntv, pb) + __popc((unsigned)(m >> 32)), pb);
     }
     stamp(integral_constant<int, 2>{});
     // the cursors move on, the consumed lanes are free, the next windows are requested
     {
       int padv = 0x7fffffff;
       asm volatile("" : "+v"(padv));
-      tp_for<16>([&](auto jc) { tp_retire_slot<decltype(jc)::value>(cend, padv); });
+      static_for<16>([&](auto jc) { tp_retire_slot<decltype(jc)::value>(cend, padv); });
     }
     if (half == 0) {
       A += (uint64_t)(unsigned)cntv * 8u;

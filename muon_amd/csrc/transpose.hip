@@ -132,9 +132,9 @@ size_t mu_csr_transpose_worksize(int64_t n_rows, int64_t n_cols, int64_t nnz) {
   const int64_t S = num_slabs(n_cols);
   const int G = sweep_grid();
   size_t b = 0;
-  b += ((size_t)(n_rows * (S + 1)) * sizeof(int64_t) + 255) & ~(size_t)255;  // slab pointers
-  b += ((size_t)G * (size_t)n_cols * sizeof(uint32_t) + 255) & ~(size_t)255;  // cnt / base
-  b += ((size_t)n_cols * sizeof(int64_t) + 255) & ~(size_t)255;               // column totals
+  b += align256((size_t)(n_rows * (S + 1)) * sizeof(int64_t));  // slab pointers
+  b += align256((size_t)G * (size_t)n_cols * sizeof(uint32_t));  // cnt / base
+  b += align256((size_t)n_cols * sizeof(int64_t));               // column totals
   return b + 256;
 }
 
@@ -158,9 +158,9 @@ int mu_csr_transpose(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
   const int G = sweep_grid();
   char* w = (char*)d_work;
   int64_t* sp = (int64_t*)w;
-  w += ((size_t)(n_rows * (S + 1)) * sizeof(int64_t) + 255) & ~(size_t)255;
+  w += align256((size_t)(n_rows * (S + 1)) * sizeof(int64_t));
   uint32_t* cnt = (uint32_t*)w;
-  w += ((size_t)G * (size_t)n_cols * sizeof(uint32_t) + 255) & ~(size_t)255;
+  w += align256((size_t)G * (size_t)n_cols * sizeof(uint32_t));
   int64_t* coltot = (int64_t*)w;
 
   int rc = launch_slab_ptr(n_rows, n_cols, d_indptr, d_indices, sp, st);

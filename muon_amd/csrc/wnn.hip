@@ -26,17 +26,6 @@ constexpr int kBwCap = 8192;     // candidate entries per wave, repetitions incl
 constexpr int kBwWaves = 4;
 constexpr int kBwPMax = 256;     // embedding dimensions held in LDS
 
-__device__ __forceinline__ void bw_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 struct BwLds {
   int ids[kBwCap];  // candidates with repetitions, then sorted
   double xi[kBwPMax];
@@ -56,7 +45,7 @@ __global__ __launch_bounds__(64 * kBwWaves) void k_wnn_bandwidth(
   for (int64_t cell = (int64_t)blockIdx.x * kBwWaves + wave; cell < n; cell += n_waves) {
     const int64_t g0 = uniform64(g_ptr[cell]), g1 = uniform64(g_ptr[cell + 1]);
     const double deg_i = (double)(g1 - g0);
-    bw_sync();  // (the previous cell is done with xi)
+    wave_lds_sync();  // (the previous cell is done with xi)
     for (int d = lane; d < p; d += 64) L.xi[d] = X[cell * p + d];
     // 1. the cells that list one of this cell's neighbours
     int m = 0;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(64 * kBwWaves) void k_wnn_bandwidth(
     int P = 64;
     while (P < m) P <<= 1;
     for (int t = m + lane; t < P; t += 64) L.ids[t] = 0x7fffffff;
-    bw_sync();
+    wave_lds_sync();
     for (int k = 2; k <= P; k <<= 1) {
       for (int j = k >> 1; j > 0; j >>= 1) {
         for (int t = lane; t < P; t += 64) {
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(64 * kBwWaves) void k_wnn_bandwidth(
             }
           }
         }
-        bw_sync();
+        wave_lds_sync();
       }
     }
     // 3. runs -> (candidate, overlap) -> key; 4. the n_bw smallest (key, candidate) pairs live in the lanes:

@@ -48,7 +48,7 @@ CHUNK = 256  # csrc/fragments.hip's candidates per work item
 
 
 def wave_grid(n_cus):
-    """waves frag_wave_grid launches at most: a wave per work item, 4 to a block, 16 blocks per CU"""
+    """waves csrc/fragments.hip's wave_grid(n, 4, 16) launches at most: a wave per work item, 4 to a block, 16 blocks per CU"""
     return 64 * n_cus
 
 

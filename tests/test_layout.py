@@ -203,16 +203,14 @@ def test_stream_spmm_isa_keeps_out_of_the_asm_owned_registers(tmp_path):
     naming v110+, 126 allocated VGPRs."""
     import re
     import shutil
-    import subprocess
+
+    from muon_amd.csrc import build as csrc_build
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "spmm_win.hip")
     out = tmp_path / "spmm_win.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), "-S", "--cuda-device-only", "-w",
-                           "-o", str(out), src])
+    csrc_build.device_asm("spmm_win.hip", out)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN[^\n:]*k_spmm_win[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
@@ -252,19 +250,15 @@ def test_poisson_matrix_core_sweep_isa(tmp_path):
     tiles per wave, libm in the transform)."""
     import re
     import shutil
-    import subprocess
 
     from muon_amd.csrc import build as csrc_build
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "mofa_poisson.hip")
     assert "-amdgpu-mfma-vgpr-form" in csrc_build.EXTRA["mofa_poisson.hip"]
     out = tmp_path / "mofa_poisson.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), *csrc_build.EXTRA["mofa_poisson.hip"], "-S",
-                           "--cuda-device-only", "-w", "-o", str(out), src])
+    csrc_build.device_asm("mofa_poisson.hip", out)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN[^\n:]*k_pois_mfmaI([fd])Li(\d+)ELi(\d)E[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
@@ -294,19 +288,15 @@ def test_jaakkola_sweep_isa(tmp_path):
     accumulator register."""
     import re
     import shutil
-    import subprocess
 
     from muon_amd.csrc import build as csrc_build
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "mofa_bernoulli.hip")
     assert "-amdgpu-mfma-vgpr-form" in csrc_build.EXTRA["mofa_bernoulli.hip"]
     out = tmp_path / "mofa_bernoulli.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), *csrc_build.EXTRA["mofa_bernoulli.hip"], "-S",
-                           "--cuda-device-only", "-w", "-o", str(out), src])
+    csrc_build.device_asm("mofa_bernoulli.hip", out)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN[^\n:]*k_jaakkola_sweepI([fd])Li(\d+)ELi(\d+)E[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
@@ -328,16 +318,14 @@ def test_tpack4_isa_keeps_out_of_the_asm_owned_registers(tmp_path):
     (scratch traffic shares vmcnt with the hand-placed waits)."""
     import re
     import shutil
-    import subprocess
+
+    from muon_amd.csrc import build as csrc_build
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "tpack4.hip")
     out = tmp_path / "tpack4.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), "-S", "--cuda-device-only", "-w",
-                           "-o", str(out), src])
+    csrc_build.device_asm("tpack4.hip", out)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN[^\n:]*k_t4_fill[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M)
     assert len(kernels) == 7  # (row stream | CSR arrays) x (stream target, CSR target, stream target with phase accounting) + the row stream through circular windows

@@ -5,22 +5,18 @@ fields, nothing else."""
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from muon_amd.csrc import build as csrc_build
 
 
 def test_wide_slab_instances_in_the_isa(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "spmm_win.hip")
     out = tmp_path / "spmm_win.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), "-S", "--cuda-device-only", "-w",
-                           "-o", str(out), src])
+    csrc_build.device_asm("spmm_win.hip", out)
     text = out.read_text()
     kernels = re.findall(r"^(_ZN[^\n:]*k_spmm_wide[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M)
     # production instances: MODE = 0 (the second template argument of k_spmm_wide); the accounting instance feeds nobody

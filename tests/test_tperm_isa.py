@@ -7,22 +7,18 @@ and the 16 waves of the 1024-thread workgroup must fit one CU: 128 VGPRs, at mos
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from muon_amd.csrc import build as csrc_build
 
 
 def test_tperm_isa_keeps_out_of_the_asm_owned_registers(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "muon_amd", "csrc", "tperm.hip")
     out = tmp_path / "tperm.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "muon_amd", "csrc"), "-S", "--cuda-device-only", "-w",
-                           "-o", str(out), src])
+    csrc_build.device_asm("tperm.hip", out)
     text = out.read_text()
     assert "k_t4_fill" not in text
     kernels = re.findall(r"^(_ZN[^\n:]*k_tperm_move[^\n:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M)
