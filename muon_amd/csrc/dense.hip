@@ -352,7 +352,9 @@ __global__ __launch_bounds__(kCholT) void k_chol_rinv(int B, int w, const double
     dmax = g > dmax ? g : dmax;
   }
   const double tiny = dmax > 0.0 ? dmax * 1e-13 : 1.0;
-  const double pad = dmax > 0.0 ? dmax : 1.0;  // rows past w: a diagonal that passes the pivot test
+  // rows past w: a diagonal that passes the pivot test (also where there is no positive diagonal to take it from -
+  // w = 0 has no pivot of its own and must not raise the flag)
+  const double pad = dmax > 0.0 ? dmax : 2.0;
   for (int e = t; e < 64 * 64; e += kCholT) {
     const int i = e >> 6, j = e & 63;
     A[i][j] = (i < w && j < w) ? (j <= i ? G[(int64_t)i * B + j] : 0.0) : (i == j ? pad : 0.0);
