@@ -341,6 +341,28 @@ int mu_tperm_fill_phases(int64_t n_rows, int64_t n_cols, int64_t nnz, const int6
                          const int64_t* d_x_row_dst, const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt,
                          const int64_t* d_tile_off, const int32_t* d_tiles, const uint32_t* d_cont,
                          const uint16_t* d_slots, void* d_ent, unsigned long long* d_phases, void* stream);
+/* The same fill with a FLAT READ-IN (csrc/tflat.hip; tune "tperm_flat" = 1 in the Python layer): the plan also records how
+ * many pairs of every row fall into every tile, and lane i of a wave reads the wave's pair i of the tile - no windows.
+ * Same bytes in d_ent as mu_tperm_fill and mu_tpack4_fill_stream.  Its tile rule is its own: a tile ends at the widest
+ * column bound (<= tile_cols) at which every wave's pairs are <= 64 mu_tflat_rounds() and the block's pairs are
+ * <= mu_tperm_stage_pairs(); otherwise the width is halved (a multiple of 16, at least 16).
+ *   mu_tflat_plan: the two passes of mu_tperm_plan.  The record pass writes d_counts[512 T] instead of d_cont -
+ *     d_counts[(tile * 16 + wave) * 32 + l] = pairs of row l of the wave in the tile, uint16 - and d_slots[nnz] for ITS
+ *     tiles.  d_err (int32[1], zeroed by the caller) is set to 1 by either pass if a row is not canonical (a count
+ *     past the tile's width): the plan must then be dropped.
+ *   mu_tflat_fill / mu_tflat_fill_phases: as mu_tperm_fill / mu_tperm_fill_phases with d_counts for d_cont; d_x_ent needs
+ *     no alignment beyond its pairs'.  Phase [3] is the scan of the counts, the row search and the issue of the loads. */
+int mu_tflat_rounds(void);
+int mu_tflat_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int32_t* d_indices,
+                  const int64_t* d_x_row_dst, int tile_cols, const int64_t* d_tile_off, int32_t* d_ntile,
+                  int32_t* d_tiles, uint16_t* d_counts, uint16_t* d_slots, int* d_err, void* stream);
+int mu_tflat_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr, const int64_t* d_x_row_dst,
+                  const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt, const int64_t* d_tile_off,
+                  const int32_t* d_tiles, const uint16_t* d_counts, const uint16_t* d_slots, void* d_ent, void* stream);
+int mu_tflat_fill_phases(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
+                         const int64_t* d_x_row_dst, const void* d_x_ent, const int64_t* d_cdst, const void* d_cnt,
+                         const int64_t* d_tile_off, const int32_t* d_tiles, const uint16_t* d_counts,
+                         const uint16_t* d_slots, void* d_ent, unsigned long long* d_phases, void* stream);
 int mu_csr_stream_len(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr, int64_t* d_len,
                       void* stream);
 int mu_csr_stream_fill(int64_t n_pos, const int32_t* d_perm, const int64_t* d_indptr,

@@ -924,7 +924,13 @@ class HipBackend(OperatorSet):
         xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
         tp = self._tperm_of(X, cached, xs_ent, xs_dst) if (cached is not None and src is not None) else None
         with self._dev_ctx():
-            if tp is not None:
+            if tp is not None and "counts" in tp:
+                # (the same with the rows' counts per tile in the plan: the flat read-in, csrc/tflat.hip)
+                cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
+                check(self.lib.mu_tflat_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
+                                             _p(tp["toff"]), _p(tp["tiles"]), _p(tp["counts"]), _p(tp["slots"]), _p(ent),
+                                             self._stream()))
+            elif tp is not None:
                 # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
                 cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
                 check(self.lib.mu_tperm_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
@@ -939,26 +945,46 @@ class HipBackend(OperatorSet):
                             self._t4_prefix(plan["work"], n, d, X.nnz), err)
 
     def _tperm_of(self, X: DeviceCSR, plan, xs_ent, xs_dst):
-        """The slot table of the table-driven fill (csrc/tperm.hip) for X's row stream as `xplan` lays it out, or None
-        (tune tperm_off = 1, a stream laid out otherwise, phase accounting asked for, no memory for the table: the fill of
-        csrc/tpack4.hip).  ``plan``: X's cached `tplan`.  Made with the FIRST fill that can use it and kept on the
-        transposition plan: it costs 2 bytes per stored entry, which only lsi's operand building gets back - a TF-IDF-only
-        caller never pays for it."""
-        import ctypes as C
-
+        """The table of the table-driven fill for X's row stream as `xplan` lays it out, or None (tune tperm_off = 1, a
+        stream laid out otherwise, phase accounting asked for, no memory for the table: the fill of csrc/tpack4.hip).
+        ``plan``: X's cached `tplan`; the table is its "tperm" entry.  Tune tperm_flat = 1 asks for the table of the flat
+        read-in (csrc/tflat.hip: its own tiles, the rows' counts per tile, the slots; no continuation words); 0, or a flat
+        table that cannot be made, for that of the windowed read-in (csrc/tperm.hip).  Made with the FIRST fill that can
+        use it and kept on the transposition plan: it costs 2 bytes per stored entry, which only lsi's operand building
+        gets back - a TF-IDF-only caller never pays for it."""
         lib = self.lib
-        if plan.get("tperm") is False:  # (no memory for the table when it was tried: the old fill from then on)
+        got = plan.get("tperm")
+        if got is False:  # (no memory for the table when it was tried: the old fill from then on)
             return None
         xplan = self._plan_of(X, "xplan")
         if (lib.mu_tune_get(b"tperm_off") == 1 or lib.mu_tune_get(b"tpack_dbg") > 0 or xplan is None
-                or xs_dst is not xplan["row_dst"] or xs_ent.data_ptr() % 256 != 0):
+                or xs_dst is not xplan["row_dst"]):
             return None
-        n, d = X.shape
-        got = plan.get("tperm")
-        # (the widest tile follows the tune keys of t4_geometry: a table recorded under other keys is made again)
-        keys = (lib.mu_tune_get(b"tpack4_c"), lib.mu_tune_get(b"tpack4_m"))
+        flat = lib.mu_tune_get(b"tperm_flat") == 1
+        # (the widest tile follows the tune keys of t4_geometry, the table's kind tperm_flat: a table recorded under other
+        #  keys is made again)
+        keys = (lib.mu_tune_get(b"tpack4_c"), lib.mu_tune_get(b"tpack4_m"), flat)
         if got is not None and got["keys"] == keys:
-            return got
+            return got if ("counts" in got or xs_ent.data_ptr() % 256 == 0) else None
+        got = self._tperm_table(X, plan, xs_dst, True) if flat else None
+        if got is None:
+            if xs_ent.data_ptr() % 256 != 0:  # (the windows of csrc/tperm.hip are 256-byte blocks of the stream)
+                return None
+            got = self._tperm_table(X, plan, xs_dst, False)
+        if got is None:
+            plan["tperm"] = False
+            return None
+        plan["tperm"] = dict(got, keys=keys)
+        return plan["tperm"]
+
+    def _tperm_table(self, X: DeviceCSR, plan, xs_dst, flat):
+        """The arrays of mu_tflat_plan (``flat``: tiles, counts per (tile, row), slots) or of mu_tperm_plan (tiles,
+        continuation rows, slots), or None when they cannot be made: no memory, a refused launch, a row that is not
+        canonical."""
+        import ctypes as C
+
+        lib = self.lib
+        n, d = X.shape
         rpb, G, Ct = C.c_int64(0), C.c_int(0), C.c_int(0)
         check(lib.mu_tpack4_geometry(n, d, X.nnz, C.byref(rpb), C.byref(G), C.byref(Ct)))
         G, Ct = int(G.value), min(int(Ct.value), 512)
@@ -966,23 +992,33 @@ class HipBackend(OperatorSet):
             with self._dev_ctx():
                 st = self._stream()
                 ntile = self.empty((G,), torch.int32)
-                check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
-                                        None, st))
+                if flat:
+                    err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+                    check(lib.mu_tflat_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
+                                            None, _p(err), st))
+                else:
+                    check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
+                                            None, st))
                 toff = torch.zeros((G + 1,), dtype=torch.int64, device=self.device)
                 toff[1:] = torch.cumsum(ntile.long(), 0)
                 T = int(toff[-1].item())
                 tiles = self.empty((T + G,), torch.int32)
-                cont = self.empty((16 * T,), torch.int32)
                 slots = self.empty((X.nnz,), torch.int16)
-                check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
-                                        _p(tiles), _p(cont), _p(slots), st))
+                if flat:
+                    side = dict(counts=self.empty((512 * T,), torch.int16))
+                    check(lib.mu_tflat_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
+                                            _p(tiles), _p(side["counts"]), _p(slots), _p(err), st))
+                    if int(err.item()) != 0:
+                        raise RuntimeError("mu_tflat_plan: a row is not canonical")
+                else:
+                    side = dict(cont=self.empty((16 * T,), torch.int32))
+                    check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
+                                            _p(tiles), _p(side["cont"]), _p(slots), st))
                 inv = plan["inv"]
                 cdst = (plan["sptr"][inv.long()] if inv is not None else plan["sptr"][:d]).contiguous()
         except (RuntimeError, MemoryError):  # (torch's out-of-memory errors and a refused launch are RuntimeErrors)
-            plan["tperm"] = False
             return None
-        plan["tperm"] = dict(keys=keys, tile_cols=Ct, toff=toff, tiles=tiles, cont=cont, slots=slots, cdst=cdst, n_tiles=T)
-        return plan["tperm"]
+        return dict(tile_cols=Ct, toff=toff, tiles=tiles, slots=slots, cdst=cdst, n_tiles=T, **side)
 
     def _t4_geometry(self, n, d, nnz):
         import ctypes as C

@@ -31,7 +31,7 @@ class OperatorSet:
     csr_qc = csr_submatrix = None
     # fragment tools (fragments.hip)
     frag_ranges = frag_overlap = frag_pileup = frag_pileup_scan = frag_length_classes = None
-    # transposition and row streams (transpose.hip, tpack4.hip, tperm.hip, spmm_win.hip); behind can_stream: stream,
+    # transposition and row streams (transpose.hip, tpack4.hip, tperm.hip, tflat.hip, spmm_win.hip); behind can_stream: stream,
     # transpose_stream, stream_both and the status of the tile-staged fill
     transpose_csr = can_stream = stream = transpose_stream = stream_both = split_streams = None
     raise_tpack4 = tpack4_status = launch_layout = spmm_slab = None

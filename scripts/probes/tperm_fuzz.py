@@ -96,7 +96,7 @@ for it in range(cases):
     done += 1
     with_table += 1
     multi_row += rpb > 16
-    with_cont += bool((table["cont"] != 0xffff).any())
+    with_cont += "cont" in table and bool((table["cont"] != 0xffff).any())  # (the flat read-in has no such words)
 print(f"seed {seed}: {done} random cases, all through the table path ({with_table}), {multi_row} with more than one row per "
       f"wave, {with_cont} with continuation windows: the table-driven fill writes the old fill's ent / sptr / perm "
       f"(and scipy's transpose on the rows compared)")

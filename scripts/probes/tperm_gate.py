@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """The table-driven fill (csrc/tperm.hip) against the fill of csrc/tpack4.hip (tune tperm_off = 1) on the bench's matrix,
 one process: cost of the plan + first fill, tiles of the schedule, equality of the two streams, and six fills of each
-kernel, twice, interleaved (torch events around the call).  Writes one JSON line (profiles/r07_tperm_gate.json).
+kernel, twice, interleaved (torch events around the call).  Then the same for the flat read-in (csrc/tflat.hip, tune
+tperm_flat = 1) against the table-driven fill: its plan, its tiles, equality, and seven fills of each, the first dropped,
+twice, interleaved.  Writes one JSON line (profiles/r07_tperm_gate.json, profiles/r10_tflat_gate_*.json).
 Usage: tperm_gate.py [cells] [out.json]"""
 import json
 import os
@@ -22,6 +24,7 @@ with hip._dev_ctx():
                                      _p(xs.sptr), _p(xs.ent), hip._stream()))
 torch.cuda.synchronize()
 out = {"n": n, "nnz": int(X.nnz)}
+hip.tune("tperm_flat", 0)  # (the first half is the windowed read-in against csrc/tpack4.hip, as in r07)
 t0 = time.perf_counter()
 new = hip.transpose_stream(X, src=(xs, row_dst))
 torch.cuda.synchronize()
@@ -39,10 +42,11 @@ out["equal"] = bool(torch.equal(old.ent[:X.nnz], new.ent[:X.nnz]) and torch.equa
 del old, new
 
 
-def timeit(off):
+def timeit(off, flat=0, fills=6):  # (flat = 0: the windowed read-in, what "new" meant when this probe was written)
     hip.tune("tperm_off", off)
+    hip.tune("tperm_flat", flat)
     ts = []
-    for _ in range(6):
+    for _ in range(fills):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         r = hip.transpose_stream(X, src=(xs, row_dst))
@@ -55,6 +59,31 @@ def timeit(off):
 
 out["old_ms"], out["new_ms"], out["old_ms_again"], out["new_ms_again"] = timeit(1), timeit(0), timeit(1), timeit(0)
 hip.tune("tperm_off", 0)
+torch.cuda.empty_cache()
+# the flat read-in: plan + first fill, its schedule, the same bytes, seven fills of each kernel (the first dropped)
+hip.tune("tperm_flat", 1)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+flat = hip.transpose_stream(X, src=(xs, row_dst))
+torch.cuda.synchronize()
+out["flat_first_fill_with_plan_s"] = time.perf_counter() - t0
+tf = hip._plan_of(X, "tplan")["tperm"]
+out["flat_tiles"], out["flat_rounds"] = tf["n_tiles"], int(hip.lib.mu_tflat_rounds())
+widths = torch.diff(tf["tiles"].long())
+widths = widths[widths > 0]
+out["flat_tile_width_min_mean_max"] = [int(widths.min()), float(widths.float().mean()), int(widths.max())]
+wave_tot = tf["counts"].view(-1, 32).long().sum(1)
+out["flat_wave_total_mean_max"] = [float(wave_tot.float().mean()), int(wave_tot.max())]
+hip.tune("tperm_flat", 0)
+win = hip.transpose_stream(X, src=(xs, row_dst))
+torch.cuda.synchronize()
+out["flat_equal"] = bool(torch.equal(win.ent[:X.nnz], flat.ent[:X.nnz]) and torch.equal(win.sptr, flat.sptr)
+                         and torch.equal(win.perm, flat.perm))
+del win, flat, wave_tot, widths
+torch.cuda.empty_cache()
+for name, key in (("win_ms7", 0), ("flat_ms7", 1), ("win_ms7_again", 0), ("flat_ms7_again", 1)):
+    out[name] = timeit(0, key, 7)[1:]
+hip.tune("tperm_flat", 1)
 print(json.dumps(out))
 if len(sys.argv) > 2:
     with open(sys.argv[2], "w") as f:
