@@ -899,6 +899,27 @@ int mu_umap_epoch_f64(int64_t n, int64_t nnz, const int64_t* d_indptr, const int
                       int n_components, int epoch, int n_epochs, int rate, double a, double b, double gamma,
                       double alpha_e, uint64_t seed, const double* d_Y_in, double* d_Y_out, void* stream);
 
+/* ---- muon.atac.pp.scopen: one coordinate-descent sweep of bounded NMF over the rows of a factor
+ * (/root/reference/muon/_atac/preproc.py:155-236 hands the arithmetic to scOpen's MF module, scikit-learn's
+ * _update_cdnmf_fast; csrc/nmf.hip, C-ABI v810) -------------------------------------------------------------
+ * All f64, row-major.  Per row i, for t = 0 .. k-1 in order:  b = d_B[i,t] (* d_bscale[i]) (- l1 when l1 != 0);
+ * grad = -b, then grad = grad + d_G[t,r] * W[i,r] for r = 0 .. k-1 ascending (product and sum two roundings, the row's
+ * already-updated entries);  pg = W[i,t] == 0 ? min(0, grad) : grad;  v_i += |pg|;  if d_G[t,t] != 0:
+ * W[i,t] = max(W[i,t] - grad / d_G[t,t], 0).  The updated d_W is bit-equal to that statement.
+ *   d_W [rows x ldw] in / out and d_B [rows x ldb]: columns >= k are neither read nor written.  d_G [k x k] (an l2 term
+ *   already on its diagonal).  d_Wout (optional) [rows x ldo]: d_oscale[i] * Wnew[i,t] (d_oscale NULL: a copy), columns
+ *   k .. ldo-1 written as zero.  d_gram [k x k] = Wnew^T Wnew, d_viol [1] = sum of the v_i.
+ * No float atomics: every workgroup (one wave, 64-row tiles walked grid-stride) leaves its partial sums in its slot of
+ * d_work (mu_nmf_cd_worksize bytes) and a second kernel adds the slots in slot order - two calls agree bit for bit.  The
+ * grid is min(ceil(rows / 64), max_blocks) workgroups (max_blocks 0: 512).  1 <= k <= mu_nmf_max_components() = 64;
+ * rows = 0 gives zeros.  Arguments are checked before any HIP call. */
+int mu_nmf_max_components(void);
+size_t mu_nmf_cd_worksize(int64_t rows, int k, int max_blocks);
+int mu_nmf_cd_sweep_f64(int64_t rows, int k, double* d_W, int64_t ldw, const double* d_B, int64_t ldb,
+                        const double* d_bscale, const double* d_G, double l1, const double* d_oscale, double* d_Wout,
+                        int64_t ldo, double* d_gram, double* d_viol, void* d_work, size_t work_bytes, int max_blocks,
+                        void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -20,6 +20,9 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.atac.tl.scan_sequences  <->  muon.atac.tl.scan_sequences  (every window of every peak sequence against a
                              bank of position weight matrices on the f64 matrix cores; atac.tl.get_sequences reads the FASTA)
 
+    muon_amd.atac.pp.scopen  <->  muon.atac.pp.scopen  (bounded NMF imputation of the peak matrix: it stays CSR, one fused
+                             coordinate-descent sweep per half-iteration; atac.pp.binarize alike)
+
     muon_amd.tl.leiden / muon_amd.tl.louvain  <->  muon.tl.leiden / muon.tl.louvain  (multiplex clustering over the
                              modalities' graphs: a wave per vertex groups its neighbours' communities in an LDS table)
     muon_amd.tl.umap         <->  muon.tl.umap        (the layout of the multimodal neighbourhood graph: a Jacobi epoch

@@ -633,3 +633,6 @@ def binarize(data, *, backend=None):
     else:
         # dense input is a toy-size branch in the reference too (:151-152)
         adata.X[adata.X != 0] = 1
+
+
+from .scopen import scopen  # noqa: E402,F401  (atac.pp.scopen resolves here, like the reference's; it imports from this module)

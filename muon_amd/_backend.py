@@ -1660,6 +1660,41 @@ class HipBackend(OperatorSet):
                                             _p(work), wb, int(max_blocks), self._stream()))
         return A, gp
 
+    # -- muon.atac.pp.scopen (csrc/nmf.hip) ----------------------------------------------------------------------------
+    def nmf_max_components(self) -> int:
+        """The most components the fused coordinate-descent sweep takes (more: the tensor formulation)."""
+        return int(self.lib.mu_nmf_max_components())
+
+    def nmf_cd_sweep(self, W, B, G, *, bscale=None, l1: float = 0.0, oscale=None, out=None, max_blocks: int = 0):
+        """One coordinate-descent sweep of bounded NMF over the rows of ``W`` (include/muon_amd.h), IN PLACE: k = G's
+        size, W [rows, >= k] and B [rows, >= k] f64 with unit column stride (columns past k are left alone), G [k, k]
+        with the l2 term on its diagonal; the right-hand side of row i is ``B[i] * bscale[i] - l1``.  ``out`` [rows, >= k]
+        receives ``oscale[i] * W[i]`` (``oscale`` None: a copy), its columns past k zero.  Returns (gram = W^T W of the
+        updated factor [k, k], viol = the sum of |projected gradient| [1]).  Two calls with the same arguments agree bit
+        for bit."""
+        k, rows = int(G.shape[0]), int(W.shape[0])
+        f64 = torch.float64
+        assert W.dtype == f64 and B.dtype == f64 and G.dtype == f64 and tuple(G.shape) == (k, k) and G.is_contiguous()
+        assert W.dim() == 2 and B.dim() == 2 and int(B.shape[0]) == rows
+        assert (W.shape[1] == 0 or W.stride(1) == 1) and (B.shape[1] == 0 or B.stride(1) == 1)
+
+        def ld(t):  # (a view narrower than k: the library refuses it by its leading dimension)
+            return int(t.stride(0)) if rows > 1 and int(t.shape[1]) >= k else int(t.shape[1])
+
+        for v in (bscale, oscale):
+            assert v is None or (v.dtype == f64 and tuple(v.shape) == (rows,) and v.is_contiguous())
+        if out is not None:
+            assert out.dtype == f64 and out.dim() == 2 and int(out.shape[0]) == rows and out.is_contiguous()
+        assert oscale is None or out is not None
+        gram, viol = self.empty((k, k), f64), self.empty((1,), f64)
+        wb = int(self.lib.mu_nmf_cd_worksize(rows, k, int(max_blocks))) if 1 <= k <= self.nmf_max_components() else 0
+        work = self.empty((max(wb, 8),), torch.uint8)
+        with self._dev_ctx():
+            check(self.lib.mu_nmf_cd_sweep_f64(rows, k, _p(W), ld(W), _p(B), ld(B), _p(bscale), _p(G), float(l1),
+                                               _p(oscale), _p(out), 0 if out is None else int(out.shape[1]), _p(gram),
+                                               _p(viol), _p(work), wb, int(max_blocks), self._stream()))
+        return gram, viol
+
     # -- muon.tl.snf (csrc/snf.hip) ----------------------------------------------------------------------------------
     def free_memory(self) -> int:
         """Bytes the device can still hand out: what the driver reports free plus what torch's allocator holds unused."""

@@ -64,6 +64,8 @@ class OperatorSet:
     cluster_max_table = cluster_max_layers = cluster_move = cluster_segsum = None
     # muon.tl.umap (umap.hip)
     umap_max_components = umap_epoch = None
+    # muon.atac.pp.scopen (nmf.hip)
+    nmf_max_components = nmf_cd_sweep = None
     # muon.atac.tl.scan_sequences (motif.hip): behind motif_scan
     motif_max_len = motif_tile = motif_group = motif_room = motif_scan = None
     # synthetic counts of the benchmark and the tests (synth.hip)
