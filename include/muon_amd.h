@@ -350,6 +350,11 @@ int mu_tperm_fill_phases(int64_t n_rows, int64_t n_cols, int64_t nnz, const int6
  *     d_counts[(tile * 16 + wave) * 32 + l] = pairs of row l of the wave in the tile, uint16 - and d_slots[nnz] for ITS
  *     tiles.  d_err (int32[1], zeroed by the caller) is set to 1 by either pass if a row is not canonical (a count
  *     past the tile's width): the plan must then be dropped.
+ *     d_slots is laid out in the order the fill READS it, not by stream position: a wave's rows are consecutive CSR
+ *     rows, and the CSR range [d_indptr[first row of the wave], ...) holds the wave's slots tile after tile; inside a
+ *     tile, slot number P_r + k belongs to pair k of row r's pairs in the tile (P_r: the exclusive prefix of the
+ *     tile's counts over the wave's rows), so lane l reads slot 64 u + l in round u.  The slot VALUES are those of
+ *     mu_tperm_plan's.  d_x_row_dst is not read by either pass (it may be NULL); the fill needs it and d_indptr.
  *   mu_tflat_fill / mu_tflat_fill_phases: as mu_tperm_fill / mu_tperm_fill_phases with d_counts for d_cont; d_x_ent needs
  *     no alignment beyond its pairs'.  Phase [3] is the scan of the counts, the row search and the issue of the loads. */
 int mu_tflat_rounds(void);

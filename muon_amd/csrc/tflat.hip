@@ -7,7 +7,10 @@
 // each.  The per-step kernel `k_tflat_move` then reads a tile as the write-out writes it: lanes 0 .. 31 of a wave hold
 // their row's cursor and its count, a scan gives the prefixes P_r and the wave's total T, and in round u lane l takes
 // the wave's pair i = 64 u + l < T - the pair i - P_r of row r, r the last row with P_r <= i (five steps through a
-// 32-word table in the LDS) - with ONE full-wave load of the pair and one of its staging slot.  Everything else is
+// 32-word table in the LDS) - with ONE full-wave load of the pair and one of its staging slot.  The slots lie in that
+// read order: a wave's rows are consecutive CSR rows, the CSR range of its entries holds its slots tile after tile, and
+// slot i of a tile is pair i's - a round's slot load is 64 consecutive 16-bit words from a wave-uniform pointer, it
+// needs no row search, and no line of the table is read in two tiles.  Everything else is
 // `k_tperm_move`'s: the row blocks, the tile schedule array, the two staging buffers, dcol / wsum, the header a tile ahead,
 // one barrier per tile, the flat write-out, the same bytes out.
 //
@@ -38,11 +41,13 @@ static_assert(kR >= 8&& 16 * kRows <= kWaveCap && 16 * kNW * kRows <= kCap, "the
 // drops the plan; the step kernel checks nothing.
 // REC = false: counts the tiles of every row block (ntile); REC = true: the same schedule again, written down together
 // with the counts and the slots.  A wave owns the same rw rows as in the fill (lane l < 32 = row l of the wave).
+// A slot's VALUE is the pair's place in the staging buffer, the tile's pairs in (column, cell) order; its PLACE in
+// `slots` is indptr[first row of the wave] + the wave's pairs in the block's earlier tiles + P_r + k for the k-th pair
+// of row r in the tile (tests/test_tflat_slots_host.py restates both in numpy and fills with them).
 template <bool REC>
 __global__ __launch_bounds__(kT) void k_tflat_plan(int64_t n_rows, int64_t n_cols, int Cmax, int rw,
                                                    const int64_t* __restrict__ indptr,
                                                    const int32_t* __restrict__ indices,
-                                                   const int64_t* __restrict__ row_dst,
                                                    const int64_t* __restrict__ toff, int32_t* __restrict__ ntile,
                                                    int32_t* __restrict__ tiles, uint16_t* __restrict__ counts,
                                                    uint16_t* __restrict__ slots, int* __restrict__ err) {
@@ -59,7 +64,10 @@ __global__ __launch_bounds__(kT) void k_tflat_plan(int64_t n_rows, int64_t n_col
   const bool active = lane < 32 && sub < rw && row < r1;
   int64_t cur = active ? indptr[row] : 0;
   const int64_t end = active ? indptr[row + 1] : 0;
-  const int64_t dst0 = (REC && active) ? row_dst[row] - cur : 0;  // slot index of CSR position q: dst0 + q
+  // where the wave's slots of the next tile start: its rows are consecutive CSR rows, so its entries are one CSR range,
+  // and the slots lie in it tile after tile in the order the fill's lanes read them (a wave without rows never has one)
+  const int64_t wrow = r0 + (int64_t)wave * rw;
+  int64_t sl = REC ? indptr[wrow < r1 ? wrow : r1] : 0;
   if (REC)
     for (int t = tid; t < kNW * kMaxC; t += kT) (&bm[0][0])[t] = 0u;
   const int64_t tb = REC ? toff[g] + g : 0, tc = REC ? toff[g] : 0;
@@ -107,6 +115,15 @@ __global__ __launch_bounds__(kT) void k_tflat_plan(int64_t n_rows, int64_t n_col
     if (REC) {
       if (tid == 0) tiles[tb + t] = (int32_t)cb;
       if (lane < 32) counts[((tc + t) * kNW + wave) * kRows + sub] = (uint16_t)n;
+      // the wave's pair P_r + k of the tile is the k-th of row r's: the prefix the fill's `prepare` makes of the counts
+      int pin = n;  // (a lane >= 32 has no row and no count)
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(pin, off, 64);
+        if (lane >= off) pin += v;
+      }
+      const int64_t sl_r = sl + (pin - n);
+      sl += __builtin_amdgcn_readlane(pin, 63);
       if (total > 0u && total <= (unsigned)kCap) {
         const int W = cend - (int)cb;
         for (int k = 0; k < n; ++k) {
@@ -136,7 +153,7 @@ __global__ __launch_bounds__(kT) void k_tflat_plan(int64_t n_rows, int64_t n_col
         for (int k = 0; k < n; ++k) {
           const int c = indices[cur + k] - (int)cb;
           if (c >= 0 && c < W)
-            slots[dst0 + cur + k] = (uint16_t)(fs[wave][c] + (uint32_t)__popc(bm[wave][c] & ((1u << sub) - 1u)));
+            slots[sl_r + k] = (uint16_t)(fs[wave][c] + (uint32_t)__popc(bm[wave][c] & ((1u << sub) - 1u)));
         }
         __syncthreads();
         if (tid < W)
@@ -205,6 +222,9 @@ __device__ __forceinline__ void tflat_move_body(
   const int64_t tb = tc + g;  // this block's tile boundaries: tiles[tb .. tb + nt]
   const int nt = (int)(uniform64(toff[g + 1]) - tc);
   const uint16_t* cnt_w = counts + (tc * kNW + wave) * kRows + sub;  // this lane's count of tile t: cnt_w[t * 512]
+  // the slots of the wave's pairs of the next tile to request, in the order its lanes take them: wave-uniform, moved on
+  // by the wave's total with every tile (the plan laid them out so, inside the CSR range of the wave's rows)
+  const uint16_t* sl_w = slots + uniform64(indptr[wr0 < r1 ? wr0 : r1]);
 
   // the pairs of a tile in flight: round u, lane l = pair 64 u + l of the wave
   unsigned long long e[kR];  // (column, value bits)
@@ -251,6 +271,12 @@ __device__ __forceinline__ void tflat_move_body(
           i[k] = i[k] < (unsigned)T ? i[k] : (unsigned)T - 1u;  // (idle lanes repeat the wave's last pair)
           r[k] = 0;
         }
+        // (the slots do not wait for the search: a scalar base and the lane's pair number as a 32-bit byte offset, one or
+        //  two lines a round)
+#pragma unroll
+        for (int k = 0; k < kGrp; ++k)
+          if (64 * (u0 + k) < T)
+            s[u0 + k] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(sl_w) + 2u * i[k]);
 #pragma unroll
         for (int st = 16; st > 0; st >>= 1)
 #pragma unroll
@@ -261,13 +287,13 @@ __device__ __forceinline__ void tflat_move_body(
         for (int k = 0; k < kGrp; ++k)
           if (64 * (u0 + k) < T) {
             e[u0 + k] = xent[p[k]];
-            s[u0 + k] = slots[p[k]];
             rr[u0 + k] = r[k];
           }
       }
     });
     wave_lds_sync();
     pos += n;
+    sl_w += T;
   };
   auto count_of = [&](int t) { return (t < nt && lane < 32) ? (int)cnt_w[(int64_t)t * (kNW * kRows)] : 0; };
 
@@ -470,8 +496,9 @@ int mu_tflat_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_
   MU_REQUIRE(mu_tpack4_supported(n_rows, n_cols, nnz), "shape out of range (mu_tpack4_supported)");
   MU_REQUIRE(d_indptr && d_indices && d_err, "null pointer");
   MU_REQUIRE(tile_cols >= 16 && tile_cols <= kMaxC, "tile_cols out of range (16 .. 512)");
-  MU_REQUIRE(d_tile_off ? (d_x_row_dst && d_tiles && d_counts && d_slots) : d_ntile != nullptr,
-             "count pass: d_ntile; record pass: d_x_row_dst, d_tile_off, d_tiles, d_counts, d_slots");
+  MU_REQUIRE(d_tile_off ? (d_tiles && d_counts && d_slots) : d_ntile != nullptr,
+             "count pass: d_ntile; record pass: d_tile_off, d_tiles, d_counts, d_slots");
+  (void)d_x_row_dst;  // (the slots lie in the waves' CSR ranges: no pass reads the stream's layout)
   int64_t rpb = 0;
   int G = 0;
   mu_tpack4_geometry(n_rows, n_cols, nnz, &rpb, &G, nullptr);
@@ -479,10 +506,10 @@ int mu_tflat_plan(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_
   hipStream_t st = (hipStream_t)stream;
   if (d_tile_off)
     hipLaunchKernelGGL((k_tflat_plan<true>), dim3(G), dim3(kT), 0, st, n_rows, n_cols, tile_cols, rw, d_indptr, d_indices,
-                       d_x_row_dst, d_tile_off, d_ntile, d_tiles, d_counts, d_slots, d_err);
+                       d_tile_off, d_ntile, d_tiles, d_counts, d_slots, d_err);
   else
     hipLaunchKernelGGL((k_tflat_plan<false>), dim3(G), dim3(kT), 0, st, n_rows, n_cols, tile_cols, rw, d_indptr,
-                       d_indices, d_x_row_dst, d_tile_off, d_ntile, d_tiles, d_counts, d_slots, d_err);
+                       d_indices, d_tile_off, d_ntile, d_tiles, d_counts, d_slots, d_err);
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
