@@ -925,6 +925,29 @@ int mu_nmf_cd_sweep_f64(int64_t rows, int k, double* d_W, int64_t ldw, const dou
                         int64_t ldo, double* d_gram, double* d_viol, void* d_work, size_t work_bytes, int max_blocks,
                         void* stream);
 
+/* ---- muon_amd.rna.pp / muon_amd.tl.pca: the RNA branch on the device CSR (scanpy's normalize_total, log1p,
+ * highly_variable_genes and pca, the steps with which /root/reference/docs/source/omics opens every RNA modality;
+ * csrc/rna.hip, C-ABI v811) ------------------------------------------------------------------------------
+ *   mu_gene_moments: X^T as a CSR (d rows = genes; only d_indptr and d_values [nnz] are read).  d_sums [4 x d] f64:
+ *     row 0 sum x, row 1 sum x^2, row 2 sum e, row 3 sum e^2 with e = expm1(x * c) (rows 2 and 3 are zero when with_e
+ *     is 0); d_nnz [d]: stored values != 0 (NaN counts, a stored zero does not).  Values are widened to f64 first.  A
+ *     wave per gene, walked grid-stride; lane l adds the entries lo + l, lo + l + 64, ... in that order (squares by fma)
+ *     and the lane sums are combined by a tree over the lane offsets 32, 16, .. 1: no atomics, two calls agree bit for
+ *     bit.  The grid is min(ceil(d / 4), max_blocks) workgroups (max_blocks 0: mu_gene_moments_max_blocks()).
+ *   mu_rna_value_sweep: v = x (/ d_div[row] when d_div is given) (-> log1p(v) when log_flag, then / log_div when
+ *     log_div != 0: log_div = ln(base)), computed in f64 and rounded once to the storage type.  d_out may be d_in.
+ *   mu_shift_cols_f32: Y[i, j] -= (float)d_m[j] for a row-major n x B block, B in {16, 32, 64}: the f32 subtraction
+ *     of the once-rounded mean, bit for bit.  A column with d_m[j] = 0 comes back as it was.
+ *   mu_scale_rows_f32: d_out[i, j] = d_s[i] * d_Q[i, j] (one f32 product) for a row-major d x B block; d_out may be d_Q.
+ * Arguments are checked before any HIP call. */
+int mu_gene_moments_max_blocks(void);
+int mu_gene_moments(int dtype, int64_t d, int64_t nnz, const int64_t* d_indptr, const void* d_values, double c,
+                    int with_e, double* d_sums, int64_t* d_nnz, int max_blocks, void* stream);
+int mu_rna_value_sweep(int dtype, int64_t n, int64_t nnz, const int64_t* d_indptr, const void* d_in, void* d_out,
+                       const double* d_div, int log_flag, double log_div, void* stream);
+int mu_shift_cols_f32(int64_t n, int B, float* d_Y, const double* d_m, void* stream);
+int mu_scale_rows_f32(int64_t d, int B, const float* d_s, const float* d_Q, float* d_out, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

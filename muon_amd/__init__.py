@@ -23,6 +23,10 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.atac.pp.scopen  <->  muon.atac.pp.scopen  (bounded NMF imputation of the peak matrix: it stays CSR, one fused
                              coordinate-descent sweep per half-iteration; atac.pp.binarize alike)
 
+    muon_amd.rna.pp.normalize_total / log1p / highly_variable_genes, muon_amd.tl.pca  <->  scanpy's, the steps with which
+                             the reference's tutorials open every RNA modality: the matrix stays the device CSR, PCA is
+                             lsi's block Lanczos process on the implicitly centred (and scaled) operator
+
     muon_amd.tl.leiden / muon_amd.tl.louvain  <->  muon.tl.leiden / muon.tl.louvain  (multiplex clustering over the
                              modalities' graphs: a wave per vertex groups its neighbours' communities in an LDS table)
     muon_amd.tl.umap         <->  muon.tl.umap        (the layout of the multimodal neighbourhood graph: a Jacobi epoch
@@ -33,6 +37,7 @@ Everything else of muon (I/O, plotting, ...) is out of scope; see DESIGN.md.
 from ._containers import AnnData, MuData  # duck-typed stand-ins when anndata/mudata are absent
 from . import atac  # noqa: F401
 from . import prot  # noqa: F401
+from . import rna  # noqa: F401
 from ._core import tools as tl  # noqa: F401
 from ._core import preproc as pp  # noqa: F401  (mu.pp.neighbors - weighted nearest neighbours -, mu.pp.l2norm,
 #   mu.pp.filter_obs / filter_var on the resident device copy, qc_metrics: the columns they key on)

@@ -491,13 +491,43 @@ def _warm_start(backend, comm, Xcsr, Xt, B, w, seed, start, adaptive, n_obs, nnz
     return Q0, {"cells": n_s, "power_steps": qsteps, "slice": "ranges" if wplan is not None else "operands"}, t4_err
 
 
+class CentredOperand:
+    """What ``_KrylovBasis`` multiplies by instead of X (``muon_amd.tl.pca``): A = (X - 1 mu^T) D^-1,
+    never formed.  A Q = X (D^-1 Q) with its column means taken off (``mean``: the means are those of the f32 image
+    itself, so 1^T Y = 0 up to the rounding of one subtraction and A^T Y = D^-1 X^T Y needs no mean term); ``dinv``
+    (f32 [d], or None for D = I) scales the rows of a d x B block on either side.  One rank only."""
+
+    def __init__(self, n_obs: int, mean: bool = True, dinv=None):
+        self.n_obs, self.mean, self.dinv = int(n_obs), bool(mean), dinv
+
+
+def _shift_cols(be, Y, m):
+    """Y[:, j] -= f32(m[j]) in place (m f64 [B])."""
+    if has(be, "shift_cols"):
+        return be.shift_cols(Y, m)
+    Y -= m.to(torch.float32)
+    return Y
+
+
+def _scale_rows(be, s, Q, out=None):
+    """s[:, None] * Q (s f32 [d]); ``out`` may be Q."""
+    if has(be, "scale_rows"):
+        return be.scale_rows(s, Q, out=out)
+    r = s[:, None] * Q
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
 class _KrylovBasis:
     """The state of ``_lsi_device``'s block Krylov process: the blocks Q_0 .. Q_j (d x B, replicated; w active columns),
     their images Y_i = X Q_i (rows sharded) with their column sums, and T = K^T X^T X K and M = K^T K as w x w f64 host
     blocks (i, j), i <= j.  ``qr_flag`` (the device CholeskyQR's failure flag) or None: B x B factorisations on the host."""
 
-    def __init__(self, backend, comm, Q0, w, qr_flag, t4_err, rsqr):
+    def __init__(self, backend, comm, Q0, w, qr_flag, t4_err, rsqr, operand=None):
         self.backend, self.comm, self.w, self.B = backend, comm, w, Q0.shape[1]
+        self.operand = operand   # a CentredOperand, or None: X itself (lsi)
         self.qr_flag, self.rsqr = qr_flag, rsqr
         self.Qs, self.Ys, self.css, self.Tb, self.Mb = [Q0], [], [], {}, {}
         self.grams = None        # (fetch handle, restart coefficients `through` or None) of the newest block's Grams
@@ -519,9 +549,22 @@ class _KrylovBasis:
         self.pending_g1 = self.t4_err = None
         return be.fetch_async([Gj, cs] + cross + mq + extra + chk), bool(extra), len(Yolds), bool(chk)
 
+    def _image(self, X, Q):
+        """X Q, or A Q of the centred operand: the scaled block through the same product, the image's own column means
+        taken off before anything else reads it.  The column sums are one pass over the n x B block: ``col_moments``
+        where the set has it (half the time of ``gram``, whose B x B product would be thrown away), else ``gram``'s."""
+        op, be = self.operand, self.backend
+        if op is None:
+            return be.spmm(X, Q)
+        Y = be.spmm(X, Q if op.dinv is None else _scale_rows(be, op.dinv, Q))
+        if op.mean:
+            cs = be.col_moments(Y, 0, int(Y.shape[0]))[0] if has(be, "col_moments") else be.gram(Y)[1]
+            _shift_cols(be, Y, cs / float(op.n_obs))
+        return Y
+
     def add_image(self, X):
         """Y_j = X Q_j of the newest block; its Grams against the other blocks set off to the host."""
-        self.Ys.append(self.backend.spmm(X, self.Qs[-1]))
+        self.Ys.append(self._image(X, self.Qs[-1]))
         self.grams = (self._launch(self.Ys[-1], self.Qs[-1], self.Ys[:-1], self.Qs[:-1]), None)
 
     def collect(self):
@@ -622,6 +665,8 @@ class _KrylovBasis:
     def expand_product(self, Xt):
         """Z = X^T Y_j of the newest block, summed over the ranks (rsqr: reduce-scattered, this rank's rows in ``rows``)."""
         Z = self.backend.spmm(Xt, self.Ys[-1])
+        if self.operand is not None and self.operand.dinv is not None:
+            _scale_rows(self.backend, self.operand.dinv, Z, out=Z)  # A^T Y = D^-1 X^T Y: the columns of Y sum to zero
         if self.rsqr:
             self.rows = self.comm.reduce_scatter_rows(Z)
         else:  # (plain all-reduce, or reduce-scatter + all-gather: _comm.py)
@@ -632,7 +677,7 @@ class _KrylovBasis:
         """The half of the next expansion that does not need this step's Ritz pairs (see `pipeline` in the driver): the
         next block from Z, its image and their Grams against the present blocks, under way.  Returns (Q, Y, handle)."""
         Zp = self.next_block(Z, self.project_new(Z))
-        Yn = self.backend.spmm(X, Zp)
+        Yn = self._image(X, Zp)
         return Zp, Yn, self._launch(Yn, Zp, list(self.Ys), list(self.Qs))
 
     def push(self, nxt, through):
@@ -781,7 +826,8 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
                 n_iter: Optional[int] = None, tol: float = 1e-7, angle_tol: float = 3e-5, max_iter: int = 60,
                 oversample: int = DEFAULT_OVERSAMPLE, seed: int = 1, Xt=None, return_info: bool = False,
                 pack: Optional[bool] = None, max_blocks: Optional[int] = None, device_qr: Optional[bool] = None,
-                start: Optional[torch.Tensor] = None, return_basis: bool = False, refine_f64: bool = False):
+                start: Optional[torch.Tensor] = None, return_basis: bool = False, refine_f64: bool = False,
+                operand: Optional[CentredOperand] = None):
     """Truncated SVD of a device-resident CSR (row shard) by block Lanczos on X^T X with full
     reorthogonalisation and Rayleigh-Ritz over the whole block Krylov space.
 
@@ -789,9 +835,15 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
     scaled if asked), stdev numpy f64 [k], V torch f32 [d, k] - torch f64 with ``refine_f64`` (what ``lsi`` asks for when
     the caller's X is f64, like the reference's f64 ARPACK: the f32 process is continued in f64 arithmetic, ``_refine_f64``).  ``n_iter=None`` expands the
     Krylov space until the top-k Ritz subspace has settled (``angle_tol``); ``n_iter=q`` does
-    exactly q expansions.  m blocks cost 2 m - 1 SpMMs."""
+    exactly q expansions.  m blocks cost 2 m - 1 SpMMs.
+
+    ``operand`` (a ``CentredOperand``; ``muon_amd.tl.pca``): the process runs on (X - 1 mu^T) D^-1 instead of X, applied
+    at the three places the basis multiplies by X or X^T; the warm start's slice products stay those of X (they only
+    choose a start block).  One rank, no ``refine_f64``.  Without it nothing here differs from before."""
     comm = default_comm(comm)
     world = getattr(comm, "world_size", 1)
+    if operand is not None and (world > 1 or refine_f64):
+        raise NotImplementedError("a centred operand runs on one rank, in the f32 process")
     n_local, d = X.shape
     if n_obs is None:
         n_obs = int(comm.sum_scalar(n_local))
@@ -883,7 +935,7 @@ def _lsi_device(backend, X, n_comps: int = 50, scale_embeddings: bool = True, n_
     # either way, and its cross Grams are Cw^T applied to the ones computed against the old blocks (`collect`,
     # `through`).  A wrong guess ("not the last step") costs the two products it queued.
     pipeline = device_qr and not big_products and not rsqr and os.environ.get("MUON_AMD_LSI_PIPELINE", "1") != "0"
-    basis = _KrylovBasis(backend, comm, Q0, w, qr_flag, t4_err, rsqr)
+    basis = _KrylovBasis(backend, comm, Q0, w, qr_flag, t4_err, rsqr, operand)
     with phase("lsi/krylov"):
         while True:
             if basis.grams is None:

@@ -1695,6 +1695,64 @@ class HipBackend(OperatorSet):
                                                _p(viol), _p(work), wb, int(max_blocks), self._stream()))
         return gram, viol
 
+    # -- muon_amd.rna.pp / muon_amd.tl.pca (csrc/rna.hip) --------------------------------------------------------------
+    def gene_moments_max_blocks(self) -> int:
+        """The workgroups ``gene_moments`` launches at most when no cap is given."""
+        return int(self.lib.mu_gene_moments_max_blocks())
+
+    def gene_moments(self, Xt: DeviceCSR, c: float = 1.0, with_e: bool = True, max_blocks: int = 0):
+        """``(sums f64 [4, d], nnz int64 [d])`` of the rows of ``Xt`` (X^T as a CSR: one row per gene): sum x, sum x^2,
+        sum e, sum e^2 with e = expm1(x * c) (the last two rows zero without ``with_e``) and the count of stored values
+        that are not zero.  All arithmetic in f64; two calls agree bit for bit (include/muon_amd.h)."""
+        d = int(Xt.shape[0])
+        assert Xt.indptr.dtype == torch.int64 and int(Xt.indptr.numel()) == d + 1 and Xt.indptr.is_contiguous()
+        assert Xt.values.is_contiguous()
+        sums, cnt = self.zeros((4, d), torch.float64), self.empty((d,), torch.int64)
+        with self._dev_ctx():
+            check(self.lib.mu_gene_moments(_dt(Xt.values), d, int(Xt.values.numel()), _p(Xt.indptr), _p(Xt.values),
+                                           float(c), int(bool(with_e)), _p(sums), _p(cnt), int(max_blocks),
+                                           self._stream()))
+        return sums, cnt
+
+    def value_sweep(self, X: DeviceCSR, div=None, log: bool = False, log_div: float = 0.0, out=None):
+        """The stored values of ``X`` through ``x / div[row]`` (``div`` f64 [n] or None), then ``log1p`` when ``log``,
+        then ``/ log_div`` (ln(base); 0: natural): f64 arithmetic, one rounding to the storage type.  ``out`` may be
+        ``X.values`` itself; returns the values tensor written."""
+        n = int(X.shape[0])
+        v = X.values
+        assert X.indptr.dtype == torch.int64 and int(X.indptr.numel()) == n + 1 and X.indptr.is_contiguous()
+        assert v.is_contiguous() and (div is None or (div.dtype == torch.float64 and tuple(div.shape) == (n,)
+                                                      and div.is_contiguous()))
+        if out is None:
+            out = torch.empty_like(v)
+        assert out.dtype == v.dtype and out.shape == v.shape and out.is_contiguous()
+        with self._dev_ctx():
+            check(self.lib.mu_rna_value_sweep(_dt(v), n, int(v.numel()), _p(X.indptr), _p(v), _p(out), _p(div),
+                                              int(bool(log)), float(log_div), self._stream()))
+        return out
+
+    def shift_cols(self, Y: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+        """``Y[:, j] -= float32(m[j])`` IN PLACE: Y [n, B] f32 row-major, B in {16, 32, 64}, m f64 [B]."""
+        n, B = Y.shape
+        assert Y.dtype == torch.float32 and Y.is_contiguous() and Y.data_ptr() % 16 == 0
+        assert m.dtype == torch.float64 and tuple(m.shape) == (B,) and m.is_contiguous()
+        with self._dev_ctx():
+            check(self.lib.mu_shift_cols_f32(int(n), int(B), _p(Y), _p(m), self._stream()))
+        return Y
+
+    def scale_rows(self, s: torch.Tensor, Q: torch.Tensor, out=None) -> torch.Tensor:
+        """``out = s[:, None] * Q`` (one f32 product per element): Q [d, B] f32 row-major, B in {16, 32, 64}, s f32 [d];
+        ``out`` may be ``Q``."""
+        d, B = Q.shape
+        if out is None:
+            out = torch.empty_like(Q)
+        assert Q.dtype == torch.float32 and Q.is_contiguous() and Q.data_ptr() % 16 == 0
+        assert out.dtype == torch.float32 and out.shape == Q.shape and out.is_contiguous() and out.data_ptr() % 16 == 0
+        assert s.dtype == torch.float32 and tuple(s.shape) == (d,) and s.is_contiguous()
+        with self._dev_ctx():
+            check(self.lib.mu_scale_rows_f32(int(d), int(B), _p(s), _p(Q), _p(out), self._stream()))
+        return out
+
     # -- muon.tl.snf (csrc/snf.hip) ----------------------------------------------------------------------------------
     def free_memory(self) -> int:
         """Bytes the device can still hand out: what the driver reports free plus what torch's allocator holds unused."""

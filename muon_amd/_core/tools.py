@@ -33,6 +33,7 @@ from scipy.sparse import csr_matrix, issparse
 
 from .._containers import MuData, is_anndata, is_mudata
 from .ica import ConvergenceWarning, ica  # noqa: F401  (mu.tl.ica: FastICA of an embedding on the device)
+from .pca import pca  # noqa: F401  (scanpy's pca on the device CSR: block Lanczos on the implicitly centred operator)
 from .snf import snf  # noqa: F401  (mu.tl.snf: similarity network fusion on the device)
 from .cluster import leiden, louvain  # noqa: F401  (mu.tl.leiden / mu.tl.louvain: multiplex clustering on the device)
 from .umap import umap  # noqa: F401  (mu.tl.umap: the layout of the multimodal neighbourhood graph on the device)

@@ -1,0 +1,330 @@
+"""``muon_amd.rna.pp``: scanpy's ``normalize_total``, ``log1p`` and ``highly_variable_genes`` on the device CSR.
+
+The reference opens every RNA modality with these steps (/root/reference/docs/source/omics/*.rst) and hands them to
+scanpy; signatures and slots here follow scanpy's.  Parity with scanpy itself is NOT pinned (it is not installed where
+this package is tested): every function is stated below and pinned by an independent restatement in the tests, and
+``highly_variable_genes`` additionally by a hand-computed case.
+
+Where each step runs:
+
+  * a matrix that carries a device copy (``_atac.preproc.attach_device``), or any sparse matrix when ``backend=`` is
+    given: on that backend.  The matrix is uploaded at most once; the result keeps the device copy attached, so
+    ``normalize_total -> log1p -> highly_variable_genes -> tl.pca`` cross PCIe for results only.  The value sweep and the
+    per-gene moments are kernels of csrc/rna.hip (``value_sweep``, ``gene_moments``); an operator set without them (the
+    CPU set of the tests) takes the tensor formulation of the same statements.
+  * a matrix without a device copy and no ``backend=``: numpy / scipy on the host, like ``pp.filter_obs`` - these
+    functions never start using the GPU on their own.  Dense matrices always take this route.
+
+Statements (f64 arithmetic, one rounding to the storage type; integer matrices become float32):
+
+  normalize_total   x <- x / (total_i / target); target_sum=None: the median of the totals > 0; a cell with total 0
+                    keeps its values (divisor 1).
+  log1p             x <- log1p(x) (/ ln(base)); ``uns["log1p"] = {"base": base}``.
+  highly_variable_genes (flavor "seurat")   e = expm1(x ln(base)) (base from ``uns["log1p"]``), mean_j = sum_i e_ij / n,
+                    var_j with ddof = 1 (zeros count); mean == 0 -> 1e-12; disp = var / mean, 0 -> NaN; dispersions =
+                    log(disp), means = log1p(mean); bins = pandas.cut(means, n_bins); per bin mean and std (ddof = 1) of
+                    the non-NaN dispersions, a bin with fewer than two of them gets std = its mean and mean = 0;
+                    dispersions_norm = (dispersions - bin mean) / bin std.  The device computes the per-gene sums, the
+                    binning runs on d-vectors on the host.
+"""
+from __future__ import annotations
+
+from typing import Optional
+from warnings import warn
+
+import numpy as np
+import pandas as pd
+import torch
+from scipy.sparse import csr_matrix, issparse
+
+from .._containers import is_anndata, is_mudata
+from .._operators import has
+
+
+def _modality(data):
+    if is_anndata(data):
+        return data
+    if is_mudata(data) and "rna" in data.mod:
+        return data.mod["rna"]
+    raise TypeError("Expected AnnData or MuData object with 'rna' modality")
+
+
+def _one_rank(comm, what):
+    if comm is not None and getattr(comm, "world_size", 1) > 1:
+        raise NotImplementedError(f"{what} runs on one rank")
+
+
+def _float_csr(m):
+    """A sparse matrix as float CSR (integers -> float32; a float CSR comes back as it is)."""
+    if m.format != "csr":
+        m = m.tocsr()
+    if m.dtype not in (np.float32, np.float64):
+        m = m.astype(np.float32)
+    return m
+
+
+def device_copy(m, backend):
+    """``(host, DeviceCSR, backend)`` for float CSR ``m``.  ``host`` is the CANONICAL host matrix every result is built
+    on - sorted column indices, duplicates summed: ``m`` itself when it is canonical, else a copy (scipy's products and
+    slices hand out unsorted rows; a stored value is only a matrix entry once duplicates are summed, and ``log1p`` /
+    ``expm1`` are not linear).  The device CSR is ``m``'s valid device copy (a resident copy is canonical); else, with a
+    ``backend``, an upload of ``host`` that stays attached to ``m`` when ``host`` is ``m``; else ``(host, None, None)`` -
+    the host route.  The device CSR always has ``host``'s index arrays."""
+    from .._atac.preproc import attach_device, canonical_csr, upload_canonical
+    from .._core.preproc import _resident_copy
+
+    X, be = _resident_copy(m, backend)
+    if X is not None:
+        return m, X, be
+    if backend is None:
+        return canonical_csr(m), None, None
+    host, X = upload_canonical(backend, m)
+    if host is m:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
+        attach_device(m, X, backend)
+    return host, X, backend
+
+
+def _row_of(X):
+    n = X.shape[0]
+    return torch.repeat_interleave(torch.arange(n, device=X.indptr.device), X.indptr[1:] - X.indptr[:-1])
+
+
+def _sweep(be, X, div=None, log=False, log_div=0.0):
+    """New values of device CSR ``X``: x / div[row], then log1p, then / log_div (see the module docstring)."""
+    if has(be, "value_sweep"):
+        return be.value_sweep(X, div=div, log=log, log_div=log_div)
+    v = X.values.to(torch.float64)
+    if div is not None:
+        v = v / div[_row_of(X)]
+    if log:
+        v = torch.log1p(v)
+        if log_div:
+            v = v / log_div
+    return v.to(X.values.dtype)
+
+
+def _sweep_host(m, div=None, log=False, log_div=0.0):
+    v = m.data.astype(np.float64)
+    if div is not None:
+        v = v / np.repeat(div, np.diff(m.indptr))
+    if log:
+        v = np.log1p(v)
+        if log_div:
+            v = v / log_div
+    return v.astype(m.dtype)
+
+
+def _with_values(m, X, be, values):
+    """The host CSR with ``m``'s pattern and the new values; with a device CSR ``X`` the values are a device tensor and
+    the new matrix keeps the device copy."""
+    if X is None:
+        return csr_matrix((values, m.indices.copy(), m.indptr.copy()), shape=m.shape)
+    from .._atac.preproc import attach_device
+
+    new = csr_matrix((be.to_host(values), m.indices.copy(), m.indptr.copy()), shape=m.shape)
+    new.has_sorted_indices = True  # (a resident copy is canonical)
+    attach_device(new, X.with_values(values), be)
+    return new
+
+
+def _get(adata, layer):
+    return adata.X if layer is None else adata.layers[layer]
+
+
+def _put(adata, layer, m):
+    if layer is None:
+        adata.X = m
+    else:
+        adata.layers[layer] = m
+
+
+def normalize_total(data, target_sum: Optional[float] = None, *, exclude_highly_expressed: bool = False,
+                    layer: Optional[str] = None, inplace: bool = True, copy: bool = False,
+                    key_added: Optional[str] = None, comm=None, backend=None):
+    """
+    Normalize counts per cell: every cell's values are divided by ``total / target_sum`` (scanpy's signature).
+
+    ``target_sum=None``: the median of the totals over the cells with a total > 0.  A cell with total 0 is left as it
+    is.  An integer matrix becomes float32.  ``key_added``: the totals go to ``.obs``.  ``inplace=False`` returns
+    ``{"X": ..., "norm_factor": ...}`` and touches nothing; ``copy=True`` works on a copy and returns it.
+    ``exclude_highly_expressed=True`` is not implemented.  See the module docstring for where it runs.
+    """
+    if exclude_highly_expressed:
+        raise NotImplementedError("normalize_total: exclude_highly_expressed=True is not implemented")
+    _one_rank(comm, "rna.pp.normalize_total")
+    adata = _modality(data)
+    if copy:
+        if not inplace:
+            raise ValueError("`copy=True` cannot be used with `inplace=False`.")
+        adata = adata.copy()
+    counts = _get(adata, layer)
+    X = be = None
+    if issparse(counts):
+        m, X, be = device_copy(_float_csr(counts), backend)
+        totals = be.to_host(be.row_col_sums(X)[0]) if X is not None else \
+            np.asarray(m.astype(np.float64).sum(axis=1)).reshape(-1)
+    else:
+        m = np.asarray(counts)
+        if m.dtype not in (np.float32, np.float64):
+            m = m.astype(np.float32)
+        totals = m.sum(axis=1, dtype=np.float64)
+    totals = np.asarray(totals, dtype=np.float64)
+    pos = totals > 0
+    target = float(target_sum) if target_sum is not None else (float(np.median(totals[pos])) if pos.any() else 1.0)
+    div = np.ones_like(totals)
+    div[pos] = totals[pos] / target
+    if X is not None:
+        new = _with_values(m, X, be, _sweep(be, X, div=be.to_device(div, np.float64)))
+    elif issparse(counts):
+        new = _with_values(m, None, None, _sweep_host(m, div=div))
+    else:
+        new = (m.astype(np.float64) / div[:, None]).astype(m.dtype)
+    if not inplace:
+        return {"X": new, "norm_factor": totals}
+    _put(adata, layer, new)
+    if key_added is not None:
+        adata.obs[key_added] = totals
+    return adata if copy else None
+
+
+def log1p(data, *, base: Optional[float] = None, layer: Optional[str] = None, copy: bool = False, comm=None,
+          backend=None):
+    """
+    Logarithmize the data matrix: ``log1p`` of the stored values, divided by ``ln(base)`` if ``base`` is given;
+    ``uns["log1p"] = {"base": base}`` (scanpy's signature).  An integer matrix becomes float32.
+    """
+    _one_rank(comm, "rna.pp.log1p")
+    adata = _modality(data)
+    if copy:
+        adata = adata.copy()
+    counts = _get(adata, layer)
+    log_div = float(np.log(base)) if base is not None else 0.0
+    if issparse(counts):
+        m, X, be = device_copy(_float_csr(counts), backend)
+        vals = _sweep(be, X, log=True, log_div=log_div) if X is not None else _sweep_host(m, log=True, log_div=log_div)
+        new = _with_values(m, X, be, vals)
+    else:
+        m = np.asarray(counts)
+        if m.dtype not in (np.float32, np.float64):
+            m = m.astype(np.float32)
+        v = np.log1p(m.astype(np.float64))
+        new = (v / log_div if log_div else v).astype(m.dtype)
+    _put(adata, layer, new)
+    adata.uns["log1p"] = {"base": base}
+    return adata if copy else None
+
+
+# ---- highly variable genes --------------------------------------------------------------------------------------------
+def gene_moments_device(be, X, c: float = 1.0, with_e: bool = True):
+    """``(sums f64 [4, d], nnz int64 [d])`` of the columns of device CSR ``X`` as host arrays: sum x, sum x^2, sum e,
+    sum e^2 with e = expm1(x c) (zero without ``with_e``) and the count of stored non-zero values.  The kernel walks
+    the CSR of X^T, a wave per gene (csrc/rna.hip); without it the same sums are tensor operations."""
+    d = X.shape[1]
+    if has(be, "gene_moments", "gene_moments_max_blocks"):
+        sums, cnt = be.gene_moments(be.transpose(X), c=c, with_e=with_e)
+    else:
+        v = X.values.to(torch.float64)
+        col = X.indices.long()
+        sums = torch.zeros((4, d), dtype=torch.float64, device=v.device)
+        sums[0].index_add_(0, col, v)
+        sums[1].index_add_(0, col, v * v)
+        if with_e:
+            e = torch.expm1(v * c)
+            sums[2].index_add_(0, col, e)
+            sums[3].index_add_(0, col, e * e)
+        cnt = torch.bincount(col[X.values != 0], minlength=d)
+    return be.to_host(sums), be.to_host(cnt)
+
+
+def _e_sums_host(m, c):
+    """sum e, sum e^2 per column of a host matrix, e = expm1(x c)."""
+    if issparse(m):
+        e = m.astype(np.float64).tocsc()
+        e.data = np.expm1(e.data * c)
+        s1 = np.asarray(e.sum(axis=0)).reshape(-1)
+        e.data = e.data * e.data
+        return s1, np.asarray(e.sum(axis=0)).reshape(-1)
+    e = np.expm1(np.asarray(m, dtype=np.float64) * c)
+    return e.sum(axis=0), (e * e).sum(axis=0)
+
+
+def seurat_dispersions(s1, s2, n, n_bins=20):
+    """``(means, dispersions, dispersions_norm)`` of flavor "seurat" from the per-gene sums of e and e^2 over ``n``
+    cells (the module docstring states every step)."""
+    mean = np.asarray(s1, dtype=np.float64) / n
+    var = (np.asarray(s2, dtype=np.float64) / n - mean ** 2) * (n / (n - 1))
+    mean[mean == 0] = 1e-12
+    disp = var / mean
+    disp[disp == 0] = np.nan
+    with np.errstate(invalid="ignore", divide="ignore"):
+        disp = np.log(disp)
+    mean = np.log1p(mean)
+    df = pd.DataFrame({"means": mean, "dispersions": disp})
+    df["mean_bin"] = pd.cut(df["means"], bins=n_bins)
+    grouped = df.groupby("mean_bin", observed=False)["dispersions"]
+    bin_mean, bin_std = grouped.mean(), grouped.std(ddof=1)
+    single = bin_std.isnull()
+    bin_std[single] = bin_mean[single]
+    bin_mean[single] = 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        norm = (df["dispersions"].values - bin_mean[df["mean_bin"].values].values) / bin_std[df["mean_bin"].values].values
+    return mean, disp, np.asarray(norm, dtype=np.float64)
+
+
+def highly_variable_genes(data, *, n_top_genes: Optional[int] = None, min_mean: float = 0.0125, max_mean: float = 3,
+                          min_disp: float = 0.5, max_disp: float = np.inf, n_bins: int = 20, flavor: str = "seurat",
+                          subset: bool = False, inplace: bool = True, layer: Optional[str] = None, batch_key=None,
+                          comm=None, backend=None):
+    """
+    Annotate highly variable genes, flavor "seurat", on log-normalised data (scanpy's signature; other flavors and
+    ``batch_key`` raise ``NotImplementedError``).
+
+    Writes ``var["highly_variable" | "means" | "dispersions" | "dispersions_norm"]`` and ``uns["hvg"] = {"flavor":
+    "seurat"}``; ``inplace=False`` returns the DataFrame instead.  With ``n_top_genes`` the genes whose normalised
+    dispersion is ``>=`` the n-th largest non-NaN one are selected (all of them, with a warning, when fewer exist);
+    without it ``min_mean < means < max_mean`` and ``min_disp < dispersions_norm < max_disp``; NaN is never selected.
+    ``subset=True`` subsets through ``pp.filter_var``, so a device copy follows.  See the module docstring for the
+    statement and for where it runs.
+    """
+    if flavor != "seurat":
+        raise NotImplementedError(f"highly_variable_genes: flavor {flavor!r} is not implemented (only 'seurat')")
+    if batch_key is not None:
+        raise NotImplementedError("highly_variable_genes: batch_key is not implemented")
+    _one_rank(comm, "rna.pp.highly_variable_genes")
+    adata = _modality(data)
+    counts = _get(adata, layer)
+    n = int(counts.shape[0])
+    base = (adata.uns.get("log1p") or {}).get("base")
+    c = float(np.log(base)) if base is not None else 1.0
+    X = None
+    if issparse(counts):
+        m, X, be = device_copy(_float_csr(counts), backend)
+    if X is not None:
+        sums, _nnz = gene_moments_device(be, X, c=c, with_e=True)
+        s1, s2 = sums[2], sums[3]
+    else:
+        s1, s2 = _e_sums_host(m if issparse(counts) else counts, c)
+    means, disps, norm = seurat_dispersions(s1, s2, n, n_bins)
+
+    if n_top_genes is not None:
+        ok = norm[~np.isnan(norm)]
+        ok[::-1].sort()
+        if n_top_genes > ok.size:
+            warn("`n_top_genes` > number of normalized dispersions, returning all genes with normalized dispersions.")
+            n_top_genes = ok.size
+        hv = (np.nan_to_num(norm, nan=-np.inf) >= ok[n_top_genes - 1]) if n_top_genes > 0 else np.zeros(norm.size, bool)
+    else:
+        with np.errstate(invalid="ignore"):
+            hv = (means > min_mean) & (means < max_mean) & (norm > min_disp) & (norm < max_disp)
+    df = pd.DataFrame({"means": means, "dispersions": disps, "dispersions_norm": norm, "highly_variable": hv},
+                      index=adata.var_names)
+    if not inplace:
+        return df[df["highly_variable"].values] if subset else df
+    adata.uns["hvg"] = {"flavor": "seurat"}
+    for col in ("highly_variable", "means", "dispersions", "dispersions_norm"):
+        adata.var[col] = df[col].values
+    if subset:
+        from .._core.preproc import filter_var
+
+        filter_var(adata, np.asarray(hv, dtype=bool), backend=backend)
+    return None
