@@ -469,17 +469,16 @@ int mu_ell16_fill(int64_t n_groups, int64_t n_cols, int64_t nnz, int slab_cols, 
                   void* d_ent, void* stream);
 
 
-/* Tuning / ablation knobs (tests and bench only; all default to 0 = what ships):
- *   "spmm_k"     row-sets per wave of the packed SpMM (0 = automatic)
- *   "spmm_slab"  Q slab width of the row-stream SpMM the host asks for: 0 decide, 256 / 320 force (320 where it exists)
- *   "spmm_waves" waves per workgroup of the packed SpMM: 16 (default), 12, 8
- *   "spmm_pipe"  software pipelining level of the packed SpMM
- *   "spmm_mode"  timing ablations of the packed SpMM (bit mask; results are then WRONG)
- *   "mfma_mode"  timing ablations of the matrix-core SpMM (1 no MFMA, 2 no gathers, 4 no masks; WRONG results)
- *   "ell_mode"   timing ablations of the sliced-ELL SpMM (1 no gathers / FMAs, 2 no Q slab copies; WRONG results)
- *   "tfidf_wide" 1: the f32 TF-IDF scale sweep with 8192-column idf slabs (r03) instead of 32 768 (same results) */
+/* Tune keys (tests, probes and bench only; process-global; every default is what ships).  The keys, their defaults, largest
+ * accepted values and meanings are declared once, in csrc/common.hpp (MU_TUNE_KEYS); INTEGRATION.md lists them.
+ * mu_tune_set fails on a NULL or unknown key ("unknown key"), a negative value and a value above the key's largest;
+ * mu_tune_get of a NULL or unknown key returns -1.  mu_tune_count / mu_tune_name(i) / mu_tune_default(i) list the table
+ * (host only; i out of range: NULL / -1). */
 int mu_tune_set(const char* key, int value);
 int mu_tune_get(const char* key);
+int mu_tune_count(void);
+const char* mu_tune_name(int i);
+int mu_tune_default(int i);
 
 /* Same product in f64 (MOFA runs in float64 unless use_float32=True, tools.py:308). */
 int mu_spmm_f64(int64_t n_rows, int64_t n_cols, const int64_t* d_indptr, const int32_t* d_indices,

@@ -561,8 +561,7 @@ class HipBackend(OperatorSet):
 
     def can_emit_stream(self, X: DeviceCSR) -> bool:
         """The TF-IDF scale sweep can write the row stream of its result (f32, a shape the stream SpMM takes)."""
-        return (X.values.dtype == torch.float32 and X.nnz > 0 and self.can_stream(X, 64)
-                and self.lib.mu_tune_get(b"scale_stream_off") != 1)
+        return X.values.dtype == torch.float32 and X.nnz > 0 and self.can_stream(X, 64)
 
     def stream_layout(self, X: DeviceCSR, K: Optional[int] = None):
         """Where the rows of X go in its row stream (launch_layout: needs the row LENGTHS only, so it can be made before
@@ -961,9 +960,9 @@ class HipBackend(OperatorSet):
                 or xs_dst is not xplan["row_dst"]):
             return None
         flat = lib.mu_tune_get(b"tperm_flat") == 1
-        # (the widest tile follows the tune keys of t4_geometry, the table's kind tperm_flat: a table recorded under other
+        # (the widest tile follows the tune key of t4_geometry, the table's kind tperm_flat: a table recorded under other
         #  keys is made again)
-        keys = (lib.mu_tune_get(b"tpack4_c"), lib.mu_tune_get(b"tpack4_m"), flat)
+        keys = (lib.mu_tune_get(b"tpack4_c"), flat)
         if got is not None and got["keys"] == keys:
             return got if ("counts" in got or xs_ent.data_ptr() % 256 == 0) else None
         got = self._tperm_table(X, plan, xs_dst, True) if flat else None
@@ -1358,6 +1357,11 @@ class HipBackend(OperatorSet):
 
     def tune(self, key: str, value: int) -> None:
         check(self.lib.mu_tune_set(key.encode(), int(value)))
+
+    def tune_keys(self) -> dict:
+        """{name: default} of the library's tune keys (csrc/common.hpp: MU_TUNE_KEYS)."""
+        lib = self.lib
+        return {lib.mu_tune_name(i).decode(): lib.mu_tune_default(i) for i in range(lib.mu_tune_count())}
 
     def spmm_slab(self, k_layout: int, n_pos: int, B: int, dtype=torch.float32) -> int:
         """The slab width for a product on a row stream dealt for ``k_layout`` row-sets per wave (0: the library picks

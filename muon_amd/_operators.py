@@ -40,7 +40,7 @@ class OperatorSet:
     # sliced-ELL operands of the narrow-block SpMM (spmm_ell.hip)
     ell16 = ell16_pair = spmm_ell = None
     # block orthogonalisation on the device (dense.hip); kernel switches (runtime.hip)
-    chol_rinv = tune = None
+    chol_rinv = tune = tune_keys = None
     # neighbour search and WNN (knn.hip, wnn.hip)
     umap_strengths = wnn_bandwidth = knn_filter = knn_merge = None
     # MOFA+ (mofa.hip, mofa_stats.hip, mofa_elbo.hip, skinny.hip): what MofaEngine needs (mofa_engine.REQUIRED_OPS) ...

@@ -32,6 +32,39 @@ void mu_set_error(const char* fmt, ...);
 
 constexpr int kWave = 64;
 
+// ---- tune keys: THE table (tests, probes and bench only; every default is what ships) -----------------------------
+// X(name, default, largest accepted value, description).  csrc reads a key as tune(kTune_<name>): a key that is not
+// here does not compile.  mu_tune_set / mu_tune_get (csrc/runtime.hip) look the name up in the same table and refuse
+// anything else; INTEGRATION.md lists it, tests/test_tune_keys.py holds the three together.
+constexpr int kTuneAny = 0x7fffffff;
+#define MU_TUNE_KEYS(X)                                                                                              \
+  X(spmm_k, 0, 16, "row-sets per wave of the row-stream SpMM: 0 = the layout's / automatic, 1..8 force")             \
+  X(spmm_mode, 0, kTuneAny, "64: cycle accounting of the row-stream SpMM (K = 8), 6: of the narrow kernel; any other non-zero value has no instance") \
+  X(spmm_slab, 0, 320, "Q slab width the host asks for: 0 = the host's rule, 256 / 320 force (320 where an instance exists)") \
+  X(spmm_narrow_off, 0, 1, "1: B = 16 runs the NB = 1 instance of spmm_win.hip instead of the narrow kernel")        \
+  X(gram_wg, 0, kTuneAny, "workgroups per CU of the Gram kernels: 0 = 2")                                            \
+  X(pack_wg, 0, kTuneAny, "workgroups per CU of the row-stream copy: 0 = 32")                                        \
+  X(stream_pipe, 0, 1, "1: the row-stream copy's plain loop instead of the software-pipelined one")                  \
+  X(tfidf_pipe, 0, 1, "1: the TF-IDF sweeps of r03 (the tests' reference) instead of the software-pipelined ones")   \
+  X(tfidf_sum_m, 0, 2, "f32 sum sweep: 0 = by size, 1: always 8192-column bins, 2: always 16 384-column bins")      \
+  X(nn_interleave, 0, 1, "1: every wave of k_skinny_nn takes a contiguous quarter of the columns (only probes set it)") \
+  X(tpack_dbg, 0, 1, "1: the transposition fills run their phase-accounting instances")                              \
+  X(tpack4_c, 0, kTuneAny, "columns per tile of the transposition: 0 = from the geometry")                           \
+  X(tpack4_plain, 0, 1, "1: workgroup = row block instead of the XCD-aware order (only probes set it)")              \
+  X(tpack4_circ, 0, 2, "2: the stream-source fill without its circular windows")                                     \
+  X(tpack4_off, 0, 1, "1: the host takes mu_csr_transpose + mu_csr_stream_fill instead of the fused transposition")  \
+  X(tperm_off, 0, 1, "1: the fill of tpack4.hip instead of the table-driven one")                                    \
+  X(tperm_flat, 1, 1, "1: the flat read-in of tflat.hip, 0: k_tperm_move")                                           \
+  X(pois_valu, 0, 1, "1: the Poisson sweep on the vector ALU instead of the matrix cores")                           \
+  X(pois_lane, 0, 1, "1: one lane per entry in the sparse Poisson sweep instead of four")
+enum TuneKey {
+#define MU_TUNE_ENUM(name, def, max, doc) kTune_##name,
+  MU_TUNE_KEYS(MU_TUNE_ENUM)
+#undef MU_TUNE_ENUM
+  kTuneCount
+};
+int tune(TuneKey key);  // the key's current value (csrc/runtime.hip)
+
 // number of CUs of the current device (cached per device id)
 int mu_num_cus();
 

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void k_gram_fold(int n_partials, const double*
 static inline int gram_blocks(int64_t n_rows) {
   int64_t groups = (n_rows + 15) / 16;  // one workgroup step = 16 rows
   int64_t blocks = groups < 1 ? 1 : groups;
-  const int per_cu = mu_tune_get("gram_wg") > 0 ? mu_tune_get("gram_wg") : 2;  // (probe: 1, 2, 4, 8 -> 81, 88, 104, 134 us per cross-Gram at 200k rows)
+  const int per_cu = tune(kTune_gram_wg) > 0 ? tune(kTune_gram_wg) : 2;  // (probe: 1, 2, 4, 8 -> 81, 88, 104, 134 us per cross-Gram at 200k rows)
   const int64_t cap = (int64_t)mu_num_cus() * per_cu;
   // (r03: capping small inputs at kGramFold blocks so that the reduction takes the partials directly -
   //  two launches instead of three - made the 30 000-row Grams of a 10k x 30k call slower than the

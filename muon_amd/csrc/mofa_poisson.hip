@@ -586,7 +586,7 @@ int pois_sparse_launch(int mode, int64_t n_own, int K, int ld, const int64_t* in
   hipLaunchKernelGGL((KERNEL<T, KP, MD>), dim3(blocks), dim3(256), 0, st, n_own, K, ld, indptr, indices,             \
                      (const T*)values, (const T*)E_own, (const T*)E_other, (T*)out)
   if constexpr (KP == 12 || KP == 16) {
-    if (mu_tune_get("pois_lane") <= 0) {  // four lanes per entry (k_pois_sparse_quad)
+    if (tune(kTune_pois_lane) <= 0) {  // four lanes per entry (k_pois_sparse_quad)
       if (mode == 0) MU_GO(k_pois_sparse_quad, 0);
       else if (mode == 1) MU_GO(k_pois_sparse_quad, 1);
       else if (mode == 2) MU_GO(k_pois_sparse_quad, 2);
@@ -614,7 +614,7 @@ const void* pois_dense_ptr(int mode) {
   return mode == 0 ? (const void*)k_pois_dense<T, KP, 0> : mode == 1 ? (const void*)k_pois_dense<T, KP, 1>
        : mode == 2 ? (const void*)k_pois_dense<T, KP, 2> : (const void*)k_pois_dense<T, KP, 3>;
 }
-bool pois_use_mfma(int dtype, int K) { return K <= 16 && mu_tune_get("pois_valu") <= 0; }
+bool pois_use_mfma(int dtype, int K) { return K <= 16 && tune(kTune_pois_valu) <= 0; }
 int pois_own_rows(int dtype, int K) {  // own rows of a workgroup of the dense sweep
   return pois_use_mfma(dtype, K) ? 64 * (dtype == MU_DTYPE_F32 ? PmMap<float>::OWN : PmMap<double>::OWN) : kPzThreads;
 }

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void k_skinny_nn(int64_t n_rows, int64_t D, in
 // grid its width; partial blocks are reduced in a fixed order (bit-reproducible).
 constexpr int kCT = 8;
 
-template <typename T, typename TY = T, bool PIPE = false>
+template <typename T, typename TY = T>
 __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64_t D, int64_t ldY,
                                                            const TY* __restrict__ Y,
                                                            const T* __restrict__ Z, int n_splits,
@@ -208,11 +208,10 @@ __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64
     coff[t] = c < D ? c : D - 1;
   }
   const int64_t last_row = n_rows - 1;
-  // PIPE (tune tn_pipe = 1; NOT the default): two steps in flight per wave - the loads of step i + 1 issued before the
-  // MFMAs of step i, two register sets, the loop unrolled by two.  It costs 50 registers (170-182 against 119-128:
-  // two waves per SIMD instead of four) and measured 1-3 % slower on c4 in all three instances.
-  TY xa[kCT], xb[kCT];
-  T za, zb;
+  // (Two steps in flight per wave - the loads of step i + 1 issued before the MFMAs of step i - cost 50 registers,
+  //  170-182 against 119-128: two waves per SIMD instead of four, and measured 1-3 % slower on c4; retired.)
+  TY xa[kCT];
+  T za;
   auto load = [&](TY (&x)[kCT], T& z, int64_t grp) {
     const int64_t row = grp * 4 + lr;
     const bool rk = row < n_rows;
@@ -227,24 +226,9 @@ __global__ __launch_bounds__(256) void k_skinny_tn_partial(int64_t n_rows, int64
 #pragma unroll
     for (int t = 0; t < kCT; ++t) acc[t] = Mfma16x16x4<T>::mfma((T)x[t], z, acc[t]);
   };
-  int64_t grp = g0 + wave;
-  if constexpr (!PIPE) {
-    for (; grp < g1; grp += 4) {
-      load(xa, za, grp);
-      mma(xa, za);
-    }
-  } else if (grp < g1) {
+  for (int64_t grp = g0 + wave; grp < g1; grp += 4) {
     load(xa, za, grp);
-    for (;;) {
-      const int64_t g2 = grp + 4;
-      load(xb, zb, g2 < g1 ? g2 : grp);
-      mma(xa, za);
-      if (g2 >= g1) break;
-      grp = g2 + 4;
-      load(xa, za, grp < g1 ? grp : g2);
-      mma(xb, zb);
-      if (grp >= g1) break;
-    }
+    mma(xa, za);
   }
   // reduce the four waves through LDS in a fixed order
   for (int i = threadIdx.x; i < 16 * kCT * 16; i += 256) red[i] = (T)0;
@@ -311,8 +295,8 @@ int mu_skinny_nn(int dtype, int64_t n_rows, int64_t D, int64_t ldY, const void* 
   const int64_t cap = (int64_t)mu_num_cus() * 8;
   if (blocks > cap) blocks = cap;
   hipStream_t st = (hipStream_t)stream;
-  const int quarters = mu_tune_get("nn_interleave") == 1;
-  const bool fast = nn_fast(d_Y, ldY, D, dtype == MU_DTYPE_F64 ? 8 : 4) && mu_tune_get("nn_fast_off") == 0;
+  const int quarters = tune(kTune_nn_interleave) == 1;
+  const bool fast = nn_fast(d_Y, ldY, D, dtype == MU_DTYPE_F64 ? 8 : 4);
   if (dtype == MU_DTYPE_F64 && fast)
     hipLaunchKernelGGL((k_skinny_nn<double, double, true>), dim3((unsigned)blocks), dim3(256), 0, st, n_rows, D, ldY,
                        (const double*)d_Y, (const double*)d_T, (double*)d_out, quarters);
@@ -337,7 +321,7 @@ int mu_skinny_nn_f64_f32(int64_t n_rows, int64_t D, int64_t ldY, const float* d_
   int64_t blocks = (n_rows + 16 * kSub - 1) / (16 * kSub);
   const int64_t cap = (int64_t)mu_num_cus() * 8;
   if (blocks > cap) blocks = cap;
-  const int quarters = mu_tune_get("nn_interleave") == 1;
+  const int quarters = tune(kTune_nn_interleave) == 1;
   if (nn_fast(d_Y, ldY, D, sizeof(float)))
     hipLaunchKernelGGL((k_skinny_nn<double, float, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_rows,
                        D, ldY, d_Y, d_T, d_out, quarters);
@@ -358,12 +342,8 @@ int mu_skinny_tn_f64_f32(int64_t n_rows, int64_t D, int64_t ldY, const float* d_
   const int64_t cbs = (D + 16 * kCT - 1) / (16 * kCT);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = D * 16;
-  if (mu_tune_get("tn_pipe") == 1)
-    hipLaunchKernelGGL((k_skinny_tn_partial<double, float, true>), dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                       n_rows, D, ldY, d_Y, d_Z, S, (double*)d_work);
-  else
-    hipLaunchKernelGGL((k_skinny_tn_partial<double, float>), dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st, n_rows, D,
-                       ldY, d_Y, d_Z, S, (double*)d_work);
+  hipLaunchKernelGGL((k_skinny_tn_partial<double, float>), dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st, n_rows, D,
+                     ldY, d_Y, d_Z, S, (double*)d_work);
   MU_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_skinny_tn_reduce<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S,
                      (const double*)d_work, d_C);
@@ -382,24 +362,15 @@ int mu_skinny_tn(int dtype, int64_t n_rows, int64_t D, int64_t ldY, const void* 
   const int64_t cbs = (D + 16 * kCT - 1) / (16 * kCT);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = D * 16;
-  const bool piped = mu_tune_get("tn_pipe") == 1;
   if (dtype == MU_DTYPE_F64) {
-    if (piped)
-      hipLaunchKernelGGL((k_skinny_tn_partial<double, double, true>), dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                         n_rows, D, ldY, (const double*)d_Y, (const double*)d_Z, S, (double*)d_work);
-    else
-      hipLaunchKernelGGL(k_skinny_tn_partial<double>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                         n_rows, D, ldY, (const double*)d_Y, (const double*)d_Z, S, (double*)d_work);
+    hipLaunchKernelGGL(k_skinny_tn_partial<double>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
+                       n_rows, D, ldY, (const double*)d_Y, (const double*)d_Z, S, (double*)d_work);
     MU_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_skinny_tn_reduce<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        total, S, (const double*)d_work, (double*)d_C);
   } else {
-    if (piped)
-      hipLaunchKernelGGL((k_skinny_tn_partial<float, float, true>), dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                         n_rows, D, ldY, (const float*)d_Y, (const float*)d_Z, S, (float*)d_work);
-    else
-      hipLaunchKernelGGL(k_skinny_tn_partial<float>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                         n_rows, D, ldY, (const float*)d_Y, (const float*)d_Z, S, (float*)d_work);
+    hipLaunchKernelGGL(k_skinny_tn_partial<float>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
+                       n_rows, D, ldY, (const float*)d_Y, (const float*)d_Z, S, (float*)d_work);
     MU_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_skinny_tn_reduce<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        total, S, (const float*)d_work, (float*)d_C);

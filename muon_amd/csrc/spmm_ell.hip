@@ -96,8 +96,8 @@ __device__ __forceinline__ void e_take(const unsigned char* ahead, unsigned lane
 // order: a wave that issues slab pieces cannot take a window requested after them before the pieces have landed -
 // one full memory latency per slab and wave, at the same moment in all waves (they leave the barrier together).
 // With one wave doing nothing but `issue the next slab, wait, barrier`, the others never wait for anything but
-// their own windows.   MODE (timing ablations, wrong results): 1 no gathers / FMAs, 2 no slab copies.
-template <int MODE, typename DT>
+// their own windows.
+template <typename DT>
 __global__ __launch_bounds__(64 * (kEMaxWaves + 1)) void k_spmm_ell16(int64_t n_pos, int64_t n_cols, int n_slabs, int cw,
                                                                      const int32_t* __restrict__ hdr,
                                                                      const int64_t* __restrict__ wave_base,
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64 * (kEMaxWaves + 1)) void k_spmm_ell16(int64_t n_
     const unsigned q_last = (unsigned)(n_cols * kRowBytes - 16);  // (the last slab is clamped to the end of Q)
     auto whole = [&](int s, int b) {
 #pragma unroll 8
-      for (int piece = 0; piece < ((MODE & 2) ? 1 : kESlabBytes / 1024); ++piece) {
+      for (int piece = 0; piece < kESlabBytes / 1024; ++piece) {
         unsigned o = (unsigned)s * (unsigned)kESlabBytes + (unsigned)(piece * 1024 + lane * 16);
         o = o < q_last ? o : q_last;  // past the end: never consumed
         dma_piece(Q, o, lds0 + (unsigned)b * (unsigned)kESlabBytes + (unsigned)piece * 1024u);
@@ -172,9 +172,7 @@ __global__ __launch_bounds__(64 * (kEMaxWaves + 1)) void k_spmm_ell16(int64_t n_
     float val[4];
     e_take<D>(wp, lane4, lane2, base, adr, val);
     wp += kEWin;
-    if constexpr (MODE & 1) {
-      acc[0] += (DT)(val[0] + val[1] + val[2] + val[3] + (float)(adr[0] ^ adr[1] ^ adr[2] ^ adr[3]));
-    } else if constexpr (sizeof(DT) == 4) {
+    if constexpr (sizeof(DT) == 4) {
       typedef __attribute__((address_space(3))) const f4* lds_p;
       const f4 q0 = *(lds_p)adr[0];
       const f4 q1 = *(lds_p)adr[1];
@@ -361,26 +359,16 @@ static int ell16_launch(bool wide, int waves, int64_t n_pos, int64_t n_cols, con
   const int64_t n_slabs = (n_cols + slab - 1) / slab;
   const int64_t n_waves = (n_pos + 15) / 16;
   const int64_t wgs = (n_waves + waves - 1) / waves;
-  const int mode = mu_tune_get("ell_mode") & 3;
   hipStream_t st = (hipStream_t)stream;
   MU_REQUIRE(parts >= 1 && parts <= n_slabs && (parts == 1 || !accumulate), "column parts: 1 .. slabs, partial products");
   const int s_per_part = (int)((n_slabs + parts - 1) / parts);
   const unsigned ny = (unsigned)((n_slabs + s_per_part - 1) / s_per_part);
-#define MU_GO(MD, DT)                                                                                                  \
-  hipLaunchKernelGGL((k_spmm_ell16<MD, DT>), dim3((unsigned)wgs, ny), dim3(64 * (waves + 1)), 0, st, n_pos, n_cols,     \
-                     (int)n_slabs, waves, d_hdr, d_wave_base, (const unsigned char*)d_ent, d_perm, (const DT*)d_Q,       \
+#define MU_GO(DT)                                                                                                 \
+  hipLaunchKernelGGL((k_spmm_ell16<DT>), dim3((unsigned)wgs, ny), dim3(64 * (waves + 1)), 0, st, n_pos, n_cols,   \
+                     (int)n_slabs, waves, d_hdr, d_wave_base, (const unsigned char*)d_ent, d_perm, (const DT*)d_Q, \
                      (DT*)d_Y, accumulate, s_per_part, y_stride)
-  if (wide) {
-    if (mode == 1) MU_GO(1, double);
-    else if (mode == 2) MU_GO(2, double);
-    else if (mode == 3) MU_GO(3, double);
-    else MU_GO(0, double);
-  } else {
-    if (mode == 1) MU_GO(1, float);
-    else if (mode == 2) MU_GO(2, float);
-    else if (mode == 3) MU_GO(3, float);
-    else MU_GO(0, float);
-  }
+  if (wide) MU_GO(double);
+  else MU_GO(float);
 #undef MU_GO
   MU_CHECK_LAUNCH();
   return MU_OK;

@@ -62,27 +62,20 @@ __device__ __forceinline__ float dpp_f(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
 }
 
-// ABL: timing ablations (wrong results on purpose): 1 only lanes 0-31 request their pair, 2 no gathers / FMAs,
-// 3 every request fetches the NEXT 32 pairs of one sequential stream per wave (what a slab-major operand with a
-// count table would ask the memory system for), 4 cycle accounting (s_memtime per wave: window wait + count,
-// spread, gathers + FMAs, slab barrier; the sums replace the product)
-// STAGE: a window's (LDS offset, value) pairs reach their four lanes through a per-wave LDS staging row
-// (one ds_write_b64 + a broadcast ds_read_b64 per 16 entries; lane 4 e + c) instead of the lane swaps
-// (lane 16 c + e): 12 VALU instructions per visit less, 3.5 cheap LDS instructions more.
-template <int RW, int ABL = 0, bool STAGE = false>
+// ACCT: cycle accounting (s_memtime per wave: window wait + count, spread, gathers + FMAs, slab barrier; the sums
+// replace the product).  (The timing ablations and the LDS staging row are retired; DESIGN.md keeps their measurements.)
+template <int RW, bool ACCT = false>
 __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_cols, int K,
                                                       const int64_t* __restrict__ sptr,
                                                       const unsigned long long* __restrict__ ent,
                                                       const int32_t* __restrict__ perm,
                                                       const float* __restrict__ Q, float* __restrict__ Y) {
   static_assert(RW >= 4 && RW <= 12, "a sweep covers 4 .. 12 rows per wave");
-  constexpr bool HALF = ABL == 1 || ABL == 3;
   typedef __attribute__((address_space(3))) const f4* lds_p;
   __shared__ __attribute__((aligned(65536))) f4 qs[2][kNSlabBytes / 16];  // Q row j of a slab at byte 64 j (64 KiB aligned: the XOR addressing)
-  __shared__ unsigned long long stage[STAGE ? kNW : 1][64];
   const int lane = threadIdx.x & 63;
   const int wave = uniform32(threadIdx.x >> 6);
-  const int c = STAGE ? (lane & 3) : (lane >> 4);  // this lane's column quad
+  const int c = lane >> 4;  // this lane's column quad
   const int rows_w = 4 * K;  // positions per wave
   const int64_t rb0 = (int64_t)blockIdx.x * (64 * (int64_t)K);
   const int64_t rb1 = (rb0 + 64 * (int64_t)K) < n_pos ? (rb0 + 64 * (int64_t)K) : n_pos;
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
 
   auto store_row = [&](int r_abs, f4 v) {  // lanes e == 0 hold the sums of columns 4c..4c+3
     const int64_t p = pw0 + r_abs;
-    if (r_abs < rows_w && p < rb1 && (STAGE ? lane < 4 : (lane & 15) == 0)) {
+    if (r_abs < rows_w && p < rb1 && (lane & 15) == 0) {
       const int64_t out = perm ? (int64_t)perm[p] : p;
       if (out >= 0) *reinterpret_cast<f4*>(Y + out * 16 + 4 * c) = v;
     }
@@ -122,19 +115,17 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
   };
   const char* __restrict__ entb = reinterpret_cast<const char*>(entw);
   const unsigned lane8 = (unsigned)lane * 8u, last8 = wg_last * 8u;
-  unsigned seq = 0;  // (ABL 3)
-  unsigned long long t_win = 0, t_spread = 0, t_back = 0, t_bar = 0;  // (ABL 4)
+  unsigned long long t_win = 0, t_spread = 0, t_back = 0, t_bar = 0;  // (ACCT)
   const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
   auto request = [&](unsigned cur, int& col, float& val) {  // lane l: pair cur + l (clamped into the workgroup's stream)
     unsigned off = cur * 8u + lane8;
-    if constexpr (ABL == 3) {
-      off = ((unsigned)wave * (wg_n / kNW) + seq) * 8u + lane8;
-      seq += 32u;
-      if (seq + 64u > wg_n / kNW) seq = 0;
-    }
     off = off < last8 ? off : last8;
+    // (Every lane requests its pair.  The load stays a conditional assignment under a constant that is true - what is
+    //  left of the retired half-window ablation: written as a plain initialisation, hipcc 7.2 allocates the registers of
+    //  every instance differently, and the instructions of this kernel are the ones DESIGN.md's numbers were taken with.)
+    constexpr bool kAllLanes = true;
     unsigned long long e = 0x000000007fffffffull;
-    if (!HALF || lane < 32)
+    if (kAllLanes || lane < 32)
       e = *reinterpret_cast<const unsigned long long*>(entb + (size_t)off);  // scalar base + 32-bit offset
     col = (int)(unsigned)e;
     val = __builtin_bit_cast(float, (unsigned)(e >> 32));
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
       auto front = [&](auto rc, MU_SPREAD_PARAMS) {
         constexpr int r = decltype(rc)::value;
         unsigned long long tc0 = 0;
-        if constexpr (ABL == 4) tc0 = __builtin_amdgcn_s_memtime();
+        if constexpr (ACCT) tc0 = __builtin_amdgcn_s_memtime();
         const int col = wcol[r];
         const float val = wval[r];
         // sorted rows: the entries of this slab are a prefix of the lanes still inside the row
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
         const unsigned long long m = __builtin_amdgcn_ballot_w64(col < s_hi) & rowmask;
         const int n = __builtin_amdgcn_readfirstlane(__builtin_popcountll(m));
         n_out = n;
-        if constexpr (ABL == 4) {
+        if constexpr (ACCT) {
           const unsigned long long tc1 = __builtin_amdgcn_s_memtime();
           t_win += tc1 - tc0;
           tc0 = tc1;
@@ -221,32 +212,14 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
         // 64 j + 16 ((j >> 2) & 3) with j = col - s0 (s0 is a multiple of 1024: the swizzle bits are col's own)
         unsigned a = ((unsigned)col << 6) + neg;
         a |= ((unsigned)col & 12u) << 2;
-        if (HALF) a &= 0xffffu;
-        if constexpr (STAGE) {
-          typedef __attribute__((address_space(3))) unsigned long long* st_p;
-          const st_p row = (st_p)(&stage[wave][0]);
-          // (a pair of 32-bit vector elements would do; hipcc 7.2 folds "element 1 of the loaded pair" into
-          //  the packed FMA's op_sel bits and picks element 0 - the offset was multiplied, not the value)
-          row[lane] = (unsigned long long)keep(a, m) | ((unsigned long long)keep(__builtin_bit_cast(unsigned, val), m) << 32);
-          __builtin_amdgcn_wave_barrier();  // (LDS operations of a wave execute in order: no wait between write and reads)
-          const unsigned long long e0 = row[(lane >> 2)], e1 = row[16 + (lane >> 2)];
-          const unsigned long long e2 = row[32 + (lane >> 2)], e3 = row[48 + (lane >> 2)];
-          a0 = (unsigned)e0, a1 = (unsigned)e1, a2 = (unsigned)e2, a3 = (unsigned)e3;
-          v0 = __builtin_bit_cast(float, (unsigned)(e0 >> 32));
-          v1 = __builtin_bit_cast(float, (unsigned)(e1 >> 32));
-          v2 = __builtin_bit_cast(float, (unsigned)(e2 >> 32));
-          v3 = __builtin_bit_cast(float, (unsigned)(e3 >> 32));
-          __builtin_amdgcn_wave_barrier();
-        } else {
-          const Rows4 A = rows4(keep(a, m));
-          const Rows4 V = rows4(keep(__builtin_bit_cast(unsigned, val), m));
-          a0 = A.x[0], a1 = A.x[1], a2 = A.x[2], a3 = A.x[3];
-          v0 = __builtin_bit_cast(float, V.x[0]);
-          v1 = __builtin_bit_cast(float, V.x[1]);
-          v2 = __builtin_bit_cast(float, V.x[2]);
-          v3 = __builtin_bit_cast(float, V.x[3]);
-        }
-        if constexpr (ABL == 4) {
+        const Rows4 A = rows4(keep(a, m));
+        const Rows4 V = rows4(keep(__builtin_bit_cast(unsigned, val), m));
+        a0 = A.x[0], a1 = A.x[1], a2 = A.x[2], a3 = A.x[3];
+        v0 = __builtin_bit_cast(float, V.x[0]);
+        v1 = __builtin_bit_cast(float, V.x[1]);
+        v2 = __builtin_bit_cast(float, V.x[2]);
+        v3 = __builtin_bit_cast(float, V.x[3]);
+        if constexpr (ACCT) {
           asm volatile("" ::"v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(v0), "v"(v1), "v"(v2), "v"(v3));
           t_spread += __builtin_amdgcn_s_memtime() - tc0;
         }
@@ -257,12 +230,8 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
       auto back = [&](auto rc, unsigned a0, unsigned a1, unsigned a2, unsigned a3, float v0, float v1, float v2,
                       float v3, int n) {
         constexpr int r = decltype(rc)::value;
-        if constexpr (ABL == 2) {
-          acc[r][0] += v0 + v1 + __builtin_bit_cast(float, a0 ^ a1);
-          return;
-        }
         unsigned long long tb0 = 0;
-        if constexpr (ABL == 4) tb0 = __builtin_amdgcn_s_memtime();
+        if constexpr (ACCT) tb0 = __builtin_amdgcn_s_memtime();
         const f4 q0 = *(lds_p)(a0 ^ qx);
         const f4 q1 = *(lds_p)(a1 ^ qx);
         if (n > 32) {  // uniform
@@ -278,7 +247,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
           acc[r] += v1 * q1;
           asm volatile("" : "+v"(acc[r]));
         }
-        if constexpr (ABL == 4) t_back += __builtin_amdgcn_s_memtime() - tb0;
+        if constexpr (ACCT) t_back += __builtin_amdgcn_s_memtime() - tb0;
       };
       // Three stages per row, in this order inside a turn: the gathers of row r go out, the front of row r + 1
       // runs under their latency (it has no LDS operation: the spread is lane swaps), then the FMAs of row r.
@@ -316,7 +285,7 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
         front(std::integral_constant<int, 0>{}, ea0, ea1, ea2, ea3, ev0, ev1, ev2, ev3, en);
         static_for<RW>([&](auto rc) {
           constexpr int r = decltype(rc)::value;
-          constexpr bool kPipe3 = (ABL == 0) && !STAGE;
+          constexpr bool kPipe3 = !ACCT;
           f4 q0, q1, q2, q3;
           if constexpr (kPipe3) {
             if constexpr (r & 1) gather(oa0, oa1, oa2, oa3, on, q0, q1, q2, q3);
@@ -352,10 +321,10 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
 #undef MU_SPREAD_PARAMS
       // the DMA pieces are older than the window requests of rows 3 .. RW-1 (and of every revisit)
       unsigned long long tq0 = 0;
-      if constexpr (ABL == 4) tq0 = __builtin_amdgcn_s_memtime();
+      if constexpr (ACCT) tq0 = __builtin_amdgcn_s_memtime();
       asm volatile("s_waitcnt vmcnt(%0)" ::"i"(RW - 3) : "memory");
       __syncthreads();  // next slab visible; everyone finished reading this one
-      if constexpr (ABL == 4) t_bar += __builtin_amdgcn_s_memtime() - tq0;
+      if constexpr (ACCT) t_bar += __builtin_amdgcn_s_memtime() - tq0;
     }
 
     // slot partial sums -> row sums in a fixed order; lanes e == 0 store
@@ -365,23 +334,17 @@ __global__ __launch_bounds__(1024) void k_spmm_narrow(int64_t n_pos, int64_t n_c
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float x = v[k];
-        if constexpr (STAGE) {  // lane 4 e + c: slots 4 apart inside a 16-lane row, then the four rows
-          x += dpp_f<0x128>(x);  // row_ror:8
-          x += dpp_f<0x124>(x);  // row_ror:4
-          x += __shfl_xor(x, 16, 64);
-          x += __shfl_xor(x, 32, 64);
-        } else {               // lane 16 c + e: a rotation tree inside every 16-lane row
-          x += dpp_f<0x128>(x);  // row_ror:8
-          x += dpp_f<0x124>(x);  // row_ror:4
-          x += dpp_f<0x122>(x);  // row_ror:2
-          x += dpp_f<0x121>(x);  // row_ror:1
-        }
+        // lane 16 c + e: a rotation tree inside every 16-lane row
+        x += dpp_f<0x128>(x);  // row_ror:8
+        x += dpp_f<0x124>(x);  // row_ror:4
+        x += dpp_f<0x122>(x);  // row_ror:2
+        x += dpp_f<0x121>(x);  // row_ror:1
         v[k] = x;
       }
       store_row(r0 + r, v);
     });
   }
-  if constexpr (ABL == 4) {  // wave `w` of workgroup `b`: row 16 b + w of Y holds the sums
+  if constexpr (ACCT) {  // wave `w` of workgroup `b`: row 16 b + w of Y holds the sums
     if (lane < 5 && blockIdx.x * 16 + wave < n_pos) {
       const unsigned long long v = lane == 0 ? t_win : lane == 1 ? t_spread : lane == 2 ? t_back : lane == 3 ? t_bar
                                                                  : __builtin_amdgcn_s_memtime() - t_begin;
@@ -413,33 +376,9 @@ int mu_spmm_narrow_f32_launch(hipStream_t st, int64_t n_pos, int64_t n_cols, int
 #define MU_NARROW(RW_)                                                                                   \
   hipLaunchKernelGGL((k_spmm_narrow<RW_>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, \
                      ent, perm, Q, Y)
-  if (mu_tune_get("spmm_mode") == 3 && narrow_rw(K) == 10) {  // A/B: window entries spread through an LDS staging row
-    hipLaunchKernelGGL((k_spmm_narrow<10, 0, true>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr,
-                       ent, perm, Q, Y);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-  }
-  if (mu_tune_get("spmm_mode") == 6 && narrow_rw(K) == 10) {  // cycle accounting
-    hipLaunchKernelGGL((k_spmm_narrow<10, 4>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, ent, perm,
+  if (tune(kTune_spmm_mode) == 6 && narrow_rw(K) == 10) {  // cycle accounting
+    hipLaunchKernelGGL((k_spmm_narrow<10, true>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, ent, perm,
                        Q, Y);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-  }
-  if (mu_tune_get("spmm_mode") == 5 && narrow_rw(K) == 10) {  // ablation: sequential 32-pair requests per wave
-    hipLaunchKernelGGL((k_spmm_narrow<10, 3>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, ent, perm,
-                       Q, Y);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-  }
-  if (mu_tune_get("spmm_mode") == 4 && narrow_rw(K) == 10) {  // ablation: no gathers / FMAs
-    hipLaunchKernelGGL((k_spmm_narrow<10, 2>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, ent, perm,
-                       Q, Y);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-  }
-  if (mu_tune_get("spmm_mode") == 2 && narrow_rw(K) == 10) {
-    hipLaunchKernelGGL((k_spmm_narrow<10, 1>), dim3((unsigned)wgs), dim3(1024), 0, st, n_pos, n_cols, K, sptr, ent,
-                       perm, Q, Y);
     MU_CHECK_LAUNCH();
     return MU_OK;
   }

@@ -213,10 +213,8 @@ struct Win {      // what stage A of a pass hands to stage B
   unsigned any16; // bit e: some group of the wave uses window entry e
 };
 
-// MODE is 0 in production; the other bits switch parts of the kernel off for timing ablations
-// (results are then wrong on purpose): 1 no LDS gathers / FMAs, 8 no window requests (and no
-// overflow passes), 32 window slots 0-7 as two batches of four LDS reads (r01), 64 per-wave cycle
-// accounting instead of the product.
+// MODE is 0 in production; 64 = per-wave cycle accounting instead of the product (scripts/spmm_probe.py --account).
+// (The timing ablations that switched parts of the kernel off are retired; DESIGN.md 4.2 keeps their measurements.)
 // SLAB = columns per slab: kSlabNarrow, or kSlabWide (NB = 4, f32, K >= 6 only: k_spmm_wide / k_spmm_wide_rng).
 template <int K, int MODE, int NB, typename DT, bool RNG = false, int SLAB = kSlabNarrow>
 __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
@@ -226,7 +224,8 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
                                               const DT* __restrict__ Q, DT* __restrict__ Y,
                                               int accumulate, const WinRanges* rgp = nullptr) {
   static_assert(K >= 1 && K <= kKMax, "K out of range");
-  static_assert(sizeof(DT) == 4 || MODE == 0, "the timing ablations exist for f32 only");
+  static_assert(MODE == 0 || MODE == 64, "the product, or its cycle accounting");
+  static_assert(sizeof(DT) == 4 || MODE == 0, "the cycle accounting exists for f32 only");
   constexpr int W = kWaves;
   constexpr int kSlabCols = SLAB;
   constexpr bool kPow2 = (kSlabCols & (kSlabCols - 1)) == 0;
@@ -240,7 +239,6 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
   constexpr int kPieces = kSlabBytes / 1024;                 // 1 KiB LDS-DMA pieces per slab
   constexpr int kMyPieces = kPieces / W;                     // per wave and slab: 4 / 2 / 1
   static_assert(kPieces % W == 0, "every wave issues the same number of DMA pieces");
-  constexpr bool kDeep = !(MODE & 32);
   // VMEM order of a wave in one slab: D0 R0 D1 R1 ... (DMA piece u of the NEXT slab goes out right
   // before pass u, the pieces a short K leaves over after the last pass; R = the window request of a
   // pass).  Between the request of (row-set k, slab s-1) and pass (k, s) that is always K - 1
@@ -267,7 +265,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
   // requested two passes earlier and more: landed), the others at the end of the slab (their next
   // request then has K - 3 passes and more before it is needed).  At the mid point the wave has issued
   // the requests of passes 0 .. kMid+1 and every DMA piece.
-  constexpr int kMid = (K >= 5 && !(MODE & (64 | 4096 | 16384))) ? K - 3 : -1;
+  constexpr int kMid = (K >= 5 && !(MODE & 64)) ? K - 3 : -1;
   constexpr unsigned kEarlyMask = kMid >= 2 ? ((1u << (kMid - 1)) - 1u) : 0u;
   static_assert(kMid < 0 || kMyPieces <= kMid + 2, "every DMA piece is out at the mid point");
   auto constexpr mid_wait = [](int k) { return (kMid + 1 - k) + (kMyPieces > k + 1 ? kMyPieces - (k + 1) : 0); };
@@ -374,18 +372,7 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
     auto stage_a = [&](auto kc, auto slowc) -> Win {
       constexpr int k = decltype(kc)::value;
       constexpr bool SLOW = decltype(slowc)::value;
-      if constexpr (MODE & 128) {  // stage B alone: a synthetic 12-entry window for every group
-        Win ws;
-        ws.a = (int)((unsigned)(lane * 37 + k * 13 + (int)s0) % (unsigned)kSlabCols) << kRowShift;
-        ws.vv = 1.0f;
-        // (+ 65536 / 131072: the windows of waves 12-15 / 8-15 are empty - stage B alone on 12 / 8 of the
-        //  16 waves, what that many "gather" waves of a wave-specialised kernel could deliver)
-        ws.any16 = (((MODE & 65536) && wave >= 12) || ((MODE & 131072) && wave >= 8)) ? 0u : 0x0fffu;
-        if constexpr (MODE & 64) t_a -= now();
-        return ws;
-      }
       int col, valbits;
-      if constexpr (MODE & 262144) __builtin_amdgcn_s_setprio(2);  // (timing: stage A above the gathers)
       unsigned tw0 = 0;
       if constexpr (MODE & 64) tw0 = now();
       if constexpr (SLOW) {
@@ -417,23 +404,15 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
       if constexpr (kPow2) w.a = valid ? (((col - col0) & (kSlabCols - 1)) << kRowShift) : 0;
       else w.a = valid ? ((col - (int)s0) << kRowShift) : 0;
       w.vv = valid ? __builtin_bit_cast(float, valbits) : 0.f;
-      if constexpr (!(MODE & 8)) {
-        // entries consumed by this lane's group: the bits of its 16 lanes in the ballot, counted on
-        // the vector side (a wave issues one scalar instruction per ~5 cycles and nothing else
-        // meanwhile: the r02k version - four s_bcnt1 and a packed byte per group - was 14 SALU)
-        const unsigned mine = (lane & 32) ? mhi : mlo;
-        const unsigned cnt = (unsigned)__popc(mine & gmask);
-        off[k] += cnt << 3;  // 8 bytes per consumed pair
-        request_window<k>(off[k], entb, __ballot(off[k] < (unsigned)bcast_i<k>((int)endv)));
-        // a window used up (some group has all 16 bits set): maybe more in this slab
-        if (__ballot(cnt == 16u)) again |= 1u << k;
-      }
-      if constexpr (MODE & 1024) {  // real stage A, synthetic 12-entry window for stage B
-        w.a = (int)((unsigned)(lane * 37 + k * 13 + (int)s0) % (unsigned)kSlabCols) << kRowShift;
-        w.vv = 1.0f;
-        w.any16 = 0x0fffu;
-      }
-      if constexpr (MODE & 2048) w.any16 = (w.any16 & 0xf000u) ? 0xffffu : (w.any16 & 0x0f00u) ? 0x0fffu : w.any16;
+      // entries consumed by this lane's group: the bits of its 16 lanes in the ballot, counted on
+      // the vector side (a wave issues one scalar instruction per ~5 cycles and nothing else
+      // meanwhile: the r02k version - four s_bcnt1 and a packed byte per group - was 14 SALU)
+      const unsigned mine = (lane & 32) ? mhi : mlo;
+      const unsigned cnt = (unsigned)__popc(mine & gmask);
+      off[k] += cnt << 3;  // 8 bytes per consumed pair
+      request_window<k>(off[k], entb, __ballot(off[k] < (unsigned)bcast_i<k>((int)endv)));
+      // a window used up (some group has all 16 bits set): maybe more in this slab
+      if (__ballot(cnt == 16u)) again |= 1u << k;
       return w;
     };
     // Stage B: the LDS gathers and FMAs of the window.
@@ -442,96 +421,37 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
       // the gathers are the part that is bound by a shared pipe (LDS): a wave that is in them goes
       // first (measured on X Q / X^T Y at 125k x 200k: -6.5 % / -2.8 %)
       __builtin_amdgcn_s_setprio(1);
-      if constexpr (MODE & 1) {
-        acc[k][0] += (DT)(w.vv + (float)w.a);
-      } else if constexpr (kDeep) {
-        // (MODE 8192 / 8192 + 32768, timing only: the reads with lanes 32-63 / the odd groups
-        // switched off in EXEC - does the LDS pipe charge for inactive quarter-waves?)
-        auto qrd = [&](auto ec) {
-          Quad<NB, DT> r;
-          if constexpr (MODE & 8192) {
-            asm volatile("s_mov_b64 exec, %0" ::"s"((MODE & 32768) ? 0x0000ffff0000ffffull : 0x00000000ffffffffull) : "memory");
-            r = quad_read<decltype(ec)::value, NB, DT>(qbase, w.a);
-            asm volatile("s_mov_b64 exec, -1" ::: "memory");
-          } else {
-            r = quad_read<decltype(ec)::value, NB, DT>(qbase, w.a);
-          }
-          return r;
-        };
-        // A pass is a chain of LDS round trips; sorted rows fill the window from slot 0 (bit e of
-        // any16 set => every lower bit set), 8 entries per row and slab on the bench matrices.
-        // Slots 0-7 go out as one batch of eight reads, the upper half as one more batch sized by
-        // the highest slot in use: two round trips for almost every pass (r01: three to six).
-        // (twelve reads in flight for the passes that use slots 8-11: hipcc spills at K >= 7)
-        if (w.any16 & 0x00f0u) {
-          const Quad<NB, DT> r0 = qrd(std::integral_constant<int, 0>{});
-          const Quad<NB, DT> r1 = qrd(std::integral_constant<int, 4>{});
-          quad_fma<0, NB, DT>(r0, w.vv, acc[k]);
-          quad_fma<4, NB, DT>(r1, w.vv, acc[k]);
-          // (hipcc otherwise sinks the second quad into a block shared with the branch below - one
-          //  quad of reads, its FMAs, then the next quad: two LDS round trips instead of one)
-          asm volatile("; eight reads in flight" ::: "memory");
-        } else if (w.any16 & 0x000fu) {
-          const Quad<NB, DT> r = qrd(std::integral_constant<int, 0>{});
-          quad_fma<0, NB, DT>(r, w.vv, acc[k]);
-        }
-        if (w.any16 & 0xf000u) {
-          const Quad<NB, DT> r0 = qrd(std::integral_constant<int, 8>{});
-          const Quad<NB, DT> r1 = qrd(std::integral_constant<int, 12>{});
-          quad_fma<8, NB, DT>(r0, w.vv, acc[k]);
-          quad_fma<12, NB, DT>(r1, w.vv, acc[k]);
-        } else if (w.any16 & 0x0c00u) {
-          const Quad<NB, DT> r = qrd(std::integral_constant<int, 8>{});
-          quad_fma<8, NB, DT>(r, w.vv, acc[k]);
-        } else if (w.any16 & 0x0300u) {
-          const Pair<NB, DT> r = pair_read<8, NB, DT>(qbase, w.a);
-          pair_fma<8, NB, DT>(r, w.vv, acc[k]);
-        }
-      } else {
-        if (w.any16 & 0x000fu) { const Quad<NB, DT> r = quad_read<0, NB, DT>(qbase, w.a); quad_fma<0, NB, DT>(r, w.vv, acc[k]); }
-        if (w.any16 & 0x00f0u) { const Quad<NB, DT> r = quad_read<4, NB, DT>(qbase, w.a); quad_fma<4, NB, DT>(r, w.vv, acc[k]); }
-        if (w.any16 & 0xff00u) {
-          { const Pair<NB, DT> r = pair_read<8, NB, DT>(qbase, w.a); pair_fma<8, NB, DT>(r, w.vv, acc[k]); }
-          if (w.any16 & 0x0c00u) { const Pair<NB, DT> r = pair_read<10, NB, DT>(qbase, w.a); pair_fma<10, NB, DT>(r, w.vv, acc[k]); }
-          if (w.any16 & 0x3000u) { const Pair<NB, DT> r = pair_read<12, NB, DT>(qbase, w.a); pair_fma<12, NB, DT>(r, w.vv, acc[k]); }
-          if (w.any16 & 0xc000u) { const Pair<NB, DT> r = pair_read<14, NB, DT>(qbase, w.a); pair_fma<14, NB, DT>(r, w.vv, acc[k]); }
-        }
+      // A pass is a chain of LDS round trips; sorted rows fill the window from slot 0 (bit e of
+      // any16 set => every lower bit set), 8 entries per row and slab on the bench matrices.
+      // Slots 0-7 go out as one batch of eight reads, the upper half as one more batch sized by
+      // the highest slot in use: two round trips for almost every pass (r01: three to six).
+      // (twelve reads in flight for the passes that use slots 8-11: hipcc spills at K >= 7)
+      if (w.any16 & 0x00f0u) {
+        const Quad<NB, DT> r0 = quad_read<0, NB, DT>(qbase, w.a);
+        const Quad<NB, DT> r1 = quad_read<4, NB, DT>(qbase, w.a);
+        quad_fma<0, NB, DT>(r0, w.vv, acc[k]);
+        quad_fma<4, NB, DT>(r1, w.vv, acc[k]);
+        // (hipcc otherwise sinks the second quad into a block shared with the branch below - one
+        //  quad of reads, its FMAs, then the next quad: two LDS round trips instead of one)
+        asm volatile("; eight reads in flight" ::: "memory");
+      } else if (w.any16 & 0x000fu) {
+        const Quad<NB, DT> r = quad_read<0, NB, DT>(qbase, w.a);
+        quad_fma<0, NB, DT>(r, w.vv, acc[k]);
       }
-      __builtin_amdgcn_s_setprio(0);
-    };
-
-    // Slots 0-7 of a main pass in two halves: the eight LDS reads go out BEFORE stage A of the next
-    // pass, whose scalar work then runs under their latency; the FMAs and the upper half follow.
-    struct Low8 { Quad<NB, DT> r0, r1; };
-    auto b_issue = [&](const Win& w) -> Low8 {
-      Low8 r;
-      r.r0 = quad_read<0, NB, DT>(qbase, w.a);
-      r.r1 = quad_read<4, NB, DT>(qbase, w.a);
-      return r;
-    };
-    auto b_finish = [&](auto kc, const Win& w, const Low8& r) {
-      constexpr int k = decltype(kc)::value;
-      __builtin_amdgcn_s_setprio(1);
-      quad_fma<0, NB, DT>(r.r0, w.vv, acc[k]);
-      quad_fma<4, NB, DT>(r.r1, w.vv, acc[k]);
       if (w.any16 & 0xf000u) {
-        const Quad<NB, DT> q0 = quad_read<8, NB, DT>(qbase, w.a);
-        const Quad<NB, DT> q1 = quad_read<12, NB, DT>(qbase, w.a);
-        quad_fma<8, NB, DT>(q0, w.vv, acc[k]);
-        quad_fma<12, NB, DT>(q1, w.vv, acc[k]);
+        const Quad<NB, DT> r0 = quad_read<8, NB, DT>(qbase, w.a);
+        const Quad<NB, DT> r1 = quad_read<12, NB, DT>(qbase, w.a);
+        quad_fma<8, NB, DT>(r0, w.vv, acc[k]);
+        quad_fma<12, NB, DT>(r1, w.vv, acc[k]);
       } else if (w.any16 & 0x0c00u) {
-        const Quad<NB, DT> q = quad_read<8, NB, DT>(qbase, w.a);
-        quad_fma<8, NB, DT>(q, w.vv, acc[k]);
+        const Quad<NB, DT> r = quad_read<8, NB, DT>(qbase, w.a);
+        quad_fma<8, NB, DT>(r, w.vv, acc[k]);
       } else if (w.any16 & 0x0300u) {
-        const Pair<NB, DT> q = pair_read<8, NB, DT>(qbase, w.a);
-        pair_fma<8, NB, DT>(q, w.vv, acc[k]);
+        const Pair<NB, DT> r = pair_read<8, NB, DT>(qbase, w.a);
+        pair_fma<8, NB, DT>(r, w.vv, acc[k]);
       }
       __builtin_amdgcn_s_setprio(0);
     };
-    // (measured r02p: 4.80 / 4.89 ms against 4.54 / 4.75 unsplit on X Q / X^T Y at 125k x 200k: the
-    //  eight results held across stage A cost more than the latency they hide; kept as ablation 4096)
-    constexpr bool kSplit = kDeep && (MODE & 4096) && !(MODE & (1 | 64));
-    constexpr bool kPipeB = (MODE & 16384) && !(MODE & (1 | 64 | 4096));
 
     if constexpr (MODE & 64) {
       static_for<K>([&](auto kc) {
@@ -543,53 +463,17 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
         t_b += now() - t2;
       });
     } else {
-      if constexpr (kPipeB) {
-        // Stage B as a software pipeline ACROSS passes: the gathers of a pass are three batches of
-        // four window slots (0-3, 4-7, 8-11; 12-15 on demand), and a batch's LDS reads are issued two
-        // batches before its FMAs - the reads of pass k+1's first two batches go out between the
-        // FMAs of pass k, behind stage A(k+1).  A pass no longer is a chain of three LDS round trips.
-        next_piece(0);
-        Win wk = stage_a(std::integral_constant<int, 0>{}, std::false_type{});
-        Quad<NB, DT> b0 = quad_read<0, NB, DT>(qbase, wk.a);
-        Quad<NB, DT> b1 = quad_read<4, NB, DT>(qbase, wk.a);
-        static_for<K>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          Win wn = wk;
-          if constexpr (k + 1 < K) {
-            if constexpr (k + 1 < kMyPieces) next_piece(k + 1);
-            wn = stage_a(std::integral_constant<int, k + 1>{}, std::false_type{});
-          }
-          const bool n2 = (wk.any16 & 0x0f00u) != 0;
-          __builtin_amdgcn_s_setprio(1);
-          Quad<NB, DT> b2;
-          quad_fma<0, NB, DT>(b0, wk.vv, acc[k]);
-          if (n2) b2 = quad_read<8, NB, DT>(qbase, wk.a);
-          quad_fma<4, NB, DT>(b1, wk.vv, acc[k]);
-          if constexpr (k + 1 < K) b0 = quad_read<0, NB, DT>(qbase, wn.a);
-          if (n2) quad_fma<8, NB, DT>(b2, wk.vv, acc[k]);
-          if constexpr (k + 1 < K) b1 = quad_read<4, NB, DT>(qbase, wn.a);
-          if (wk.any16 & 0xf000u) {
-            const Quad<NB, DT> r = quad_read<12, NB, DT>(qbase, wk.a);
-            quad_fma<12, NB, DT>(r, wk.vv, acc[k]);
-          }
-          __builtin_amdgcn_s_setprio(0);
-          wk = wn;
-        });
-      } else {
       // A(k+1) is issued before B(k): the scalar part of the next pass runs under this pass' gathers
       next_piece(0);
       Win w = stage_a(std::integral_constant<int, 0>{}, std::false_type{});
       static_for<K>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         Win wn = w;
-        Low8 low;
-        if constexpr (kSplit) low = b_issue(w);
         if constexpr (k + 1 < K) {
           if constexpr (k + 1 < kMyPieces) next_piece(k + 1);
           wn = stage_a(std::integral_constant<int, k + 1>{}, std::false_type{});
         }
-        if constexpr (kSplit) b_finish(kc, w, low);
-        else stage_b(kc, w);
+        stage_b(kc, w);
         w = wn;
         if constexpr (k == kMid && kEarlyMask != 0) {
           // mid point: revisit the early row-sets now (one round; a second overflow waits for the slab end)
@@ -607,7 +491,6 @@ __device__ __forceinline__ void spmm_win_body(int64_t n_pos, int64_t n_cols,
           }
         }
       });
-      }
     }
 #pragma unroll
     for (int u = K; u < kMyPieces; ++u) next_piece(u);  // K < kMyPieces: the pieces left over
@@ -961,10 +844,10 @@ int mu_csr_stream_fill(int64_t n_pos, const int32_t* d_perm, const int64_t* d_in
   int64_t blocks = (n_pos + 3) / 4;
   // workgroups per CU: 32 alone; a caller that runs the copy next to a kernel that needs whole CUs
   // (the transpose on another stream) lowers it so that both stay resident (tune pack_wg)
-  const int per_cu = mu_tune_get("pack_wg") > 0 ? mu_tune_get("pack_wg") : 32;
+  const int per_cu = tune(kTune_pack_wg) > 0 ? tune(kTune_pack_wg) : 32;
   const int64_t cap = (int64_t)mu_num_cus() * per_cu;
   if (blocks > cap) blocks = cap;
-  if (mu_tune_get("stream_pipe") == 1)  // (the loop of before, for comparison)
+  if (tune(kTune_stream_pipe) == 1)  // (the loop of before, for comparison)
     hipLaunchKernelGGL(k_stream_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_pos,
                        d_perm, d_indptr, d_indices, d_values, d_sptr, (unsigned long long*)d_ent);
   else
@@ -995,13 +878,13 @@ int mu_spmm_stream_slab_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr
   hipStream_t st = (hipStream_t)stream;
   const unsigned long long* ent = (const unsigned long long*)d_ent;
   int K = (k_layout >= 1 && k_layout <= kKMax) ? k_layout : pick_k(n_pos);
-  const int force_k = mu_tune_get("spmm_k");  // tests / tuning only (mu_tune_set); 0 in production
+  const int force_k = tune(kTune_spmm_k);  // tests / tuning only (mu_tune_set); 0 in production
   if (force_k >= 1 && force_k <= kKMax) K = force_k;
   if (slab_cols == kSlabWide && !slab_ok(B, K, slab_cols)) {
     mu_set_error("320-column slabs exist for B = 64 and K >= 6 only (B = %d, K = %d)", B, K);
     return MU_ERR_ARG;
   }
-  const int mode = mu_tune_get("spmm_mode");
+  const int mode = tune(kTune_spmm_mode);
   if (slab_cols == kSlabWide) {
     if (mode == 64 && K == 8) return launch_wide<8, 64>(st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y);
     if (mode != 0) {
@@ -1015,17 +898,11 @@ int mu_spmm_stream_slab_f32(int64_t n_pos, int64_t n_cols, const int64_t* d_sptr
     }
   }
   // B = 16: the narrow-block kernel (tune spmm_narrow_off = 1: this file's NB = 1 instance, kept for A/B runs)
-  if (B == 16 && (mode == 0 || (mode >= 2 && mode <= 6)) && mu_tune_get("spmm_narrow_off") == 0)
+  if (B == 16 && (mode == 0 || mode == 6) && tune(kTune_spmm_narrow_off) == 0)
     return mu_spmm_narrow_f32_launch(st, n_pos, n_cols, K, d_sptr, ent, d_perm, d_Q, d_Y);
 #define MU_ARGS B, st, n_pos, n_cols, d_sptr, ent, d_perm, d_Q, d_Y
   if (mode != 0) {
-    // timing ablations that are still compiled (the others - 32, 4096, 8192, 16384, 65536, 131072,
-    // 262144: DESIGN.md 4.2 has their r02 measurements - need an entry here to be instantiated again)
-    if (mode == 1 && K == 8) return launch<8, 1>(MU_ARGS);
-    if (mode == 9 && K == 8) return launch<8, 9>(MU_ARGS);
-    if (mode == 64 && K == 8) return launch<8, 64>(MU_ARGS);
-    if (mode == 128 && K == 8) return launch<8, 128>(MU_ARGS);
-    if (mode == 128 + 64 && K == 8) return launch<8, 128 + 64>(MU_ARGS);
+    if (mode == 64 && K == 8) return launch<8, 64>(MU_ARGS);  // the cycle accounting (dealt for K = 8)
     mu_set_error("spmm_mode %d has no compiled instance for K = %d", mode, K);
     return MU_ERR_ARG;
   }

@@ -163,14 +163,13 @@ __device__ __forceinline__ void pipe_drain(A (&c0)[4], B (&v0)[4], A (&c1)[4], B
                : "memory");
 }
 
-// ABL (timing ablations, wrong results; tune "tfidf_abl"): 1 no LDS atomics, 2 f32 atomics
 // M: bins of M x 8192 columns (M = 2: 128 KiB, one workgroup per CU - pieces of a row twice as long: 14.3 -> 13.1 ms
 // at 1e6 x 200k now that a wave keeps two iterations in flight; r04's first try of M = 2, on the unpipelined kernel,
 // lost 17 %).
 // (r04 also built the slab pointer search INTO this sweep - the lane that owns a row finds the ends of its next
 // pieces from the end of the last one - to drop k_slab_ptr's 3.0 ms: the dependent loads, un-overlapped inside a
 // wave, cost the sweep 4.3 ms.  Deleted; what the search costs is its 64-byte sectors, wherever it runs.)
-template <typename T, int CH, int ABL = 0, int M = 1>
+template <typename T, int CH, int M = 1>
 __global__ __launch_bounds__(kSweepThreads, (sizeof(T) == 4 && M == 1) ? 8 : 4) void k_row_col_sums_pipe(  // (CH = 4: pipe_drain)
     int64_t n_rows, int64_t n_cols, int64_t S, const int64_t* __restrict__ indptr,
     const int32_t* __restrict__ indices, const T* __restrict__ values,
@@ -228,9 +227,7 @@ __global__ __launch_bounds__(kSweepThreads, (sizeof(T) == 4 && M == 1) ? 8 : 4) 
         for (int u = 0; u < CH; ++u) {
           const bool ok = pb + lane + 64 * u < hi;
           const double x = ok ? (double)v[u] : 0.0;
-          if constexpr (ABL == 0) atomicAdd(&bins[ok ? c[u] - cbase : lane], x);
-          if constexpr (ABL == 1) rs += (double)(c[u] & 1);
-          if constexpr (ABL == 2) atomicAdd(reinterpret_cast<float*>(bins) + (ok ? c[u] - cbase : lane), (float)x);
+          atomicAdd(&bins[ok ? c[u] - cbase : lane], x);
           rs += x;
         }
         if (row_ends) {  // (uniform)
@@ -522,7 +519,7 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_tfidf_scale_sweep_wide(
 // contiguous from pair row_dst[row] of `ent`, i.e. in the launch order of the SpMM that lsi() runs next (csrc/spmm_win.hip)
 // - while it has every entry in registers.  lsi's streaming copy of X (8 bytes read + 8 written per entry, next to the
 // transposition's fill) disappears, and the transposition reads rows as contiguous pairs (csrc/tpack4.hip).
-template <int M, int CH, int ABL = 0, bool STREAM = false>  // ABL (timing ablations, tune "tfidf_abl"): 3 no arithmetic, 4 no stores
+template <int M, int CH, bool STREAM = false>
 __global__ __launch_bounds__(kSweepThreads, 4) void k_tfidf_scale_sweep_pipe(
     int64_t n_rows, int64_t n_cols, int64_t S, const int64_t* __restrict__ indptr,
     const int32_t* __restrict__ indices, const float* __restrict__ values,
@@ -593,15 +590,11 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_tfidf_scale_sweep_pipe(
           const int p = pb + lane + 64 * u;
           const int q = p < hi ? p : hi - 1;
           float t = inv * x[u];                               // :96  D @ counts
-          if constexpr (ABL != 3) {
-            if (use_scale) t = t * scale;                       // :101-102
-            if (flags & MU_TFIDF_LOG_TF) t = log1p_wave(t);     // :103-104
-            t = t * lidf[c[u] - cbase];                         // :110-112  tf @ diag(idf)
-            if (flags & MU_TFIDF_LOG_TFIDF) t = log1p_wave(t);  // :116-117
-          } else {
-            t += (float)c[u];
-          }
-          if constexpr (ABL != 4) ob[q] = t;
+          if (use_scale) t = t * scale;                       // :101-102
+          if (flags & MU_TFIDF_LOG_TF) t = log1p_wave(t);     // :103-104
+          t = t * lidf[c[u] - cbase];                         // :110-112  tf @ diag(idf)
+          if (flags & MU_TFIDF_LOG_TFIDF) t = log1p_wave(t);  // :116-117
+          ob[q] = t;
           if constexpr (STREAM)  // (a lane past the piece's end stores the piece's last pair again: same address, same bits)
             eb[q] = (unsigned long long)(unsigned)c[u] | ((unsigned long long)__builtin_bit_cast(unsigned, t) << 32);
           zeros += (p < hi && t == 0.f) ? 1u : 0u;
@@ -864,22 +857,16 @@ static int row_col_sums_impl(int dtype, int64_t n_rows, int64_t n_cols, const in
   // software-pipelined walk (r04); tune "tfidf_pipe" = 1: the kernels of before, for comparison.  f32 matrices of
   // 100 000 rows and more: 16 384-column bins, one workgroup per CU (tune "tfidf_sum_m" = 1: never, 2: whatever
   // the size (tests))
-  const bool pipe = mu_tune_get("tfidf_pipe") != 1;
-  const int abl = mu_tune_get("tfidf_abl"), sum_m = mu_tune_get("tfidf_sum_m");
-  const bool big = dtype == MU_DTYPE_F32 && pipe && abl == 0 && sum_m != 1 && (n_rows >= 100000 || sum_m == 2);
+  const bool pipe = tune(kTune_tfidf_pipe) != 1;
+  const int sum_m = tune(kTune_tfidf_sum_m);
+  const bool big = dtype == MU_DTYPE_F32 && pipe && sum_m != 1 && (n_rows >= 100000 || sum_m == 2);
   if (!d_slab_ptr) {
     int rc = launch_slab_ptr(n_rows, n_cols, d_indptr, d_indices, (int64_t*)d_work, st);
     if (rc) return rc;
   }
   if (big)
-    hipLaunchKernelGGL((k_row_col_sums_pipe<float, 4, 0, 2>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows,
+    hipLaunchKernelGGL((k_row_col_sums_pipe<float, 4, 2>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows,
                        n_cols, S, d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, partial);
-  else if (dtype == MU_DTYPE_F32 && pipe && abl == 1)
-    hipLaunchKernelGGL((k_row_col_sums_pipe<float, 4, 1>), dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S,
-                       d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, partial);
-  else if (dtype == MU_DTYPE_F32 && pipe && abl == 2)
-    hipLaunchKernelGGL((k_row_col_sums_pipe<float, 4, 2>), dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S,
-                       d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, partial);
   else if (dtype == MU_DTYPE_F32 && pipe)
     hipLaunchKernelGGL((k_row_col_sums_pipe<float, 4>), dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S,
                        d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, partial);
@@ -986,28 +973,15 @@ static int scale_sweep_impl(int dtype, int64_t n_rows, int64_t n_cols, const int
   }
   const int use_scale = !(scale == 0.0 || scale == 1.0);  // preproc.py:101
   const int G = sweep_grid();
-  // f32: idf slabs of 4 x 8192 columns, one workgroup per CU (r04: 18.2 -> 14.4 ms at 1e6 x 200k, bit-identical;
-  // tune "tfidf_wide" = 1 keeps the 8192-column kernel for comparison)
-  const int abl = mu_tune_get("tfidf_abl");
-  if (dtype == MU_DTYPE_F32 && mu_tune_get("tfidf_wide") != 1 && mu_tune_get("tfidf_pipe") != 1 && abl == 3)
-    hipLaunchKernelGGL((k_tfidf_scale_sweep_pipe<4, 4, 3>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows, n_cols,
-                       S, d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, (const float*)d_idf,
-                       (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
-  else if (dtype == MU_DTYPE_F32 && mu_tune_get("tfidf_wide") != 1 && mu_tune_get("tfidf_pipe") != 1 && abl == 4)
-    hipLaunchKernelGGL((k_tfidf_scale_sweep_pipe<4, 4, 4>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows, n_cols,
-                       S, d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, (const float*)d_idf,
-                       (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
-  else if (dtype == MU_DTYPE_F32 && mu_tune_get("tfidf_wide") != 1 && mu_tune_get("tfidf_pipe") != 1)
+  // f32: idf slabs of 4 x 8192 columns, one workgroup per CU (r04: 18.2 -> 14.4 ms at 1e6 x 200k, bit-identical);
+  // tune "tfidf_pipe" = 1: the same sweep without the software pipeline (the tests' reference)
+  if (dtype == MU_DTYPE_F32 && tune(kTune_tfidf_pipe) != 1)
     hipLaunchKernelGGL((k_tfidf_scale_sweep_pipe<4, 4>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows, n_cols,
                        S, d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, (const float*)d_idf,
                        (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
-  else if (dtype == MU_DTYPE_F32 && mu_tune_get("tfidf_wide") != 1)
+  else if (dtype == MU_DTYPE_F32)
     hipLaunchKernelGGL((k_tfidf_scale_sweep_wide<4, 4>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows, n_cols,
                        S, d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, (const float*)d_idf,
-                       (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
-  else if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_tfidf_scale_sweep<float>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S,
-                       d_indptr, d_indices, (const float*)d_values, sp, d_rowsum, (const float*)d_idf,
                        (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
   else
     hipLaunchKernelGGL(k_tfidf_scale_sweep<double>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols,
@@ -1041,7 +1015,7 @@ int mu_tfidf_scale_sweep_stream(int64_t n_rows, int64_t n_cols, const int64_t* d
     if (rc) return rc;
   }
   const int use_scale = !(scale == 0.0 || scale == 1.0);  // preproc.py:101
-  hipLaunchKernelGGL((k_tfidf_scale_sweep_pipe<4, 4, 0, true>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows,
+  hipLaunchKernelGGL((k_tfidf_scale_sweep_pipe<4, 4, true>), dim3(mu_num_cus()), dim3(kSweepThreads), 0, st, n_rows,
                      n_cols, S, d_indptr, d_indices, d_values, sp, d_rowsum, d_idf, (float)scale, use_scale, flags,
                      d_out, d_zero_count, d_row_dst, (unsigned long long*)d_ent);
   MU_CHECK_LAUNCH();

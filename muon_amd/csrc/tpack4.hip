@@ -295,14 +295,12 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
     int64_t n_rows, int64_t n_cols, int C, int rw, int G, const int64_t* __restrict__ indptr,
     const int64_t* __restrict__ row_dst, const void* __restrict__ src0, const void* __restrict__ src1,
     const int64_t* __restrict__ cdst, const uint32_t* __restrict__ base, const int64_t* __restrict__ coltot,
-    T4Out out, int* __restrict__ err, int abl) {
-  const bool late = (abl & 8) != 0;
+    T4Out out, int* __restrict__ err) {
   __shared__ unsigned long long stage[kCap];  // 80 KiB
   __shared__ uint2 bm[kNW][kMaxC];            // 64 KiB: (wave, column): .x bitmap of the wave's rows, .y its first slot
-  // per column of a tile: pairs << 16 | first staging slot, and where the run goes - TWO sets: a tile is written out
-  // while the next one is being ranked (see the loop)
-  __shared__ uint32_t lrun[2][kMaxC];
-  __shared__ int64_t gdst[2][kMaxC];
+  // per column of a tile: pairs << 16 | first staging slot, and where the run goes
+  __shared__ uint32_t lrun[kMaxC];
+  __shared__ int64_t gdst[kMaxC];
   __shared__ uint32_t wsum[kNW];
   __shared__ int s_flag;
   // Workgroup -> row block, XCD-aware: workgroup w runs on XCD w % 8 (observed dispatch order; for speed only), and the
@@ -411,11 +409,12 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
 
   // ---- phase 4: write-out, one 16-lane group per column, consecutive lanes = consecutive pairs of the run -----------
   // (four columns of a group at a time: their four table entries first, then the four staged pairs, then the four
-  //  stores - three LDS round trips per FOUR columns.)  Two sets of run tables: `late` (tune tpack4_late = 1) runs it ONE
-  //  TILE LATE, between the first and the second barrier of the next tile, so that the stores have a whole tile to drain
-  //  before this wave's next `s_waitcnt vmcnt(0)`.  Measured (profiles/r05_tpack4_ablations.txt): 58.9 against 55.8 ms -
+  //  stores - three LDS round trips per FOUR columns.)  It runs behind the tile's third barrier.  Running it ONE TILE
+  //  LATE, between the first and the second barrier of the next tile, so that the stores have a whole tile to drain
+  //  before this wave's next `s_waitcnt vmcnt(0)`, measured 58.9 against 55.8 ms (profiles/r05_tpack4_ablations.txt):
   //  the drain leaves the top of the tile, and the window requests of phase 3 queue behind the stores instead (phase 3
-  //  160 instead of 74 hundred cycles): the stores cost their ~20 ms wherever they sit.  Not the default.
+  //  160 instead of 74 hundred cycles): the stores cost their ~20 ms wherever they sit.  Retired with its second set of
+  //  run tables.
   auto put = [&](int64_t pos, unsigned long long e) {
     if constexpr (OUT_CSR) {
       out.idx[pos] = (int32_t)(unsigned)e;
@@ -424,7 +423,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
       out.ent[pos] = e;
     }
   };
-  auto write_out = [&](int set, int ncol) {
+  auto write_out = [&](int ncol) {
     const int grp = tid >> 4, s16 = tid & 15;
     for (int c0 = grp; c0 < ncol; c0 += 4 * (kT / 16)) {  // (uniform trip count per wave up to the last round)
       uint32_t lr[4];
@@ -434,25 +433,22 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
       for (int u = 0; u < 4; ++u) {
         const int cl = c0 + u * (kT / 16);
         const bool in = cl < ncol;
-        lr[u] = in ? lrun[set][in ? cl : 0] : 0u;
-        gd[u] = gdst[set][in ? cl : 0];
+        lr[u] = in ? lrun[in ? cl : 0] : 0u;
+        gd[u] = gdst[in ? cl : 0];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint32_t L = lr[u] >> 16, src = lr[u] & 0xffffu;
         e[u] = stage[(uint32_t)s16 < L ? src + s16 : 0];
       }
-      if (abl & 2) continue;  // (timing ablations, tune tpack4_abl: 2 no stores, 4 every run to the start of the target)
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint32_t L = lr[u] >> 16, src = lr[u] & 0xffffu;
-        const int64_t dd = (abl & 4) ? (int64_t)((c0 + u) & 63) * 16 : gd[u];
-        if ((uint32_t)s16 < L) put(dd + s16, e[u]);
-        for (uint32_t i = 16 + s16; i < L; i += 16) put(dd + i, stage[src + i]);  // (a column with more than 16 pairs here)
+        if ((uint32_t)s16 < L) put(gd[u] + s16, e[u]);
+        for (uint32_t i = 16 + s16; i < L; i += 16) put(gd[u] + i, stage[src + i]);  // (a column with more than 16 pairs here)
       }
     }
   };
-  int pend_cols = 0, pend_set = 0, tset = 0;  // the tile staged and not yet written out (its columns, its table set)
 
   int Ct = C;
   int64_t hdr_cb = -1;  // the tile (its first column) whose header sits in / is on its way to v[kH0 ..]
@@ -598,8 +594,8 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
       continue;
     }
     if (tid < Ct) {
-      lrun[tset][tid] = (mine << 16) | my_lpos;  // (both < 2^14: the tile fits the staging buffer)
-      gdst[tset][tid] = gd;
+      lrun[tid] = (mine << 16) | my_lpos;  // (both < 2^14: the tile fits the staging buffer)
+      gdst[tid] = gd;
     }
     {  // the next tile's header, one tile ahead (the registers were taken at the top)
       const int64_t ncb = cb + Ct;
@@ -622,10 +618,6 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
       if (run - my_lpos != mine) atomicOr(err, 1);  // the bitmap and the count pass disagree: never
     }
     mark(2);
-    // the tile before (staged behind ITS third barrier, untouched since: phase 3 below is the next writer of the
-    // staging buffer, behind this tile's second barrier)
-    if (pend_cols > 0) write_out(pend_set, pend_cols);
-    pend_cols = 0;
     __syncthreads();  // B2
     // ---- phase 3: every entry to its slot, from the window registers -------------------------------------------------
     // (eight slots at a time: their eight (bitmap, first slot) pairs first - one LDS round trip - then the eight stores.
@@ -683,20 +675,12 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_num_vgpr(44))) void k_t4_
     issue_all();
     mark(3);
     __syncthreads();  // B3: the staged tile is complete
-    // ---- phase 4: the write-out (tune tpack4_late = 1: one tile late, between the next tile's first two barriers) ----
-    if (late) {
-      pend_cols = cend - cbase;
-      pend_set = tset;
-      tset ^= 1;
-    } else {
-      write_out(tset, cend - cbase);
-    }
+    // ---- phase 4: the write-out ----
+    write_out(cend - cbase);
     mark(4);
     cb += Ct;
     Ct = C;
   }
-  // (the last staged tile; the barrier orders it behind every wave's phase 3 - it is the third barrier of that tile)
-  if (pend_cols > 0) write_out(pend_set, pend_cols);
   t4_wait_all();  // (the windows requested for a tile that does not exist)
   if (DBG && tid == 0)
     for (int i = 0; i < 6; ++i) atomicAdd(&g_t4_phase[i], ph[i]);
@@ -719,11 +703,11 @@ inline T4Geo t4_geometry(int64_t n_rows, int64_t n_cols, int64_t nnz) {
   q.G = (int)((n_rows + q.rpb - 1) / q.rpb);
   if (q.G < 1) q.G = 1;
   // tile width: the block's pairs of a tile fill ~88 % of the staging buffer, and a row has ~m entries in a tile
-  // (tune tpack4_m, default 16: measured on the bench matrix - whose rows are burstier than Poisson - 14 / 16 / 18
+  // (m = 16: measured on the bench matrix - whose rows are burstier than Poisson - 14 / 16 / 18
   //  entries per row and tile retried 0.1 / 3 / 50 % of the tiles with ONE overflow slot per wave)
   const double per_col = (double)nnz / (double)q.G / (double)(n_cols > 0 ? n_cols : 1);
   double Cc = per_col > 0 ? 0.88 * kCap / per_col : (double)kMaxC;
-  const int m = mu_tune_get("tpack4_m") > 0 ? mu_tune_get("tpack4_m") : 16;
+  const int m = 16;
   const double row_avg = (double)nnz / (double)(n_rows > 0 ? n_rows : 1);
   const double Cm = row_avg > 0 ? (double)m * (double)n_cols / row_avg : (double)kMaxC;
   if (Cm < Cc) Cc = Cm;
@@ -731,7 +715,7 @@ inline T4Geo t4_geometry(int64_t n_rows, int64_t n_cols, int64_t nnz) {
   C = (C / 32) * 32;
   if (C < 32) C = 32;
   if (C > kMaxC) C = kMaxC;
-  if (mu_tune_get("tpack4_c") > 0) C = mu_tune_get("tpack4_c");
+  if (tune(kTune_tpack4_c) > 0) C = tune(kTune_tpack4_c);
   if (C > kMaxC) C = kMaxC;
   if (C < 16) C = 16;
   q.C = (int)C;
@@ -783,19 +767,19 @@ int t4_fill_impl(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_i
   hipLaunchKernelGGL(k_t4_cdst, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, n_cols, d_cptr, d_inv,
                      w.cdst);
   MU_CHECK_LAUNCH();
-  const bool dbg = mu_tune_get("tpack_dbg") > 0;
-  const bool xcd = mu_tune_get("tpack4_plain") != 1;  // (tune tpack4_plain = 1: workgroup = row block, for comparison)
+  const bool dbg = tune(kTune_tpack_dbg) > 0;
+  const bool xcd = tune(kTune_tpack4_plain) != 1;  // (tune tpack4_plain = 1: workgroup = row block, for comparison)
   const unsigned grid = xcd ? (unsigned)(8 * ((q.G + 7) / 8)) : (unsigned)q.G;
 #define MU_T4_LAUNCH(PAIRS_, DBG_, CSR_, RD_, S0_, S1_) MU_T4_LAUNCH4(PAIRS_, DBG_, CSR_, false, RD_, S0_, S1_)
 #define MU_T4_LAUNCH4(PAIRS_, DBG_, CSR_, CIRC_, RD_, S0_, S1_)                                                        \
   hipLaunchKernelGGL((k_t4_fill<PAIRS_, DBG_, CSR_, CIRC_>), dim3(grid), dim3(kT), 0, st, n_rows, n_cols, q.C, q.rw,    \
                      xcd ? q.G : -q.G, d_indptr, RD_, (const void*)(S0_), (const void*)(S1_), w.cdst, w.cnt, w.coltot,  \
-                     out, w.err, mu_tune_get("tpack4_abl") | (mu_tune_get("tpack4_late") == 1 ? 8 : 0))
+                     out, w.err)
   const bool csr_out = out.idx != nullptr;
   const int64_t* no_rd = nullptr;
   // (circular windows: the row stream as source, 256-byte aligned - the lane of a pair is its number mod 32
   //  - the default; tune tpack4_circ = 2: plain windows, for comparison)
-  const bool circ = mu_tune_get("tpack4_circ") != 2 && (reinterpret_cast<uintptr_t>(d_x_ent) & 255) == 0;
+  const bool circ = tune(kTune_tpack4_circ) != 2 && (reinterpret_cast<uintptr_t>(d_x_ent) & 255) == 0;
   if (d_x_ent && dbg && !csr_out) MU_T4_LAUNCH(true, true, false, d_row_dst, d_x_ent, nullptr);
   else if (d_x_ent && !csr_out && circ) MU_T4_LAUNCH4(true, false, false, true, d_row_dst, d_x_ent, nullptr);
   else if (d_x_ent && !csr_out) MU_T4_LAUNCH(true, false, false, d_row_dst, d_x_ent, nullptr);

@@ -590,7 +590,7 @@ static int tperm_fill(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t
   int G = 0;
   mu_tpack4_geometry(n_rows, n_cols, nnz, &rpb, &G, nullptr);
   const int rw = (int)(rpb / kNW);
-  const bool xcd = mu_tune_get("tpack4_plain") != 1;
+  const bool xcd = tune(kTune_tpack4_plain) != 1;
   const unsigned grid = xcd ? (unsigned)(8 * ((G + 7) / 8)) : (unsigned)G;
   if (d_phases)
     hipLaunchKernelGGL(k_tperm_phases, dim3(grid), dim3(kT), 0, (hipStream_t)stream, n_rows, n_cols, rw, xcd ? G : -G,

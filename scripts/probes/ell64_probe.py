@@ -127,15 +127,10 @@ def main():
             out = product(be, L, Q, n, d, waves)
             err = float((out - ref).abs().max() / ref.abs().max())
             same = bool(torch.equal(out, ref))
-            ts = []
-            for mode in (0, 1, 2, 3, 4, 7):
-                be.tune("ell_mode", mode)
-                ts.append(timed(lambda: product(be, L, Q, n, d, waves)))
-            be.tune("ell_mode", 0)
+            t = timed(lambda: product(be, L, Q, n, d, waves))
             wgs = -(-L["n_waves"] // waves)
-            line += (f"\n   waves {waves} ({wgs} wgs): {ts[0]:.3f} ms ({alg / ts[0] / 1e6:.0f} GB/s algorithmic; err {err:.1e}, bit-identical to "
-                     f"k_spmm_win {same}) | no gathers {ts[1]:.3f} | no slab copies {ts[2]:.3f} | neither {ts[3]:.3f} | overflow ignored {ts[4]:.3f} | "
-                     f"all three {ts[5]:.3f}")
+            line += (f"\n   waves {waves} ({wgs} wgs): {t:.3f} ms ({alg / t / 1e6:.0f} GB/s algorithmic; err {err:.1e}, bit-identical to "
+                     f"k_spmm_win {same})")
         print(line, flush=True)
         del L
 

@@ -46,16 +46,10 @@ def main():
         same = bool(torch.equal(out, be.spmm(E, Q)))
         line = (f"[{name}] plan waves {E.waves}; slots/nnz {E.slots / M.nnz:.3f} build {t_build:.2f}s err {err:.2e} "
                 f"reproducible {same}")
-        n_waves = -(-rows // 16)
-        for w, ragged in ((15, 0), (14, 0), (13, 0), (12, 0)):
+        for w in (15, 14, 13, 12):
             E.waves = w
-            ts = []
-            for mode in (0, 1, 2, 3):
-                be.tune("ell_mode", mode | ragged)
-                ts.append(timed(lambda: be.spmm(E, Q)))
-            be.tune("ell_mode", 0)
-            line += (f"\n      waves {w:2d} : {ts[0]:.3f} ms ({E.slots * 6 / ts[0] / 1e6:.0f} GB/s)"
-                     f" | no gathers {ts[1]:.3f} | no slab copies {ts[2]:.3f} | neither {ts[3]:.3f}")
+            t = timed(lambda: be.spmm(E, Q))
+            line += f"\n      waves {w:2d} : {t:.3f} ms ({E.slots * 6 / t / 1e6:.0f} GB/s)"
         print(line, flush=True)
         del E, out
         # f64 blocks (512-column slabs)
@@ -66,13 +60,8 @@ def main():
         line = f"[{name}] f64 blocks: slots/nnz {E.slots / M.nnz:.3f} waves {E.waves} err vs f32 {err:.2e}"
         for w in (15, 14, 12):
             E.waves = w
-            ts = []
-            for mode in (0, 1, 2, 3):
-                be.tune("ell_mode", mode)
-                ts.append(timed(lambda: be.spmm(E, Q64)))
-            be.tune("ell_mode", 0)
-            line += (f"\n      waves {w:2d}: {ts[0]:.3f} ms ({E.slots * 6 / ts[0] / 1e6:.0f} GB/s)"
-                     f" | no gathers {ts[1]:.3f} | no slab copies {ts[2]:.3f} | neither {ts[3]:.3f}")
+            t = timed(lambda: be.spmm(E, Q64))
+            line += f"\n      waves {w:2d}: {t:.3f} ms ({E.slots * 6 / t / 1e6:.0f} GB/s)"
         print(line, flush=True)
         del Q, ref, E, Q64, ref64
 

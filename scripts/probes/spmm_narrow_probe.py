@@ -47,13 +47,6 @@ def main():
         new = be.spmm(S, Q).clone()
         again = be.spmm(S, Q).clone()
         t_new = timed(lambda: be.spmm(S, Q))
-        be.tune("spmm_mode", 2)  # timing ablation: half windows (results wrong on purpose)
-        t_half = timed(lambda: be.spmm(S, Q))
-        be.tune("spmm_mode", 0)
-        be.tune("spmm_mode", 3)  # A/B: the LDS staging row instead of lane swaps (same results up to summation order)
-        t_swap = timed(lambda: be.spmm(S, Q))
-        be.tune("spmm_mode", 4)  # ablation: no gathers / FMAs
-        t_nog = timed(lambda: be.spmm(S, Q))
         be.tune("spmm_mode", 6)  # cycle accounting: per wave sums of s_memtime differences replace the product
         acct = be.spmm(S, Q)
         be.tune("spmm_mode", 0)
@@ -63,12 +56,6 @@ def main():
         print(f"{name:6s}: accounting (share of a wave's time): window wait + count {a[:, 0].mean().item() / tot:.2f}, "
               f"mask + spread + request {a[:, 1].mean().item() / tot:.2f}, gathers + FMAs {a[:, 2].mean().item() / tot:.2f}, "
               f"slab barrier {a[:, 3].mean().item() / tot:.2f}; ticks per wave {tot:.0f}", flush=True)
-        be.tune("spmm_mode", 5)  # ablation: every request = the next 32 pairs of one sequential stream per wave
-        t_seq = timed(lambda: be.spmm(S, Q))
-        be.tune("spmm_mode", 0)
-        print(f"{name:6s}: sequential 32-pair requests per wave (ablation) {t_seq:.3f} ms", flush=True)
-        print(f"{name:6s}: narrow kernel with 32-entry requests (ablation) {t_half:.3f} ms, through an LDS staging row {t_swap:.3f} ms, "
-              f"without gathers / FMAs (ablation) {t_nog:.3f} ms", flush=True)
         scale = ref.abs().max().item()
         err = (new - ref).abs().max().item() / scale
         gb = (8.0 * X.nnz + 4 * 16 * (n + d)) / 1e9

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """r05 operand-building probe on the bench matrix: the TF-IDF scale sweep with / without the row stream, the
 transposition's third generation (alone and next to the streaming copy, as lsi ran it in r04) against the fourth
-(csrc/tpack4.hip: CSR source, row-stream source), their output bytes compared, the fourth generation's phase cycles
-and a sweep of its tile-width parameter.  Usage: tpack4_probe.py [cells] [--sweep]"""
+(csrc/tpack4.hip: CSR source, row-stream source), their output bytes compared, and the fourth generation's phase
+cycles.  Usage: tpack4_probe.py [cells]"""
 import ctypes
 import os
 import sys
@@ -128,13 +128,3 @@ del r_
 print(f"v4 with workgroup = row block (no XCD-aware order): {ms:.2f} ms", flush=True)
 phases("plain order")
 be.tune("tpack4_plain", 0)
-if "--sweep" in sys.argv:
-    for m in (14, 15, 17):
-        be.tune("tpack4_m", m)
-        ms, r_ = timed(lambda: be.stream_both(T))
-        del r_
-        g = (ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0))
-        be.lib.mu_tpack4_geometry(cells, peaks, T.nnz, ctypes.byref(g[0]), ctypes.byref(g[1]), ctypes.byref(g[2]))
-        print(f"v4 m = {m} (tile {g[2].value} columns, {g[1].value} blocks of {g[0].value} rows): {ms:.2f} ms", flush=True)
-        phases(f"m = {m}")
-    be.tune("tpack4_m", 0)

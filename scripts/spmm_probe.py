@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """The row-stream SpMM (mu_spmm_stream_f32) in both directions on the bench matrix: launch times,
-the cost of building the operands, timing ablations and the per-wave cycle accounting of the kernel
-(spmm_mode 64).  Used bare or under rocprofv3 (--kernel-trace --stats, or --pmc in a separate pass).
+the cost of building the operands and the per-wave cycle accounting of the kernel (spmm_mode 64).  Used bare or under rocprofv3 (--kernel-trace --stats, or --pmc in a separate pass).
 (r02a-j compared it with the r01 packed kernel, bit for bit: gpurun_out/r02h.)"""
 import argparse
 import os
@@ -17,11 +16,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--cells", type=int, default=125000)
 ap.add_argument("--peaks", type=int, default=200000)
 ap.add_argument("--reps", type=int, default=4)
-ap.add_argument("--modes", default="1,9,32,64,96")
 ap.add_argument("--no-packed", action="store_true")
 ap.add_argument("--B", type=int, default=64)
 ap.add_argument("--ks", default="", help="also time layouts dealt for these K (row-sets per wave)")
-ap.add_argument("--k-modes", default="", help="ablation modes to time on the --ks layouts as well")
 ap.add_argument("--slab", type=int, default=0, choices=(0, 256, 320),
                 help="Q slab width (tune key spmm_slab): 0 = the backend's rule, 256 / 320 forced where an instance exists")
 ap.add_argument("--account", action="store_true",
@@ -67,7 +64,6 @@ print(f"transpose_stream(X): {ms:8.3f} ms", flush=True)
 B = args.B
 Q = be.randn(args.peaks, B, 1)
 Yn = be.spmm(Ts, Q)
-Zn = be.spmm(Tts, Yn)
 torch.cuda.synchronize()
 if args.cells <= 500000:  # (a third 8 B/nnz copy: not next to the 1e6-row operands)
     Y0 = be.spmm(be.stream(T, sort_rows=False), Q)
@@ -109,35 +105,11 @@ if args.account:
     account(A8, Q, "X*Q ")
     account(At8, Yn, "Xt*Y")
     del A8, At8
-for M, D, tag in ((Ts, Q, "X*Q "), (Tts, Yn, "Xt*Y")):
-    if M.k != 8 and not all(int(m) in (4096, 16384, 262144) for m in args.modes.split(",") if m):
-        continue
-    for mode in [int(m) for m in args.modes.split(",") if m]:
-        be.tune("spmm_mode", mode)
-        be.tune("spmm_slab", args.slab if mode == 64 else 256)  # (the accounting is the only ablation with a 320-column instance)
-        bench(f"{tag} stream mode {mode:2d}", M, D)
-        if mode & 64:
-            t = be.spmm(M, D)
-            nw = M.n_pos // (64 * M.k) * 16
-            tt = t.reshape(-1)[: nw * B].reshape(nw, B)[:, :5].double()
-            width = be.spmm_slab(M.k, M.n_pos, B)
-            passes = -(-M.shape[1] // width) * M.k
-            print("   cycles per pass and wave: " + ", ".join(f"{n} {float(tt[:, i].mean()) / passes:7.1f}" for i, n in enumerate(names))
-                  + f"; sum {float(tt.sum(dim=1).mean()) / passes:7.1f}", flush=True)
-    be.tune("spmm_mode", 0)
-    be.tune("spmm_slab", args.slab)
 
 for K in [int(k) for k in args.ks.split(",") if k]:
-    for mode in [0] + [int(m) for m in args.k_modes.split(",") if m]:
-        be.tune("spmm_mode", mode)
-        A = be.stream(T, K=K)
-        bench(f"X*Q  stream K={K} mode {mode} ({A.n_pos // (64 * K)} workgroups)", A, Q)
-        if mode:
-            print("   vs mode 0:", "bit-identical" if torch.equal(be.spmm(A, Q), Yn) else "DIFFERS", flush=True)
-        del A
-        At = be.transpose_stream(T, K=K)
-        bench(f"Xt*Y stream K={K} mode {mode} ({At.n_pos // (64 * K)} workgroups)", At, Yn)
-        if mode:
-            print("   vs mode 0:", "bit-identical" if torch.equal(be.spmm(At, Yn), Zn) else "DIFFERS", flush=True)
-        del At
-    be.tune("spmm_mode", 0)
+    A = be.stream(T, K=K)
+    bench(f"X*Q  stream K={K} ({A.n_pos // (64 * K)} workgroups)", A, Q)
+    del A
+    At = be.transpose_stream(T, K=K)
+    bench(f"Xt*Y stream K={K} ({At.n_pos // (64 * K)} workgroups)", At, Yn)
+    del At
