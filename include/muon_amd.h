@@ -947,6 +947,22 @@ int mu_rna_value_sweep(int dtype, int64_t n, int64_t nnz, const int64_t* d_indpt
 int mu_shift_cols_f32(int64_t n, int B, float* d_Y, const double* d_m, void* stream);
 int mu_scale_rows_f32(int64_t d, int B, const float* d_s, const float* d_Q, float* d_out, void* stream);
 
+/* ---- muon.tl.mofa with smooth_covariate (MEFISTO): the eigen route's two passes over the eigenvectors of a factor's
+ * prior covariance (csrc/gp.hip, C-ABI v813) -----------------------------------------------------------------
+ * d_V [n x n] f64 row-major with leading dimension ldv >= n; every vector f64 [n]; 1 <= n <= 2^22 (n = 0: nothing is done).
+ *   mu_gp_project_f64:   d_u = V^T d_r.  Panels of 256 rows write partial sums to d_work [ceil(n / 256) x n]
+ *     (mu_gp_project_worksize bytes): within a panel a column's products are added in four chains (row mod 4), then
+ *     ((c0 + c1) + c2) + c3; a second kernel adds the panels in panel order.
+ *   mu_gp_posterior_f64: d_m[i] = sum_j V[i,j] d_g[j] d_u[j] and d_dc[i] = sum_j V[i,j]^2 d_g[j] from ONE read of row i.
+ *     A wave per row: lane l adds the terms j = l, l + 64, ... in four chains (j / 64 mod 4), added as above, and the lane
+ *     sums are combined by a tree over the lane offsets 32, 16, .. 1.
+ * No atomics; two calls agree bit for bit.  Arguments are checked before any HIP call. */
+size_t mu_gp_project_worksize(int64_t n);
+int mu_gp_project_f64(int64_t n, const double* d_V, int64_t ldv, const double* d_r, double* d_u, void* d_work,
+                      size_t work_bytes, void* stream);
+int mu_gp_posterior_f64(int64_t n, const double* d_V, int64_t ldv, const double* d_g, const double* d_u, double* d_m,
+                        double* d_dc, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

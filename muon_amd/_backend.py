@@ -1699,6 +1699,37 @@ class HipBackend(OperatorSet):
                                                _p(viol), _p(work), wb, int(max_blocks), self._stream()))
         return gram, viol
 
+    # -- muon.tl.mofa with smooth_covariate (csrc/gp.hip) --------------------------------------------------------------
+    @staticmethod
+    def _gp_square(V, *vs):
+        f64 = torch.float64
+        assert V.dtype == f64 and V.dim() == 2 and V.shape[0] == V.shape[1]
+        n = int(V.shape[0])
+        assert n <= 1 or (V.stride(1) == 1 and V.stride(0) >= n)
+        for v in vs:
+            assert v.dtype == f64 and tuple(v.shape) == (n,) and v.is_contiguous() and v.device == V.device
+        return n, (int(V.stride(0)) if n > 1 else n)
+
+    def gp_project(self, V, r):
+        """``V^T r`` for the n x n f64 matrix ``V`` (row-major; a row stride of n or more) and the f64 vector ``r``: one
+        pass over V, every sum in the order include/muon_amd.h states - two calls agree bit for bit."""
+        n, ldv = self._gp_square(V, r)
+        u = self.empty((n,), torch.float64)
+        wb = int(self.lib.mu_gp_project_worksize(n))
+        work = self.empty((max(wb, 8),), torch.uint8)
+        with self._dev_ctx():
+            check(self.lib.mu_gp_project_f64(n, _p(V), ldv, _p(r), _p(u), _p(work), wb, self._stream()))
+        return u
+
+    def gp_posterior(self, V, g, u):
+        """``(V (g o u), (V o V) g)`` from one pass over the n x n f64 matrix ``V``: the posterior mean and the
+        diagonal of the posterior covariance of a factor on MEFISTO's eigen route.  Two calls agree bit for bit."""
+        n, ldv = self._gp_square(V, g, u)
+        m, dc = self.empty((n,), torch.float64), self.empty((n,), torch.float64)
+        with self._dev_ctx():
+            check(self.lib.mu_gp_posterior_f64(n, _p(V), ldv, _p(g), _p(u), _p(m), _p(dc), self._stream()))
+        return m, dc
+
     # -- muon_amd.rna.pp / muon_amd.tl.pca (csrc/rna.hip) --------------------------------------------------------------
     def gene_moments_max_blocks(self) -> int:
         """The workgroups ``gene_moments`` launches at most when no cap is given."""

@@ -464,7 +464,6 @@ class GeneralMofaEngine(MofaDriver):
         for g, (a0, b0) in enumerate(self.gslice):
             for lo in range(a0, b0, step):
                 hi = min(b0, lo + step)
-                Zc, Z2c = self.EZ[lo:hi], self.EZ2[lo:hi]
                 # (views whose share is a product come first and START the sums - see _update_w; row-constant shares
                 #  and chunk-walked views add to them)
                 S = a = None
@@ -501,35 +500,46 @@ class GeneralMofaEngine(MofaDriver):
                         else:
                             S[l2 - lo:h2 - lo] += Om @ WW[m]
                         a[l2 - lo:h2 - lo] += R @ self.W[m].EW
-                S = S.reshape(hi - lo, K, K)
-                ssf = self.opts["spikeslab_factors"]
-                if has(self.be, "mofa_gs_update") and K <= 32:
-                    # (row slices of contiguous [N, K] tensors are contiguous: updated in place)
-                    if ssf:  # the W form of the sweep: (alpha, ln theta, ln(1 - theta)) of this group
-                        self.be.mofa_gs_update(S.contiguous(), a.contiguous(), az[g].to(torch.float64).contiguous(),
-                                               self.lthz[g].contiguous(), self.l1mthz[g].contiguous(), True, Zc, Z2c,
-                                               self.gamma_z[lo:hi], self.EZh2[lo:hi], self.sig2z[lo:hi])
-                    else:
-                        self.be.mofa_gs_update(S.contiguous(), a.contiguous(), az[g].to(torch.float64).contiguous(), None,
-                                               None, False, Zc, Z2c, None, None, self.sig2z[lo:hi])
-                    continue
-                for k in range(K):
-                    num = a[:, k] - (Zc * S[:, k, :]).sum(dim=1) + Zc[:, k] * S[:, k, k]
-                    prec = az[g, k] + S[:, k, k]
-                    s2 = 1.0 / prec
-                    mu = num * s2
-                    if ssf:
-                        lam = ((self.lthz[g, k] - self.l1mthz[g, k]).to(self.T) + 0.5 * torch.log(az[g, k]) - 0.5 * torch.log(prec)
-                               + 0.5 * num * num * s2)
-                        gz = torch.sigmoid(lam)
-                        Zc[:, k] = gz * mu
-                        Z2c[:, k] = gz * (mu * mu + s2)
-                        self.gamma_z[lo:hi, k] = gz
-                        self.EZh2[lo:hi, k] = gz * (mu * mu + s2) + (1.0 - gz) / az[g, k]
-                    else:
-                        Zc[:, k] = mu
-                        Z2c[:, k] = mu * mu + s2
-                    self.sig2z[lo:hi, k] = s2
+                self._sweep_z(g, lo, hi, S.reshape(hi - lo, K, K), a, az)
+        self._finish_z()
+
+    def _sweep_z(self, g, lo, hi, S, a, az):
+        """The factors of the samples lo..hi (group ``g``) from their statistics ``a`` [rows, K] and ``S`` [rows, K, K]:
+        one Gauss-Seidel sweep over the factors per sample, in place.  (A prior that couples the samples overrides this
+        and ``_finish_z``: _core/mefisto.py.)"""
+        K = self.K
+        Zc, Z2c = self.EZ[lo:hi], self.EZ2[lo:hi]
+        ssf = self.opts["spikeslab_factors"]
+        if has(self.be, "mofa_gs_update") and K <= 32:
+            # (row slices of contiguous [N, K] tensors are contiguous: updated in place)
+            if ssf:  # the W form of the sweep: (alpha, ln theta, ln(1 - theta)) of this group
+                self.be.mofa_gs_update(S.contiguous(), a.contiguous(), az[g].to(torch.float64).contiguous(),
+                                       self.lthz[g].contiguous(), self.l1mthz[g].contiguous(), True, Zc, Z2c,
+                                       self.gamma_z[lo:hi], self.EZh2[lo:hi], self.sig2z[lo:hi])
+            else:
+                self.be.mofa_gs_update(S.contiguous(), a.contiguous(), az[g].to(torch.float64).contiguous(), None,
+                                       None, False, Zc, Z2c, None, None, self.sig2z[lo:hi])
+            return
+        for k in range(K):
+            num = a[:, k] - (Zc * S[:, k, :]).sum(dim=1) + Zc[:, k] * S[:, k, k]
+            prec = az[g, k] + S[:, k, k]
+            s2 = 1.0 / prec
+            mu = num * s2
+            if ssf:
+                lam = ((self.lthz[g, k] - self.l1mthz[g, k]).to(self.T) + 0.5 * torch.log(az[g, k]) - 0.5 * torch.log(prec)
+                       + 0.5 * num * num * s2)
+                gz = torch.sigmoid(lam)
+                Zc[:, k] = gz * mu
+                Z2c[:, k] = gz * (mu * mu + s2)
+                self.gamma_z[lo:hi, k] = gz
+                self.EZh2[lo:hi, k] = gz * (mu * mu + s2) + (1.0 - gz) / az[g, k]
+            else:
+                Zc[:, k] = mu
+                Z2c[:, k] = mu * mu + s2
+            self.sig2z[lo:hi, k] = s2
+
+    def _finish_z(self):
+        """After the last chunk of a Z update (nothing to do where the samples are independent a priori)."""
 
     def _bump_z(self):
         self._zver += 1
@@ -635,12 +645,40 @@ class GeneralMofaEngine(MofaDriver):
             for V, Wm in zip(self.views, self.W):
                 be.mofa_w_elbo(Wm.EWh2, Wm.gamma, Wm.sig2, o["ard_weights"], o["spikeslab_weights"], A0 + 0.5 * V.D, A0, B0,
                                TH_A0, TH_B0, Wm.alpha, Wm.lalpha, Wm.lth, Wm.l1mth, elbo, work)
+            return self._factor_terms(elbo) + lik
+        # ---- prior / entropy terms (the same expressions as oracle run()) ----------------------------------
+        elbo = lik
+        for m, (V, Wm) in enumerate(zip(self.views, self.W)):
+            aw = Wm.alpha if o["ard_weights"] else torch.ones((K,), dtype=f64, device=self.dev)
+            law = Wm.lalpha if o["ard_weights"] else torch.zeros((K,), dtype=f64, device=self.dev)
+            gam, EWh2, sig2 = Wm.gamma.to(f64), Wm.EWh2.to(f64), Wm.sig2.to(f64)
+            elbo = elbo + (0.5 * law - 0.5 * aw * EWh2).sum()
+            elbo = elbo + (gam * 0.5 * torch.log(sig2) + (1 - gam) * 0.5 * torch.log(1.0 / aw) + 0.5).sum()
+            if o["spikeslab_weights"]:
+                elbo = elbo + (gam * Wm.lth + (1 - gam) * Wm.l1mth).sum()
+                ent = -(torch.xlogy(gam, gam) + torch.xlogy(1 - gam, 1 - gam))
+                elbo = elbo + torch.nan_to_num(ent).sum()
+                sg = gam.sum(dim=0)
+                a, b = TH_A0 + sg, TH_B0 + V.D - sg
+                elbo = elbo + _beta_kl(TH_A0, TH_B0, a, b, Wm.lth, Wm.l1mth).sum()
+            if o["ard_weights"]:
+                a = torch.full((K,), A0 + 0.5 * V.D, dtype=f64, device=self.dev)
+                b = B0 + 0.5 * EWh2.sum(dim=0)
+                elbo = elbo + _gamma_kl(A0, B0, a, b, aw, law).sum()
+        return self._factor_terms(elbo)
+
+    def _factor_terms(self, elbo):
+        """The factors' ARD (and sparsity) nodes from the current <Z>, and ``elbo`` plus the factors' prior / entropy
+        terms.  (The part of an iteration that a different prior on the factors replaces: _core/mefisto.py.)"""
+        o, K, G, be = self.opts, self.K, self.G, self.be
+        f64 = torch.float64
+        if self._fused_small:
             zs = self._zs
             for g, (a0, b0) in enumerate(self.gslice):
-                be.mofa_z_sums(self.EZ2, self.sig2z, a0, b0, zs[g], work)
+                be.mofa_z_sums(self.EZ2, self.sig2z, a0, b0, zs[g], self._elbo_work)
             self._allreduce(zs)
             be.mofa_z_elbo(zs, self._Ng_dev, o["ard_factors"], A0, B0, self.alpha_z, self.lalpha_z, elbo)
-            return elbo + lik
+            return elbo
         # factors: per-group sums over this rank's samples, added up over the ranks
         ssf = o["spikeslab_factors"]
         zs = torch.zeros((G, 5 if ssf else 2, K), dtype=f64, device=self.dev)
@@ -666,25 +704,6 @@ class GeneralMofaEngine(MofaDriver):
             a, b = TH_A0 + zs[:, 2], TH_B0 + Ng[:, None] - zs[:, 2]
             self.lthz.copy_(torch.digamma(a) - torch.digamma(a + b))
             self.l1mthz.copy_(torch.digamma(b) - torch.digamma(a + b))
-        # ---- prior / entropy terms (the same expressions as oracle run()) ----------------------------------
-        elbo = lik
-        for m, (V, Wm) in enumerate(zip(self.views, self.W)):
-            aw = Wm.alpha if o["ard_weights"] else torch.ones((K,), dtype=f64, device=self.dev)
-            law = Wm.lalpha if o["ard_weights"] else torch.zeros((K,), dtype=f64, device=self.dev)
-            gam, EWh2, sig2 = Wm.gamma.to(f64), Wm.EWh2.to(f64), Wm.sig2.to(f64)
-            elbo = elbo + (0.5 * law - 0.5 * aw * EWh2).sum()
-            elbo = elbo + (gam * 0.5 * torch.log(sig2) + (1 - gam) * 0.5 * torch.log(1.0 / aw) + 0.5).sum()
-            if o["spikeslab_weights"]:
-                elbo = elbo + (gam * Wm.lth + (1 - gam) * Wm.l1mth).sum()
-                ent = -(torch.xlogy(gam, gam) + torch.xlogy(1 - gam, 1 - gam))
-                elbo = elbo + torch.nan_to_num(ent).sum()
-                sg = gam.sum(dim=0)
-                a, b = TH_A0 + sg, TH_B0 + V.D - sg
-                elbo = elbo + _beta_kl(TH_A0, TH_B0, a, b, Wm.lth, Wm.l1mth).sum()
-            if o["ard_weights"]:
-                a = torch.full((K,), A0 + 0.5 * V.D, dtype=f64, device=self.dev)
-                b = B0 + 0.5 * EWh2.sum(dim=0)
-                elbo = elbo + _gamma_kl(A0, B0, a, b, aw, law).sum()
         az = self.alpha_z if o["ard_factors"] else torch.ones((G, K), dtype=f64, device=self.dev)
         laz = self.lalpha_z if o["ard_factors"] else torch.zeros((G, K), dtype=f64, device=self.dev)
         for g in range(G):

@@ -9,10 +9,11 @@ products, PyTorch-ROCm for the dense blocks.
 
 Deliberate deviations, all explicit:
   * sparse modalities are NOT densified (tools.py:117-141 does ``.todense()``);
-  * only the Gaussian likelihood is implemented: views whose likelihood the reference's default
-    would GUESS as bernoulli / poisson are modelled as gaussian with a warning; asking for them
-    explicitly, SVI and MEFISTO (smooth_*) raise NotImplementedError (``spikeslab_factors=True`` runs, on the
-    general engine: ``_needs_general_engine``);
+  * poisson / bernoulli views, element-wise NaN and ``spikeslab_factors=True`` run on the general engine
+    (``_needs_general_engine``); SVI raises NotImplementedError;
+  * MEFISTO (``smooth_covariate``) runs on ``mefisto.SmoothMofaEngine`` (one covariance over all samples, a lengthscale
+    grid of our own: parity with mofapy2 unpinned); its warping, sparse-GP and group-kernel options raise
+    NotImplementedError (``_smooth_options``);
   * a bad ``groups_label`` raises ValueError where the reference calls ``sys.exit()`` (:106-113);
   * the model file is HDF5 (mofapy2's layout) when h5py is importable; otherwise ``outfile`` +
     ".npz" (NumPy archive, with a warning); results reach the write-back directly, not through it.
@@ -165,6 +166,77 @@ def _needs_general_engine(backend, views, lik, groups, n_factors, spikeslab_fact
     return bool(local) or wide or not two_pass_fits(len(views), n_groups, K)
 
 
+# the reference's defaults of smooth_kwargs (/root/reference/muon/_core/tools.py:531-545; ``covariates_names`` defaults to
+# ``smooth_covariate`` itself)
+SMOOTH_DEFAULTS = dict(scale_cov=False, start_opt=20, n_grid=20, opt_freq=10, model_groups=True, warping_freq=20,
+                       warping_ref=0, warping_open_begin=True, warping_open_end=True, sparseGP=False, frac_inducing=None,
+                       new_values=None)
+
+
+def _smooth_options(smooth_covariate, smooth_warping, smooth_kwargs):
+    """The MEFISTO options as the reference merges them (tools.py:531-562): ``smooth_kwargs`` over the defaults, plus
+    ``warping``.  None without ``smooth_covariate``: the reference then ignores the other two (:564)."""
+    if smooth_covariate is None:
+        return None
+    opts = {"covariates_names": smooth_covariate, **SMOOTH_DEFAULTS, **dict(smooth_kwargs or {})}
+    opts["warping"] = smooth_warping
+    return opts
+
+
+def _smooth_new_values(opts):
+    """``new_values`` as the reference hands them to ``predict_factor`` (tools.py:587-597): [P, C], a 1-d list as one
+    column; None when there is nothing to interpolate."""
+    nv = opts["new_values"]
+    if nv is None or len(nv) == 0:
+        return None
+    nv = np.array(nv, dtype=np.float64)
+    return nv.reshape(-1, 1) if nv.ndim == 1 else nv
+
+
+def _check_smooth_options(opts, n_groups, spikeslab_factors, comm):
+    """What of MEFISTO is not built raises, naming the option."""
+    from .._comm import default_comm
+
+    if opts["warping"]:
+        raise NotImplementedError("smooth_warping=True (aligning the covariate across groups) is not implemented")
+    if opts["sparseGP"]:
+        raise NotImplementedError("smooth_kwargs['sparseGP']=True (inducing points) is not implemented")
+    if opts["frac_inducing"] is not None:
+        raise NotImplementedError("smooth_kwargs['frac_inducing'] (inducing points) is not implemented")
+    if opts["model_groups"] and n_groups > 1:
+        raise NotImplementedError("smooth_kwargs['model_groups']=True with more than one group (a group kernel) is not "
+                                  "implemented: pass model_groups=False for one covariance over all samples")
+    if default_comm(comm).world_size > 1:
+        raise NotImplementedError("smooth_covariate runs on one rank")
+    if spikeslab_factors:
+        raise ValueError("spikeslab_factors=True cannot be combined with smooth_covariate (the factors' prior is the "
+                         "Gaussian process)")
+
+
+def _smooth_covariates(obs, obs_names, smooth_covariate, opts):
+    """(covariates [N, C] f64 in the model's sample order, their names, (mean, std) of ``scale_cov`` or None)."""
+    cols = [smooth_covariate] if isinstance(smooth_covariate, str) else list(smooth_covariate)
+    for c in cols:
+        if c not in obs.columns:
+            raise KeyError(f"smooth_covariate: there is no column {c!r} in .obs")
+    names = opts["covariates_names"]
+    names = [names] if isinstance(names, str) else [str(n) for n in names]
+    if len(names) != len(cols):
+        raise ValueError(f"covariates_names has {len(names)} entries for {len(cols)} covariates")
+    try:
+        cov = np.column_stack([np.asarray(obs.loc[obs_names, c].values, dtype=np.float64) for c in cols])
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"smooth_covariate: the columns {cols} must be numeric ({e})") from None
+    if not np.isfinite(cov).all():
+        raise ValueError(f"smooth_covariate: the columns {cols} hold NaN or infinite values")
+    scaling = None
+    if opts["scale_cov"]:
+        mean, std = cov.mean(axis=0), cov.std(axis=0)
+        std = np.where(std > 0, std, 1.0)
+        cov, scaling = (cov - mean) / std, (mean, std)
+    return cov, names, scaling
+
+
 def _mofa_engine(backend, views, lik, groups, n_factors, spikeslab_factors, **kw):
     """The engine of a Gaussian or pseudo-data fit (_needs_general_engine decides which); ``kw`` goes to its
     constructor (``comm``, ``row_offset``, ``n_total`` among them)."""
@@ -222,11 +294,17 @@ def mofa(
     comm=None,
 ):
     """
-    Run Multi-Omics Factor Analysis (MOFA+, Gaussian likelihood) on the GPU.
+    Run Multi-Omics Factor Analysis (MOFA+) on the GPU.
 
     Same parameters as ``muon.tl.mofa`` (reference tools.py:290-416).  ``gpu_mode`` /
     ``gpu_device`` are accepted and ignored (this implementation always runs on the GPU).
     Keyword-only extras: ``backend`` (operator set) and ``comm`` (samples sharded over ranks).
+
+    ``smooth_covariate`` (one ``.obs`` column or a list of them) gives every factor a Gaussian-process prior over the
+    covariate (MEFISTO; the model: ``muon_amd/_core/mefisto.py``).  ``smooth_kwargs`` takes ``covariates_names``,
+    ``scale_cov``, ``start_opt``, ``n_grid``, ``opt_freq``, ``model_groups`` and ``new_values``; ``smooth_warping=True``,
+    ``sparseGP=True``, ``frac_inducing`` and ``model_groups=True`` with several groups raise NotImplementedError.  The
+    learned hyperparameters land in ``.uns["mofa"]["smooth"]``.
     """
     if is_anndata(data):
         logger.info("Wrapping an AnnData object into an MuData container")
@@ -261,8 +339,7 @@ def mofa(
 
     if svi_mode:
         raise NotImplementedError("stochastic variational inference (svi_mode) is not implemented")
-    if smooth_covariate is not None or smooth_warping or smooth_kwargs:
-        raise NotImplementedError("MEFISTO (smooth_covariate / smooth_warping) is not implemented")
+    smooth = _smooth_options(smooth_covariate, smooth_warping, smooth_kwargs)
     if convergence_mode not in ("fast", "medium", "slow"):
         raise ValueError("convergence_mode must be 'fast', 'medium' or 'slow'")
 
@@ -285,10 +362,29 @@ def mofa(
               center_groups=center_groups, scale_views=scale_views, scale_groups=scale_groups,
               ard_weights=ard_weights, ard_factors=ard_factors, spikeslab_weights=spikeslab_weights,
               seed=seed, comm=comm)
-    eng = _mofa_engine(backend, views, lik, groups, n_factors, spikeslab_factors, **kw)
+    if smooth is not None:
+        from .mefisto import SmoothMofaEngine
+
+        _check_smooth_options(smooth, len(group_names), spikeslab_factors, comm)
+        cov, cov_names, scaling = _smooth_covariates(mdata.obs, obs_used, smooth_covariate, smooth)
+        if ard_factors:
+            logger.info("ard_factors is ignored with smooth_covariate: the factors' prior is the Gaussian process")
+        eng = SmoothMofaEngine(backend, views, list(lik), groups, n_factors, cov, start_opt=smooth["start_opt"],
+                               n_grid=smooth["n_grid"], opt_freq=smooth["opt_freq"], **kw)
+    else:
+        eng = _mofa_engine(backend, views, lik, groups, n_factors, spikeslab_factors, **kw)
     logger.info("Running the model...")
     eng.run(n_iterations=n_iterations, convergence_mode=convergence_mode)
     res = eng.results(sort_factors=True)
+    if smooth is not None:
+        res["smooth"]["covariates_names"] = cov_names
+        res["smooth"]["covariates"] = cov
+        nv = _smooth_new_values(smooth)
+        if nv is not None:
+            logger.info("Interpolating factors...")
+            at = nv if scaling is None else (nv - scaling[0]) / scaling[1]
+            res["smooth"]["new_values"] = nv
+            res["smooth"]["Z_predicted"] = eng.predict(at)[:, res["order"]]
 
     logger.info("Saving the model...")
     try:
@@ -360,6 +456,10 @@ def mofa(
         # (not in the reference) the file actually written: without h5py the archive is `outfile`.npz
         "model_file": str(written),
     }
+    if smooth is not None:
+        # (not in the reference, which leaves them in the model file) the learned GP hyperparameters per factor, in the
+        # factor order of X_mofa, the lengthscale grid and - with ``new_values`` - the interpolated factors
+        data.uns["mofa"]["smooth"] = {k: v for k, v in res["smooth"].items() if k != "covariates"}
     # Variance explained, R2 in % per factor (tools.py:681-697)
     variance = {m: {} for m in mdata.mod}
     for i, m in enumerate(mdata.mod):
@@ -397,6 +497,11 @@ def _model_datasets(res, view_names, group_names, obs_names, groups):
     d["views/views"] = _bytes(view_names)
     d["groups/groups"] = _bytes(group_names)
     d["training_stats/elbo"] = np.asarray(res["elbo"])
+    if res.get("smooth") is not None:  # a fit with smooth_covariate: the hyperparameters per factor, the covariates per group
+        d["training_stats/length_scales"] = np.asarray(res["smooth"]["lengthscale"], dtype=np.float64)
+        d["training_stats/scales"] = np.asarray(res["smooth"]["scale"], dtype=np.float64)
+        for gi, g in enumerate(group_names):
+            d[f"covariates/{g}"] = np.ascontiguousarray(np.asarray(res["smooth"]["covariates"])[groups == gi])
     return d
 
 

@@ -51,6 +51,8 @@ class OperatorSet:
     skinny_nn = skinny_tn = col_moments = densify_rows = None
     mofa_jaakkola = mofa_poisson_pseudo = mofa_poisson_pass = mofa_softplus_sweep = mofa_jaakkola_sweep = None
     mofa_gs_update = mofa_stats_resid = mofa_tau_finish = None
+    # ... and the two passes of the eigen route of a fit with smooth_covariate (gp.hip; _core/mefisto.py)
+    gp_project = gp_posterior = None
     # muon.prot.pp.dsb (prot.hip)
     prot_max_proteins = prot_log_moments = prot_dsb_fit = None
     # muon.tl.ica (ica.hip)
