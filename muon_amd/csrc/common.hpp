@@ -125,6 +125,77 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
+// ---- host-side dispatch: a run-time value picks the template instance, every ladder spelt once -------------------
+// Each returns what f returns (every branch the same type).  MU_REQUIRE / MU_CHECK_* inside f return from f: either f
+// returns the int status and the entry point returns the helper's, or f only launches and MU_CHECK_LAUNCH() follows
+// the helper call.  The entry point's MU_REQUIRE lines have refused every value the ladders do not name.
+// f(float{}) for MU_DTYPE_F32, f(double{}) otherwise
+template <class F>
+inline constexpr auto by_dtype(int dtype, F&& f) {
+  if (dtype == MU_DTYPE_F32) return f(float{});
+  return f(double{});
+}
+// f(integral_constant<int, Wi>) for the first Wi with k <= Wi; the last entry takes everything larger
+template <int W0, int... Ws, class F>
+inline constexpr auto by_width(int k, F&& f) {
+  if constexpr (sizeof...(Ws) == 0) {
+    return f(std::integral_constant<int, W0>{});
+  } else {
+    if (k <= W0) return f(std::integral_constant<int, W0>{});
+    return by_width<Ws...>(k, f);
+  }
+}
+// f(integral_constant<int, i>) for i in 0 .. N - 2, f(<N - 1>) for anything else (a bool goes through by_index<2>)
+template <int N, int I = 0, class F>
+inline constexpr auto by_index(int i, F&& f) {
+  if constexpr (I == N - 1) {
+    return f(std::integral_constant<int, I>{});
+  } else {
+    if (i == I) return f(std::integral_constant<int, I>{});
+    return by_index<N, I + 1>(i, f);
+  }
+}
+
+namespace dispatch_check {  // both sides of every edge of every width list the library uses
+constexpr auto self = [](auto w) { return (int)w(); };
+constexpr auto size = [](auto t) { return (int)sizeof(t); };
+static_assert(by_dtype(MU_DTYPE_F32, size) == 4 && by_dtype(MU_DTYPE_F64, size) == 8);
+static_assert(by_width<16, 32>(-1, self) == 16 && by_width<16, 32>(1, self) == 16 && by_width<16, 32>(16, self) == 16 &&
+              by_width<16, 32>(17, self) == 32 && by_width<16, 32>(32, self) == 32 && by_width<16, 32>(33, self) == 32);
+static_assert(by_width<16, 32, 64>(0, self) == 16 && by_width<16, 32, 64>(16, self) == 16 &&
+              by_width<16, 32, 64>(17, self) == 32 && by_width<16, 32, 64>(32, self) == 32 &&
+              by_width<16, 32, 64>(33, self) == 64 && by_width<16, 32, 64>(64, self) == 64 &&
+              by_width<16, 32, 64>(65, self) == 64);
+static_assert(by_width<16, 32, 48, 64>(0, self) == 16 && by_width<16, 32, 48, 64>(16, self) == 16 &&
+              by_width<16, 32, 48, 64>(17, self) == 32 && by_width<16, 32, 48, 64>(32, self) == 32 &&
+              by_width<16, 32, 48, 64>(33, self) == 48 && by_width<16, 32, 48, 64>(48, self) == 48 &&
+              by_width<16, 32, 48, 64>(49, self) == 64 && by_width<16, 32, 48, 64>(64, self) == 64 &&
+              by_width<16, 32, 48, 64>(65, self) == 64);
+static_assert(by_width<4, 8, 12, 16>(0, self) == 4 && by_width<4, 8, 12, 16>(4, self) == 4 &&
+              by_width<4, 8, 12, 16>(5, self) == 8 && by_width<4, 8, 12, 16>(8, self) == 8 &&
+              by_width<4, 8, 12, 16>(9, self) == 12 && by_width<4, 8, 12, 16>(12, self) == 12 &&
+              by_width<4, 8, 12, 16>(13, self) == 16 && by_width<4, 8, 12, 16>(16, self) == 16 &&
+              by_width<4, 8, 12, 16>(17, self) == 16);
+static_assert(by_width<4, 8, 12, 16, 32>(0, self) == 4 && by_width<4, 8, 12, 16, 32>(4, self) == 4 &&
+              by_width<4, 8, 12, 16, 32>(5, self) == 8 && by_width<4, 8, 12, 16, 32>(8, self) == 8 &&
+              by_width<4, 8, 12, 16, 32>(9, self) == 12 && by_width<4, 8, 12, 16, 32>(12, self) == 12 &&
+              by_width<4, 8, 12, 16, 32>(13, self) == 16 && by_width<4, 8, 12, 16, 32>(16, self) == 16 &&
+              by_width<4, 8, 12, 16, 32>(17, self) == 32 && by_width<4, 8, 12, 16, 32>(32, self) == 32 &&
+              by_width<4, 8, 12, 16, 32>(33, self) == 32);
+static_assert(by_width<64, 128, 256, 512, 1024>(0, self) == 64 && by_width<64, 128, 256, 512, 1024>(64, self) == 64 &&
+              by_width<64, 128, 256, 512, 1024>(65, self) == 128 && by_width<64, 128, 256, 512, 1024>(128, self) == 128 &&
+              by_width<64, 128, 256, 512, 1024>(129, self) == 256 && by_width<64, 128, 256, 512, 1024>(256, self) == 256 &&
+              by_width<64, 128, 256, 512, 1024>(257, self) == 512 && by_width<64, 128, 256, 512, 1024>(512, self) == 512 &&
+              by_width<64, 128, 256, 512, 1024>(513, self) == 1024 && by_width<64, 128, 256, 512, 1024>(1024, self) == 1024 &&
+              by_width<64, 128, 256, 512, 1024>(1025, self) == 1024);
+static_assert(by_index<2>(false, self) == 0 && by_index<2>(true, self) == 1 && by_index<2>(-1, self) == 1 &&
+              by_index<2>(7, self) == 1);
+static_assert(by_index<3>(0, self) == 0 && by_index<3>(1, self) == 1 && by_index<3>(2, self) == 2 &&
+              by_index<3>(3, self) == 2 && by_index<3>(-1, self) == 2);
+static_assert(by_index<4>(0, self) == 0 && by_index<4>(1, self) == 1 && by_index<4>(2, self) == 2 &&
+              by_index<4>(3, self) == 3 && by_index<4>(4, self) == 3 && by_index<4>(-1, self) == 3);
+}  // namespace dispatch_check
+
 // lane `l` of a 64-bit value, as two 32-bit readlanes (l wave-uniform)
 __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);

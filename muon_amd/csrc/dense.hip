@@ -475,26 +475,20 @@ int mu_gram_cross_f32(int64_t n_rows, int B, const float* d_A, const float* d_Bm
   double* partial = (double*)d_work;
   double* folded = partial + (size_t)blocks * (size_t)(B * B + B);
   const unsigned rblocks = (unsigned)((B * B + B + 255) / 256);
-#define MU_CROSS(BB)                                                                                  \
-  hipLaunchKernelGGL(k_gram_cross_partial<BB>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A,  \
-                     d_Bm, partial);                                                                  \
-  MU_CHECK_LAUNCH();                                                                                  \
-  if (blocks <= kGramFold) {                                                                          \
-    hipLaunchKernelGGL(k_gram_cross_reduce<BB>, dim3(rblocks), dim3(256), 0, st, blocks, partial, d_C); \
-  } else {                                                                                            \
-    hipLaunchKernelGGL(k_gram_fold<BB>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial,  \
-                       folded);                                                                       \
-    MU_CHECK_LAUNCH();                                                                                \
-    hipLaunchKernelGGL(k_gram_cross_reduce<BB>, dim3(rblocks), dim3(256), 0, st, kGramFold, folded, d_C); \
-  }
-  switch (B) {
-    case 64: MU_CROSS(64) break;
-    case 32: MU_CROSS(32) break;
-    default: MU_CROSS(16) break;
-  }
-#undef MU_CROSS
-  MU_CHECK_LAUNCH();
-  return MU_OK;
+  return by_width<16, 32, 64>(B, [&](auto bb) -> int {
+    constexpr int BB = decltype(bb)::value;
+    hipLaunchKernelGGL(k_gram_cross_partial<BB>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A, d_Bm, partial);
+    MU_CHECK_LAUNCH();
+    const bool fold = blocks > kGramFold;
+    if (fold) {
+      hipLaunchKernelGGL(k_gram_fold<BB>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial, folded);
+      MU_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_gram_cross_reduce<BB>, dim3(rblocks), dim3(256), 0, st, fold ? kGramFold : blocks,
+                       fold ? folded : partial, d_C);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+  });
 }
 
 int mu_gram_f32(int64_t n_rows, int B, const float* d_A, double* d_G, double* d_colsum, void* d_work,
@@ -508,43 +502,20 @@ int mu_gram_f32(int64_t n_rows, int B, const float* d_A, double* d_G, double* d_
   double* partial = (double*)d_work;
   double* folded = partial + (size_t)blocks * (size_t)(B * B + B);
   const unsigned rblocks = (unsigned)((B * B + B + 255) / 256);
-  switch (B) {
-    case 64:
-      hipLaunchKernelGGL(k_gram_partial<64>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A, partial);
+  return by_width<16, 32, 64>(B, [&](auto bb) -> int {
+    constexpr int BB = decltype(bb)::value;
+    hipLaunchKernelGGL(k_gram_partial<BB>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A, partial);
+    MU_CHECK_LAUNCH();
+    const bool fold = blocks > kGramFold;
+    if (fold) {
+      hipLaunchKernelGGL(k_gram_fold<BB>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial, folded);
       MU_CHECK_LAUNCH();
-      if (blocks <= kGramFold) {
-        hipLaunchKernelGGL(k_gram_reduce<64>, dim3(rblocks), dim3(256), 0, st, blocks, partial, d_G, d_colsum);
-        break;
-      }
-      hipLaunchKernelGGL(k_gram_fold<64>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial, folded);
-      MU_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_gram_reduce<64>, dim3(rblocks), dim3(256), 0, st, kGramFold, folded, d_G, d_colsum);
-      break;
-    case 32:
-      hipLaunchKernelGGL(k_gram_partial<32>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A, partial);
-      MU_CHECK_LAUNCH();
-      if (blocks <= kGramFold) {
-        hipLaunchKernelGGL(k_gram_reduce<32>, dim3(rblocks), dim3(256), 0, st, blocks, partial, d_G, d_colsum);
-        break;
-      }
-      hipLaunchKernelGGL(k_gram_fold<32>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial, folded);
-      MU_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_gram_reduce<32>, dim3(rblocks), dim3(256), 0, st, kGramFold, folded, d_G, d_colsum);
-      break;
-    default:
-      hipLaunchKernelGGL(k_gram_partial<16>, dim3(blocks), dim3(kGramThreads), 0, st, n_rows, d_A, partial);
-      MU_CHECK_LAUNCH();
-      if (blocks <= kGramFold) {
-        hipLaunchKernelGGL(k_gram_reduce<16>, dim3(rblocks), dim3(256), 0, st, blocks, partial, d_G, d_colsum);
-        break;
-      }
-      hipLaunchKernelGGL(k_gram_fold<16>, dim3(rblocks, kGramFold), dim3(256), 0, st, blocks, partial, folded);
-      MU_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_gram_reduce<16>, dim3(rblocks), dim3(256), 0, st, kGramFold, folded, d_G, d_colsum);
-      break;
-  }
-  MU_CHECK_LAUNCH();
-  return MU_OK;
+    }
+    hipLaunchKernelGGL(k_gram_reduce<BB>, dim3(rblocks), dim3(256), 0, st, fold ? kGramFold : blocks,
+                       fold ? folded : partial, d_G, d_colsum);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+  });
 }
 
 int mu_dense_apply_f32(int64_t n_rows, int B, const float* d_A, const float* d_M,
@@ -557,17 +528,10 @@ int mu_dense_apply_f32(int64_t n_rows, int B, const float* d_A, const float* d_M
   int64_t blocks = (n_rows + 63) / 64;
   const int64_t cap = (int64_t)mu_num_cus() * 8;
   if (blocks > cap) blocks = cap;
-  switch (B) {
-    case 64:
-      hipLaunchKernelGGL(k_dense_apply<64>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_M, d_bias, d_Out);
-      break;
-    case 32:
-      hipLaunchKernelGGL(k_dense_apply<32>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_M, d_bias, d_Out);
-      break;
-    default:
-      hipLaunchKernelGGL(k_dense_apply<16>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_M, d_bias, d_Out);
-      break;
-  }
+  by_width<16, 32, 64>(B, [&](auto bb) {
+    hipLaunchKernelGGL(k_dense_apply<decltype(bb)::value>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_M,
+                       d_bias, d_Out);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -583,17 +547,10 @@ int mu_dense_project_out_f32(int64_t n_rows, int B, const float* d_A, const doub
   int64_t blocks = (((n_rows + 15) / 16) + 3) / 4;
   const int64_t cap = (int64_t)mu_num_cus() * 8;
   if (blocks > cap) blocks = cap;
-  switch (B) {
-    case 64:
-      hipLaunchKernelGGL(k_dense_project<64>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_C, d_Z);
-      break;
-    case 32:
-      hipLaunchKernelGGL(k_dense_project<32>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_C, d_Z);
-      break;
-    default:
-      hipLaunchKernelGGL(k_dense_project<16>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_C, d_Z);
-      break;
-  }
+  by_width<16, 32, 64>(B, [&](auto bb) {
+    hipLaunchKernelGGL(k_dense_project<decltype(bb)::value>, dim3((unsigned)blocks), dim3(256), 0, st, n_rows, d_A, d_C,
+                       d_Z);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

@@ -250,12 +250,10 @@ int mu_csr_qc(int dtype, int64_t n_rows, int64_t n_cols, const int64_t* d_indptr
     int rc = launch_slab_ptr(n_rows, n_cols, d_indptr, d_indices, (int64_t*)d_work, st);
     if (rc) return rc;
   }
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_csr_qc<float>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S, d_indptr, d_indices,
-                       (const float*)d_values, sp, d_row_nnz, d_rowsum, partial, partial_cnt);
-  else
-    hipLaunchKernelGGL(k_csr_qc<double>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S, d_indptr, d_indices,
-                       (const double*)d_values, sp, d_row_nnz, d_rowsum, partial, partial_cnt);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_csr_qc<decltype(t)>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S, d_indptr, d_indices,
+                       (const decltype(t)*)d_values, sp, d_row_nnz, d_rowsum, partial, partial_cnt);
+  });
   MU_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_qc_reduce_partials, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, n_cols, G, partial,
                      partial_cnt, d_colsum, d_col_nnz);
@@ -290,14 +288,12 @@ int mu_csr_submatrix_fill(int dtype, int64_t n_rows, int64_t n_cols, int64_t n_k
   MU_REQUIRE(d_indptr && d_rows && d_new_indptr, "null pointer");
   MU_REQUIRE(n_cols == 0 || d_col_table, "null pointer");
   const unsigned grid = wave_grid(n_keep, 4, 16);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_submatrix_fill<uint32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols,
-                       n_keep, d_indptr, d_indices, (const uint32_t*)d_values, d_rows, d_col_table, d_new_indptr,
-                       d_new_indices, (uint32_t*)d_new_values);
-  else
-    hipLaunchKernelGGL(k_submatrix_fill<uint64_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols,
-                       n_keep, d_indptr, d_indices, (const uint64_t*)d_values, d_rows, d_col_table, d_new_indptr,
-                       d_new_indices, (uint64_t*)d_new_values);
+  by_dtype(dtype, [&](auto t) {
+    using U = std::conditional_t<sizeof(t) == 4, uint32_t, uint64_t>;  // values move as bits
+    hipLaunchKernelGGL(k_submatrix_fill<U>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n_rows, n_cols, n_keep,
+                       d_indptr, d_indices, (const U*)d_values, d_rows, d_col_table, d_new_indptr, d_new_indices,
+                       (U*)d_new_values);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

@@ -195,17 +195,6 @@ inline int64_t ica_blocks(int64_t n, int max_blocks) {
   return b < 1 ? 1 : b;
 }
 
-template <int FUN>
-void ica_launch(int nb, unsigned blocks, hipStream_t st, int64_t n, int k, int64_t ldz, const double* Z, const double* W,
-                double alpha, double* work) {
-  switch (nb) {
-    case 1: hipLaunchKernelGGL((k_ica_sweep<FUN, 1>), dim3(blocks), dim3(256), 0, st, n, k, ldz, Z, W, alpha, work); break;
-    case 2: hipLaunchKernelGGL((k_ica_sweep<FUN, 2>), dim3(blocks), dim3(256), 0, st, n, k, ldz, Z, W, alpha, work); break;
-    case 3: hipLaunchKernelGGL((k_ica_sweep<FUN, 3>), dim3(blocks), dim3(256), 0, st, n, k, ldz, Z, W, alpha, work); break;
-    default: hipLaunchKernelGGL((k_ica_sweep<FUN, 4>), dim3(blocks), dim3(256), 0, st, n, k, ldz, Z, W, alpha, work); break;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -237,9 +226,12 @@ int mu_ica_sweep_f64(int64_t n, int k, int64_t ldz, const double* d_Z, const dou
   MU_REQUIRE(d_work && work_bytes >= mu_ica_worksize(n, k, max_blocks), "work buffer too small");
   const unsigned blocks = (unsigned)ica_blocks(n, max_blocks);
   double* work = (double*)d_work;
-  if (fun == kFunLogcosh) ica_launch<kFunLogcosh>(kp / 16, blocks, st, n, k, ldz, d_Z, d_W, alpha, work);
-  else if (fun == kFunExp) ica_launch<kFunExp>(kp / 16, blocks, st, n, k, ldz, d_Z, d_W, alpha, work);
-  else ica_launch<kFunCube>(kp / 16, blocks, st, n, k, ldz, d_Z, d_W, alpha, work);
+  by_index<3>(fun, [&](auto f) {  // kFunLogcosh, kFunExp, kFunCube
+    by_width<16, 32, 48, 64>(k, [&](auto w) {  // NB = kp / 16
+      hipLaunchKernelGGL((k_ica_sweep<decltype(f)::value, decltype(w)::value / 16>), dim3(blocks), dim3(256), 0, st, n, k,
+                         ldz, d_Z, d_W, alpha, work);
+    });
+  });
   MU_CHECK_LAUNCH();
   const int total = k * k + k;
   hipLaunchKernelGGL(k_ica_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, k, kp, (int)blocks,

@@ -117,37 +117,6 @@ __global__ __launch_bounds__(kMofaThreads) void k_mofa_update_z(
   }
 }
 
-template <typename T>
-static int launch_w(int64_t D, int K, int G, const void* B, const void* tau, const void* Gz,
-                    const void* Z2, const void* alpha, const void* lth, const void* l1mth,
-                    int spikeslab, void* EW, void* EW2, void* gamma, void* EWh2, void* sig2,
-                    hipStream_t st) {
-  const unsigned blocks = (unsigned)((D + kMofaThreads - 1) / kMofaThreads);
-  const size_t sh = (size_t)(G * K * K + G * K) * sizeof(T);
-#define ARGS D, K, G, (const T*)B, (const T*)tau, (const T*)Gz, (const T*)Z2, (const T*)alpha, \
-             (const T*)lth, (const T*)l1mth, spikeslab, (T*)EW, (T*)EW2, (T*)gamma, (T*)EWh2, (T*)sig2
-  if (K <= 16) hipLaunchKernelGGL((k_mofa_update_w<T, 16>), dim3(blocks), dim3(kMofaThreads), sh, st, ARGS);
-  else hipLaunchKernelGGL((k_mofa_update_w<T, 32>), dim3(blocks), dim3(kMofaThreads), sh, st, ARGS);
-#undef ARGS
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
-template <typename T>
-static int launch_z(int64_t N, int K, int M, int G, const void* A, const void* pres,
-                    const int32_t* grp, const void* Gw, const void* dw2, const void* alphaz,
-                    const void* corr, void* EZ, void* EZ2, void* sig2, hipStream_t st) {
-  const unsigned blocks = (unsigned)((N + kMofaThreads - 1) / kMofaThreads);
-  const size_t sh = (size_t)(M * G * K * K + 2 * M * G * K) * sizeof(T);
-#define ARGS N, K, M, G, (const T*)A, (const T*)pres, grp, (const T*)Gw, (const T*)dw2, \
-             (const T*)alphaz, (const T*)corr, (T*)EZ, (T*)EZ2, (T*)sig2
-  if (K <= 16) hipLaunchKernelGGL((k_mofa_update_z<T, 16>), dim3(blocks), dim3(kMofaThreads), sh, st, ARGS);
-  else hipLaunchKernelGGL((k_mofa_update_z<T, 32>), dim3(blocks), dim3(kMofaThreads), sh, st, ARGS);
-#undef ARGS
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
 extern "C" {
 
 int mu_mofa_update_w(int dtype, int64_t D, int K, int G, const void* d_B, const void* d_tau,
@@ -160,11 +129,19 @@ int mu_mofa_update_w(int dtype, int64_t D, int K, int G, const void* d_B, const 
   if (D == 0) return MU_OK;
   MU_REQUIRE(d_B && d_tau && d_Gz && d_Z2 && d_alpha && d_EW && d_EW2 && d_gamma && d_EWh2 && d_sig2,
              "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    return launch_w<float>(D, K, G, d_B, d_tau, d_Gz, d_Z2, d_alpha, d_lth, d_l1mth, spikeslab, d_EW,
-                           d_EW2, d_gamma, d_EWh2, d_sig2, (hipStream_t)stream);
-  return launch_w<double>(D, K, G, d_B, d_tau, d_Gz, d_Z2, d_alpha, d_lth, d_l1mth, spikeslab, d_EW,
-                          d_EW2, d_gamma, d_EWh2, d_sig2, (hipStream_t)stream);
+  const unsigned blocks = (unsigned)((D + kMofaThreads - 1) / kMofaThreads);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const size_t sh = (size_t)(G * K * K + G * K) * sizeof(T);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_update_w<T, decltype(kp)::value>), dim3(blocks), dim3(kMofaThreads), sh,
+                         (hipStream_t)stream, D, K, G, (const T*)d_B, (const T*)d_tau, (const T*)d_Gz,
+                         (const T*)d_Z2, (const T*)d_alpha, (const T*)d_lth, (const T*)d_l1mth, spikeslab, (T*)d_EW,
+                         (T*)d_EW2, (T*)d_gamma, (T*)d_EWh2, (T*)d_sig2);
+    });
+  });
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 int mu_mofa_update_z(int dtype, int64_t N, int K, int M, int G, const void* d_A, const void* d_pres,
@@ -177,11 +154,18 @@ int mu_mofa_update_z(int dtype, int64_t N, int K, int M, int G, const void* d_A,
   if (N == 0) return MU_OK;
   MU_REQUIRE(d_A && d_pres && d_grp && d_Gw && d_dw2 && d_alphaz && d_EZ && d_EZ2 && d_sig2,
              "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    return launch_z<float>(N, K, M, G, d_A, d_pres, d_grp, d_Gw, d_dw2, d_alphaz, d_corr, d_EZ, d_EZ2,
-                           d_sig2, (hipStream_t)stream);
-  return launch_z<double>(N, K, M, G, d_A, d_pres, d_grp, d_Gw, d_dw2, d_alphaz, d_corr, d_EZ, d_EZ2,
-                          d_sig2, (hipStream_t)stream);
+  const unsigned blocks = (unsigned)((N + kMofaThreads - 1) / kMofaThreads);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const size_t sh = (size_t)(M * G * K * K + 2 * M * G * K) * sizeof(T);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_update_z<T, decltype(kp)::value>), dim3(blocks), dim3(kMofaThreads), sh,
+                         (hipStream_t)stream, N, K, M, G, (const T*)d_A, (const T*)d_pres, d_grp, (const T*)d_Gw,
+                         (const T*)d_dw2, (const T*)d_alphaz, (const T*)d_corr, (T*)d_EZ, (T*)d_EZ2, (T*)d_sig2);
+    });
+  });
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 }  // extern "C"

@@ -188,54 +188,25 @@ __global__ __launch_bounds__(256) void k_pack_moments(int64_t n, int K, int ldm,
 }
 
 int bj_ct(int K) { return (K * (K + 1) / 2 + 15) / 16; }
-// instantiated column-tile counts per padded width: the smallest one that holds K (K + 1) / 2 columns
+// THE (KP, CT) table: per padded width the two instantiated column-tile counts, of which K takes the smallest that holds
+// its K (K + 1) / 2 columns: 4 -> 1, 8 -> 2 | 3, 12 -> 4 | 5, 16 -> 7 | 9.  f(kernel instance, its BjShape, T{}, CT);
+// the launch, the occupancy query and the padded column count all go through this one statement.
+template <class F>
+auto bj_inst(int dtype, int K, F&& f) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return by_width<4, 8, 12, 16>(K, [&](auto kp) {
+      constexpr int KP = decltype(kp)::value;
+      constexpr int C0 = KP == 4 ? 1 : KP == 8 ? 2 : KP == 12 ? 4 : 7, C1 = KP == 4 ? 1 : KP == 8 ? 3 : KP == 12 ? 5 : 9;
+      return by_width<C0, C1>(bj_ct(K), [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        return f(k_jaakkola_sweep<T, KP, CT>, BjShape<T, KP, CT>{}, t, ct);
+      });
+    });
+  });
+}
 int bj_ct_inst(int K) {
-  const int need = bj_ct(K);
-  if (K <= 4) return 1;
-  if (K <= 8) return need <= 2 ? 2 : 3;
-  if (K <= 12) return need <= 4 ? 4 : 5;
-  return need <= 7 ? 7 : 9;
-}
-
-template <typename T, int KP, int CT>
-const void* bj_kernel() { return (const void*)k_jaakkola_sweep<T, KP, CT>; }
-
-template <typename T>
-const void* bj_pick(int K, int* own, int* sr) {
-  const int ct = bj_ct_inst(K);
-#define MU_B(KP_, CT_)                                   \
-  do {                                                   \
-    *own = BjShape<T, KP_, CT_>::OWN;                    \
-    *sr = BjShape<T, KP_, CT_>::SR;                      \
-    return bj_kernel<T, KP_, CT_>();                     \
-  } while (0)
-  if (K <= 4) MU_B(4, 1);
-  if (K <= 8) { if (ct == 2) MU_B(8, 2); MU_B(8, 3); }
-  if (K <= 12) { if (ct == 4) MU_B(12, 4); MU_B(12, 5); }
-  if (ct == 7) MU_B(16, 7);
-  MU_B(16, 9);
-#undef MU_B
-}
-
-template <typename T>
-int bj_launch(int64_t n_own, int64_t n_other, int K, int64_t other_block, const void* E_own, const void* E2_own,
-              const void* E_other, const void* E2_other, const void* M_other, int ldm, void* part, hipStream_t st) {
-  int own = 1, sr = 32;
-  (void)bj_pick<T>(K, &own, &sr);
-  const int pc = K * (K + 1) / 2, ct = bj_ct_inst(K);
-  const dim3 grid((unsigned)((n_own + 64 * own - 1) / (64 * own)), (unsigned)((n_other + other_block - 1) / other_block));
-#define MU_GO(KP_, CT_)                                                                                               \
-  hipLaunchKernelGGL((k_jaakkola_sweep<T, KP_, CT_>), grid, dim3(kBjThreads), 0, st, n_own, n_other, K, pc, other_block, \
-                     (const T*)E_own, (const T*)E2_own, (const T*)E_other, (const T*)E2_other, (const T*)M_other, ldm,   \
-                     (T*)part)
-  if (K <= 4) MU_GO(4, 1);
-  else if (K <= 8) { if (ct == 2) MU_GO(8, 2); else MU_GO(8, 3); }
-  else if (K <= 12) { if (ct == 4) MU_GO(12, 4); else MU_GO(12, 5); }
-  else if (ct == 7) MU_GO(16, 7);
-  else MU_GO(16, 9);
-#undef MU_GO
-  MU_CHECK_LAUNCH();
-  return MU_OK;
+  return bj_inst(MU_DTYPE_F32, K, [](auto, auto, auto, auto ct) { return (int)ct(); });
 }
 
 }  // namespace
@@ -251,12 +222,11 @@ int mu_mofa_pack_moments(int dtype, int64_t n, int K, int ldm, const void* d_E, 
   if (n == 0) return MU_OK;
   MU_REQUIRE(d_E && d_E2 && d_M, "null pointer");
   const unsigned nb = (unsigned)((n + 255) / 256);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_pack_moments<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n, K, ldm, (const float*)d_E,
-                       (const float*)d_E2, (float*)d_M);
-  else
-    hipLaunchKernelGGL(k_pack_moments<double>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n, K, ldm,
-                       (const double*)d_E, (const double*)d_E2, (double*)d_M);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_pack_moments<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n, K, ldm, (const T*)d_E,
+                       (const T*)d_E2, (T*)d_M);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -268,7 +238,11 @@ int64_t mu_mofa_jaakkola_blocks(int dtype, int K, int64_t n_own, int64_t n_other
   if (K < 1) K = 1;
   if (K > 16) K = 16;
   int own = 1, sr = 32;
-  const void* kern = dtype == MU_DTYPE_F32 ? bj_pick<float>(K, &own, &sr) : bj_pick<double>(K, &own, &sr);
+  const void* kern = bj_inst(dtype, K, [&](auto kernel, auto sh, auto, auto) {
+    own = sh.OWN;
+    sr = sh.SR;
+    return (const void*)kernel;
+  });
   const int64_t own_wgs = n_own > 0 ? (n_own + 64 * own - 1) / (64 * own) : 1;
   const int64_t tiles = n_other > 0 ? (n_other + sr - 1) / sr : 1;
   int occ = 0;
@@ -303,11 +277,17 @@ int mu_mofa_jaakkola_sweep(int dtype, int64_t n_own, int64_t n_other, int K, int
   if (n_own == 0 || n_other == 0) return MU_OK;
   MU_REQUIRE(d_E_own && d_E2_own && d_E_other && d_E2_other && d_M_other && d_part, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  return dtype == MU_DTYPE_F32
-             ? bj_launch<float>(n_own, n_other, K, other_block, d_E_own, d_E2_own, d_E_other, d_E2_other, d_M_other,
-                                ldm, d_part, st)
-             : bj_launch<double>(n_own, n_other, K, other_block, d_E_own, d_E2_own, d_E_other, d_E2_other, d_M_other,
-                                 ldm, d_part, st);
+  const int pc = K * (K + 1) / 2;
+  bj_inst(dtype, K, [&](auto kernel, auto sh, auto t, auto) {
+    using T = decltype(t);
+    const dim3 grid((unsigned)((n_own + 64 * sh.OWN - 1) / (64 * sh.OWN)),
+                    (unsigned)((n_other + other_block - 1) / other_block));
+    hipLaunchKernelGGL(kernel, grid, dim3(kBjThreads), 0, st, n_own, n_other, K, pc, other_block, (const T*)d_E_own,
+                       (const T*)d_E2_own, (const T*)d_E_other, (const T*)d_E2_other, (const T*)d_M_other, ldm,
+                       (T*)d_part);
+  });
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 }  // extern "C"

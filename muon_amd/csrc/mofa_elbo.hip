@@ -357,59 +357,6 @@ inline int blocks_for(int64_t items, int per_block, int cap = kEBlocksMax) {
 // the column sums (512 partials made the one-workgroup finish 0.15 ms, ten times the pass itself)
 constexpr int kEColBlocks = 256;
 
-template <typename T>
-int run_tau(int64_t D, int K, int G, const void* yy, const void* Ngm, const void* EW, const void* EW2,
-            const void* B, const void* Gz, const void* Z2, double a0, double b0, void* tau, void* ltau,
-            double* elbo, double* work, hipStream_t st) {
-  const int nb = blocks_for((int64_t)G * D, kET);
-  const size_t sh = (size_t)(kET + G * K * K + G * K) * sizeof(double);
-#define ARGS D, K, G, (const T*)yy, (const T*)Ngm, (const T*)EW, (const T*)EW2, (const T*)B, \
-             (const T*)Gz, (const T*)Z2, a0, b0, (T*)tau, (T*)ltau, work
-  if (K <= 16) hipLaunchKernelGGL((k_mofa_tau<T, 16>), dim3(nb), dim3(kET), sh, st, ARGS);
-  else hipLaunchKernelGGL((k_mofa_tau<T, 32>), dim3(nb), dim3(kET), sh, st, ARGS);
-#undef ARGS
-  MU_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_mofa_add_partials, dim3(1), dim3(64), 0, st, nb, work, elbo);
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
-template <typename T>
-int run_w(int64_t D, int K, int ard, int spikeslab, const void* EWh2, const void* gamma, const void* sig2,
-          double a_alpha, double a0, double b0, double th_a0, double th_b0, void* alpha, void* lalpha,
-          void* lth, void* l1mth, double* elbo, double* work, hipStream_t st) {
-  const int KP = K <= 16 ? 16 : 32;
-  const int nb = blocks_for(D, kET / KP, kEColBlocks);
-  if (K <= 16)
-    hipLaunchKernelGGL((k_mofa_w_colsums<T, 16>), dim3(nb), dim3(kET), 0, st, D, K, (const T*)EWh2,
-                       (const T*)gamma, (const T*)sig2, work);
-  else
-    hipLaunchKernelGGL((k_mofa_w_colsums<T, 32>), dim3(nb), dim3(kET), 0, st, D, K, (const T*)EWh2,
-                       (const T*)gamma, (const T*)sig2, work);
-  MU_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_mofa_w_finish<T>, dim3(1), dim3(kFinT), 0, st, D, K, nb, ard, spikeslab, work, a_alpha,
-                     a0, b0, th_a0, th_b0, (T*)alpha, (T*)lalpha, (T*)lth, (T*)l1mth, elbo);
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
-template <typename T>
-int run_z_sums(int64_t n0, int64_t n1, int K, const void* EZ2, const void* sig2, double* out, double* work,
-               hipStream_t st) {
-  const int KP = K <= 16 ? 16 : 32;
-  const int nb = blocks_for(n1 - n0, kET / KP, kEColBlocks);
-  if (K <= 16)
-    hipLaunchKernelGGL((k_mofa_z_colsums<T, 16>), dim3(nb), dim3(kET), 0, st, n0, n1, K, (const T*)EZ2,
-                       (const T*)sig2, work);
-  else
-    hipLaunchKernelGGL((k_mofa_z_colsums<T, 32>), dim3(nb), dim3(kET), 0, st, n0, n1, K, (const T*)EZ2,
-                       (const T*)sig2, work);
-  MU_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_mofa_fold, dim3(1), dim3(512), 0, st, nb, 2 * K, work, out);
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -426,11 +373,21 @@ int mu_mofa_tau_elbo(int dtype, int64_t D, int K, int G, const void* d_yy, const
   if (D == 0) return MU_OK;
   MU_REQUIRE(d_yy && d_Ngm && d_EW && d_EW2 && d_B && d_Gz && d_Z2 && d_tau && d_ltau && d_elbo && d_work,
              "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    return run_tau<float>(D, K, G, d_yy, d_Ngm, d_EW, d_EW2, d_B, d_Gz, d_Z2, a0, b0, d_tau, d_ltau, d_elbo,
-                          d_work, (hipStream_t)stream);
-  return run_tau<double>(D, K, G, d_yy, d_Ngm, d_EW, d_EW2, d_B, d_Gz, d_Z2, a0, b0, d_tau, d_ltau, d_elbo,
-                         d_work, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = blocks_for((int64_t)G * D, kET);
+  const size_t sh = (size_t)(kET + G * K * K + G * K) * sizeof(double);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_tau<T, decltype(kp)::value>), dim3(nb), dim3(kET), sh, st, D, K, G, (const T*)d_yy,
+                         (const T*)d_Ngm, (const T*)d_EW, (const T*)d_EW2, (const T*)d_B, (const T*)d_Gz,
+                         (const T*)d_Z2, a0, b0, (T*)d_tau, (T*)d_ltau, d_work);
+    });
+  });
+  MU_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_mofa_add_partials, dim3(1), dim3(64), 0, st, nb, d_work, d_elbo);
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 int mu_mofa_stats_resid(int dtype, int64_t D, int K, int64_t q_rows, const double* d_yy, const void* d_EW,
@@ -442,17 +399,13 @@ int mu_mofa_stats_resid(int dtype, int64_t D, int K, int64_t q_rows, const doubl
   MU_REQUIRE(d_yy && d_EW && d_EW2 && d_B && d_Q && d_S, "null pointer");
   const unsigned nb = (unsigned)((D + kET - 1) / kET);
   hipStream_t st = (hipStream_t)stream;
-#define MU_R(T_, KP_)                                                                                              \
-  hipLaunchKernelGGL((k_mofa_stats_resid<T_, KP_>), dim3(nb), dim3(kET), 0, st, D, K, q_rows, d_yy, (const T_*)d_EW, \
-                     (const T_*)d_EW2, (const T_*)d_B, (const T_*)d_Q, d_S)
-  if (dtype == MU_DTYPE_F32) {
-    if (K <= 16) MU_R(float, 16);
-    else MU_R(float, 32);
-  } else {
-    if (K <= 16) MU_R(double, 16);
-    else MU_R(double, 32);
-  }
-#undef MU_R
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_stats_resid<T, decltype(kp)::value>), dim3(nb), dim3(kET), 0, st, D, K, q_rows, d_yy,
+                         (const T*)d_EW, (const T*)d_EW2, (const T*)d_B, (const T*)d_Q, d_S);
+    });
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -465,12 +418,11 @@ int mu_mofa_tau_finish(int dtype, int64_t n, const double* d_S, const double* d_
   MU_REQUIRE(d_S && d_Ngd && d_tau && d_ltau && d_elbo && d_work, "null pointer");
   const int nb = blocks_for(n, kET);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL((k_mofa_tau_finish<float>), dim3(nb), dim3(kET), 0, st, n, d_S, d_Ngd, a0, b0, (float*)d_tau,
-                       (float*)d_ltau, d_work);
-  else
-    hipLaunchKernelGGL((k_mofa_tau_finish<double>), dim3(nb), dim3(kET), 0, st, n, d_S, d_Ngd, a0, b0, (double*)d_tau,
-                       (double*)d_ltau, d_work);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_mofa_tau_finish<T>), dim3(nb), dim3(kET), 0, st, n, d_S, d_Ngd, a0, b0, (T*)d_tau,
+                       (T*)d_ltau, d_work);
+  });
   MU_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_mofa_add_partials, dim3(1), dim3(64), 0, st, nb, d_work, d_elbo);
   MU_CHECK_LAUNCH();
@@ -486,11 +438,20 @@ int mu_mofa_w_elbo(int dtype, int64_t D, int K, int ard, int spikeslab, const vo
   MU_REQUIRE(D >= 0, "negative size");
   MU_REQUIRE(d_EWh2 && d_gamma && d_sig2 && d_alpha && d_lalpha && d_lth && d_l1mth && d_elbo && d_work,
              "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    return run_w<float>(D, K, ard, spikeslab, d_EWh2, d_gamma, d_sig2, a_alpha, a0, b0, th_a0, th_b0, d_alpha,
-                        d_lalpha, d_lth, d_l1mth, d_elbo, d_work, (hipStream_t)stream);
-  return run_w<double>(D, K, ard, spikeslab, d_EWh2, d_gamma, d_sig2, a_alpha, a0, b0, th_a0, th_b0, d_alpha,
-                       d_lalpha, d_lth, d_l1mth, d_elbo, d_work, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = blocks_for(D, kET / (K <= 16 ? 16 : 32), kEColBlocks);
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_w_colsums<T, decltype(kp)::value>), dim3(nb), dim3(kET), 0, st, D, K,
+                         (const T*)d_EWh2, (const T*)d_gamma, (const T*)d_sig2, d_work);
+    });
+    MU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mofa_w_finish<T>, dim3(1), dim3(kFinT), 0, st, D, K, nb, ard, spikeslab, d_work, a_alpha, a0,
+                       b0, th_a0, th_b0, (T*)d_alpha, (T*)d_lalpha, (T*)d_lth, (T*)d_l1mth, d_elbo);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+  });
 }
 
 int mu_mofa_z_sums(int dtype, int64_t n0, int64_t n1, int K, const void* d_EZ2, const void* d_sig2,
@@ -499,9 +460,19 @@ int mu_mofa_z_sums(int dtype, int64_t n0, int64_t n1, int K, const void* d_EZ2, 
   MU_REQUIRE(K >= 1 && K <= 32, "1 <= n_factors <= 32");
   MU_REQUIRE(n0 >= 0 && n1 >= n0, "bad row range");
   MU_REQUIRE(d_EZ2 && d_sig2 && d_out && d_work, "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    return run_z_sums<float>(n0, n1, K, d_EZ2, d_sig2, d_out, d_work, (hipStream_t)stream);
-  return run_z_sums<double>(n0, n1, K, d_EZ2, d_sig2, d_out, d_work, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = blocks_for(n1 - n0, kET / (K <= 16 ? 16 : 32), kEColBlocks);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_mofa_z_colsums<T, decltype(kp)::value>), dim3(nb), dim3(kET), 0, st, n0, n1, K,
+                         (const T*)d_EZ2, (const T*)d_sig2, d_work);
+    });
+  });
+  MU_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_mofa_fold, dim3(1), dim3(512), 0, st, nb, 2 * K, d_work, d_out);
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 int mu_mofa_z_elbo(int dtype, int K, int G, int ard, const double* d_zs, const double* d_Ng, double a0,
@@ -509,12 +480,11 @@ int mu_mofa_z_elbo(int dtype, int K, int G, int ard, const double* d_zs, const d
   MU_REQUIRE(dtype == MU_DTYPE_F32 || dtype == MU_DTYPE_F64, "dtype must be f32 or f64");
   MU_REQUIRE(K >= 1 && K <= 32 && G >= 1, "1 <= n_factors <= 32, at least one group");
   MU_REQUIRE(d_zs && d_Ng && d_alpha_z && d_lalpha_z && d_elbo, "null pointer");
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_mofa_z_finish<float>, dim3(1), dim3(64), 0, (hipStream_t)stream, K, G, ard, d_zs,
-                       d_Ng, a0, b0, (float*)d_alpha_z, (float*)d_lalpha_z, d_elbo);
-  else
-    hipLaunchKernelGGL(k_mofa_z_finish<double>, dim3(1), dim3(64), 0, (hipStream_t)stream, K, G, ard, d_zs,
-                       d_Ng, a0, b0, (double*)d_alpha_z, (double*)d_lalpha_z, d_elbo);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_mofa_z_finish<T>, dim3(1), dim3(64), 0, (hipStream_t)stream, K, G, ard, d_zs, d_Ng, a0, b0,
+                       (T*)d_alpha_z, (T*)d_lalpha_z, d_elbo);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

@@ -545,92 +545,49 @@ __global__ __launch_bounds__(256) void k_pois_sparse_quad(int64_t n_own, int K, 
   }
 }
 
-template <typename T, int KP>
-int pois_dense_launch(int mode, int64_t n_own, int64_t n_other, int K, int ld, int64_t other_block, const void* E_own,
-                      const void* E_other, const void* kappa, void* part, hipStream_t st) {
-  const dim3 grid((unsigned)((n_own + kPzThreads - 1) / kPzThreads), (unsigned)((n_other + other_block - 1) / other_block));
-#define MU_GO(MD)                                                                                                      \
-  hipLaunchKernelGGL((k_pois_dense<T, KP, MD>), grid, dim3(kPzThreads), 0, st, n_own, n_other, K, ld, other_block,      \
-                     (const T*)E_own, (const T*)E_other, (const T*)kappa, (T*)part)
-  if (mode == 0) MU_GO(0);
-  else if (mode == 1) MU_GO(1);
-  else if (mode == 2) MU_GO(2);
-  else MU_GO(3);
-#undef MU_GO
-  MU_CHECK_LAUNCH();
-  return MU_OK;
+// THE instance tables: (storage type, padded width of K, mode) -> f(kernel instance, T{}), one statement per kernel
+// family.  A launch and the occupancy query of mu_mofa_poisson_blocks_for go through the same statement.
+template <class F>
+auto pois_dense_inst(int dtype, int K, int mode, F&& f) {
+  return by_dtype(dtype, [&](auto t) {
+    return by_width<4, 8, 12, 16, 32>(K, [&](auto kp) {
+      return by_index<4>(mode, [&](auto md) {
+        return f(k_pois_dense<decltype(t), decltype(kp)::value, decltype(md)::value>, t);
+      });
+    });
+  });
+}
+template <class F>
+auto pois_mfma_inst(int dtype, int K, int mode, F&& f) {
+  return by_dtype(dtype, [&](auto t) {
+    return by_width<4, 8, 12, 16>(K, [&](auto kp) {
+      return by_index<4>(mode, [&](auto md) {
+        return f(k_pois_mfma<decltype(t), decltype(kp)::value, decltype(md)::value>, t);
+      });
+    });
+  });
+}
+template <class F>
+auto pois_sparse_inst(int dtype, int K, int mode, F&& f) {
+  return by_dtype(dtype, [&](auto t) {
+    return by_width<4, 8, 12, 16, 32>(K, [&](auto kp) {
+      return by_index<4>(mode, [&](auto md) {
+        constexpr int KP = decltype(kp)::value, MD = decltype(md)::value;
+        if constexpr (KP == 12 || KP == 16)
+          if (tune(kTune_pois_lane) <= 0) return f(k_pois_sparse_quad<decltype(t), KP, MD>, t);  // four lanes per entry
+        return f(k_pois_sparse<decltype(t), KP, MD>, t);
+      });
+    });
+  });
 }
 
-template <typename T, int KP>
-int pois_mfma_launch(int mode, int64_t n_own, int64_t n_other, int K, int ld, int64_t other_block, const void* E_own,
-                     const void* E_other, const void* kappa, void* part, hipStream_t st) {
-  const int own_rows = 64 * PmMap<T>::OWN;
-  const dim3 grid((unsigned)((n_own + own_rows - 1) / own_rows), (unsigned)((n_other + other_block - 1) / other_block));
-#define MU_GO(MD)                                                                                                 \
-  hipLaunchKernelGGL((k_pois_mfma<T, KP, MD>), grid, dim3(kPzThreads), 0, st, n_own, n_other, K, ld, other_block, \
-                     (const T*)E_own, (const T*)E_other, (const T*)kappa, (T*)part)
-  if (mode == 0) MU_GO(0);
-  else if (mode == 1) MU_GO(1);
-  else if (mode == 2) MU_GO(2);
-  else MU_GO(3);
-#undef MU_GO
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
-template <typename T, int KP>
-int pois_sparse_launch(int mode, int64_t n_own, int K, int ld, const int64_t* indptr, const int32_t* indices,
-                       const void* values, const void* E_own, const void* E_other, void* out, hipStream_t st) {
-  const unsigned blocks = (unsigned)((n_own + 3) / 4);
-#define MU_GO(KERNEL, MD)                                                                                            \
-  hipLaunchKernelGGL((KERNEL<T, KP, MD>), dim3(blocks), dim3(256), 0, st, n_own, K, ld, indptr, indices,             \
-                     (const T*)values, (const T*)E_own, (const T*)E_other, (T*)out)
-  if constexpr (KP == 12 || KP == 16) {
-    if (tune(kTune_pois_lane) <= 0) {  // four lanes per entry (k_pois_sparse_quad)
-      if (mode == 0) MU_GO(k_pois_sparse_quad, 0);
-      else if (mode == 1) MU_GO(k_pois_sparse_quad, 1);
-      else if (mode == 2) MU_GO(k_pois_sparse_quad, 2);
-      else MU_GO(k_pois_sparse_quad, 3);
-      MU_CHECK_LAUNCH();
-      return MU_OK;
-    }
-  }
-  if (mode == 0) MU_GO(k_pois_sparse, 0);
-  else if (mode == 1) MU_GO(k_pois_sparse, 1);
-  else if (mode == 2) MU_GO(k_pois_sparse, 2);
-  else MU_GO(k_pois_sparse, 3);
-#undef MU_GO
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
-template <typename T, int KP>
-const void* pois_mfma_ptr(int mode) {
-  return mode == 0 ? (const void*)k_pois_mfma<T, KP, 0> : mode == 1 ? (const void*)k_pois_mfma<T, KP, 1>
-       : mode == 2 ? (const void*)k_pois_mfma<T, KP, 2> : (const void*)k_pois_mfma<T, KP, 3>;
-}
-template <typename T, int KP>
-const void* pois_dense_ptr(int mode) {
-  return mode == 0 ? (const void*)k_pois_dense<T, KP, 0> : mode == 1 ? (const void*)k_pois_dense<T, KP, 1>
-       : mode == 2 ? (const void*)k_pois_dense<T, KP, 2> : (const void*)k_pois_dense<T, KP, 3>;
-}
 bool pois_use_mfma(int dtype, int K) { return K <= 16 && tune(kTune_pois_valu) <= 0; }
 int pois_own_rows(int dtype, int K) {  // own rows of a workgroup of the dense sweep
-  return pois_use_mfma(dtype, K) ? 64 * (dtype == MU_DTYPE_F32 ? PmMap<float>::OWN : PmMap<double>::OWN) : kPzThreads;
+  return pois_use_mfma(dtype, K) ? 64 * by_dtype(dtype, [](auto t) { return PmMap<decltype(t)>::OWN; }) : kPzThreads;
 }
 const void* pois_dense_kernel(int dtype, int mode, int K) {
-  if (pois_use_mfma(dtype, K)) {
-#define MU_Q(T_)                                                                                                  \
-  (K <= 4 ? pois_mfma_ptr<T_, 4>(mode) : K <= 8 ? pois_mfma_ptr<T_, 8>(mode) : K <= 12 ? pois_mfma_ptr<T_, 12>(mode) \
-                                                                                       : pois_mfma_ptr<T_, 16>(mode))
-    return dtype == MU_DTYPE_F32 ? MU_Q(float) : MU_Q(double);
-#undef MU_Q
-  }
-#define MU_P(T_)                                                                                                   \
-  (K <= 4 ? pois_dense_ptr<T_, 4>(mode) : K <= 8 ? pois_dense_ptr<T_, 8>(mode) : K <= 12 ? pois_dense_ptr<T_, 12>(mode) \
-   : K <= 16 ? pois_dense_ptr<T_, 16>(mode) : pois_dense_ptr<T_, 32>(mode))
-  return dtype == MU_DTYPE_F32 ? MU_P(float) : MU_P(double);
-#undef MU_P
+  const auto address = [](auto kernel, auto) { return (const void*)kernel; };
+  return pois_use_mfma(dtype, K) ? pois_mfma_inst(dtype, K, mode, address) : pois_dense_inst(dtype, K, mode, address);
 }
 
 }  // namespace
@@ -697,18 +654,17 @@ int mu_mofa_poisson_dense_ld(int dtype, int mode, int64_t n_own, int64_t n_other
   if (n_own == 0 || n_other == 0) return MU_OK;
   MU_REQUIRE(d_E_own && d_E_other && d_part && (mode == 2 || d_kappa), "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (pois_use_mfma(dtype, K)) {  // the matrix-core sweep (k_pois_mfma)
-#define MU_M(T_, KP_) pois_mfma_launch<T_, KP_>(mode, n_own, n_other, K, ld, other_block, d_E_own, d_E_other, d_kappa, d_part, st)
-#define MU_MK(T_) (K <= 4 ? MU_M(T_, 4) : K <= 8 ? MU_M(T_, 8) : K <= 12 ? MU_M(T_, 12) : MU_M(T_, 16))
-    return dtype == MU_DTYPE_F32 ? MU_MK(float) : MU_MK(double);
-#undef MU_MK
-#undef MU_M
-  }
-#define MU_D(T_, KP_) pois_dense_launch<T_, KP_>(mode, n_own, n_other, K, ld, other_block, d_E_own, d_E_other, d_kappa, d_part, st)
-#define MU_DK(T_) (K <= 4 ? MU_D(T_, 4) : K <= 8 ? MU_D(T_, 8) : K <= 12 ? MU_D(T_, 12) : K <= 16 ? MU_D(T_, 16) : MU_D(T_, 32))
-  return dtype == MU_DTYPE_F32 ? MU_DK(float) : MU_DK(double);
-#undef MU_DK
-#undef MU_D
+  const int own_rows = pois_own_rows(dtype, K);
+  const dim3 grid((unsigned)((n_own + own_rows - 1) / own_rows), (unsigned)((n_other + other_block - 1) / other_block));
+  const auto launch = [&](auto kernel, auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(kernel, grid, dim3(kPzThreads), 0, st, n_own, n_other, K, ld, other_block, (const T*)d_E_own,
+                       (const T*)d_E_other, (const T*)d_kappa, (T*)d_part);
+  };
+  if (pois_use_mfma(dtype, K)) pois_mfma_inst(dtype, K, mode, launch);  // the matrix-core sweep (k_pois_mfma)
+  else pois_dense_inst(dtype, K, mode, launch);
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 int mu_mofa_poisson_dense(int dtype, int mode, int64_t n_own, int64_t n_other, int K, int64_t other_block,
@@ -727,11 +683,14 @@ int mu_mofa_poisson_sparse_ld(int dtype, int mode, int64_t n_own, int K, int ld,
   if (n_own <= 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_E_own && d_E_other && d_out, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-#define MU_S(T_, KP_) pois_sparse_launch<T_, KP_>(mode, n_own, K, ld, d_indptr, d_indices, d_values, d_E_own, d_E_other, d_out, st)
-#define MU_SK(T_) (K <= 4 ? MU_S(T_, 4) : K <= 8 ? MU_S(T_, 8) : K <= 12 ? MU_S(T_, 12) : K <= 16 ? MU_S(T_, 16) : MU_S(T_, 32))
-  return dtype == MU_DTYPE_F32 ? MU_SK(float) : MU_SK(double);
-#undef MU_SK
-#undef MU_S
+  const unsigned blocks = (unsigned)((n_own + 3) / 4);
+  pois_sparse_inst(dtype, K, mode, [&](auto kernel, auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, n_own, K, ld, d_indptr, d_indices, (const T*)d_values,
+                       (const T*)d_E_own, (const T*)d_E_other, (T*)d_out);
+  });
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 int mu_mofa_poisson_sparse(int dtype, int mode, int64_t n_own, int K, const int64_t* d_indptr, const int32_t* d_indices,

@@ -109,26 +109,6 @@ __global__ __launch_bounds__(kFoldT) void k_rowstats_fold(int nb, int K, const d
   }
 }
 
-template <typename T>
-int run(int64_t r0, int64_t r1, int K, const void* E, const void* E2, const void* wgt, const void* aux,
-        int scale_out, void* out_pad, int ld, int col0, void* out_t, int64_t ld_t, void* gram, void* s2,
-        void* s1, double* work, hipStream_t st) {
-  const int KP = K <= 16 ? 16 : 32;
-  const int64_t rows = r1 - r0, per = kST / KP;
-  int nb = (int)((rows + per * 8 - 1) / (per * 8));  // >= 8 rows per thread group
-  if (nb < 1) nb = 1;
-  if (nb > kSBlocksMax) nb = kSBlocksMax;
-#define ARGS r0, r1, K, (const T*)E, (const T*)E2, (const T*)wgt, (const T*)aux, scale_out, (T*)out_pad, ld, \
-             col0, (T*)out_t, ld_t, work
-  if (K <= 16) hipLaunchKernelGGL((k_rowstats<T, 16>), dim3(nb), dim3(kST), 0, st, ARGS);
-  else hipLaunchKernelGGL((k_rowstats<T, 32>), dim3(nb), dim3(kST), 0, st, ARGS);
-#undef ARGS
-  MU_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_rowstats_fold<T>, dim3(1), dim3(kFoldT), 0, st, nb, K, work, (T*)gram, (T*)s2, (T*)s1);
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -148,11 +128,24 @@ int mu_mofa_rowstats(int dtype, int64_t r0, int64_t r1, int K, const void* d_E, 
   MU_REQUIRE(d_E && d_E2 && d_work, "null pointer");
   MU_REQUIRE(!d_out_pad || (ld >= col0 + K && col0 >= 0), "padded block too narrow");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    return run<float>(r0, r1, K, d_E, d_E2, d_wgt, d_aux, scale_out, d_out_pad, ld, col0, d_out_t, ld_t,
-                      d_gram, d_s2, d_s1, d_work, st);
-  return run<double>(r0, r1, K, d_E, d_E2, d_wgt, d_aux, scale_out, d_out_pad, ld, col0, d_out_t, ld_t,
-                     d_gram, d_s2, d_s1, d_work, st);
+  const int KP = K <= 16 ? 16 : 32;
+  const int64_t rows = r1 - r0, per = kST / KP;
+  int nb = (int)((rows + per * 8 - 1) / (per * 8));  // >= 8 rows per thread group
+  if (nb < 1) nb = 1;
+  if (nb > kSBlocksMax) nb = kSBlocksMax;
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_rowstats<T, decltype(kp)::value>), dim3(nb), dim3(kST), 0, st, r0, r1, K, (const T*)d_E,
+                         (const T*)d_E2, (const T*)d_wgt, (const T*)d_aux, scale_out, (T*)d_out_pad, ld, col0,
+                         (T*)d_out_t, ld_t, d_work);
+    });
+    MU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_rowstats_fold<T>, dim3(1), dim3(kFoldT), 0, st, nb, K, d_work, (T*)d_gram, (T*)d_s2,
+                       (T*)d_s1);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+  });
 }
 
 }  // extern "C"
@@ -223,15 +216,14 @@ extern "C" int mu_mofa_gs_update(int dtype, int64_t n, int K, const void* d_T, c
   MU_REQUIRE(!spikeslab || (d_lth && d_l1mth), "spike-and-slab needs the theta expectations");
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-#define MU_GS(T_, KP_)                                                                                          \
-  hipLaunchKernelGGL((k_gs_update<T_, KP_>), dim3(blocks), dim3(256), 0, st, n, K, (const T_*)d_T, (const T_*)d_b,  \
-                     d_prior, d_lth, d_l1mth, spikeslab, (T_*)d_E, (T_*)d_E2, (T_*)d_gamma, (T_*)d_Eh2, (T_*)d_sig2)
-  if (dtype == MU_DTYPE_F32) {
-    if (K <= 16) MU_GS(float, 16); else MU_GS(float, 32);
-  } else {
-    if (K <= 16) MU_GS(double, 16); else MU_GS(double, 32);
-  }
-#undef MU_GS
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    by_width<16, 32>(K, [&](auto kp) {
+      hipLaunchKernelGGL((k_gs_update<T, decltype(kp)::value>), dim3(blocks), dim3(256), 0, st, n, K, (const T*)d_T,
+                         (const T*)d_b, d_prior, d_lth, d_l1mth, spikeslab, (T*)d_E, (T*)d_E2, (T*)d_gamma, (T*)d_Eh2,
+                         (T*)d_sig2);
+    });
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -278,12 +270,11 @@ extern "C" int mu_mofa_poisson_pseudo(int dtype, int64_t n_rows, int64_t D, int 
   const int64_t cap = (int64_t)mu_num_cus() * 32;
   if (blocks > cap) blocks = cap;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_poisson_pseudo<float>, dim3((unsigned)blocks), dim3(256), 0, st, n, D, mode, (const float*)d_zeta,
-                       (const float*)d_Y, (const float*)d_kappa, (float*)d_out, 1e-30f);
-  else
-    hipLaunchKernelGGL(k_poisson_pseudo<double>, dim3((unsigned)blocks), dim3(256), 0, st, n, D, mode,
-                       (const double*)d_zeta, (const double*)d_Y, (const double*)d_kappa, (double*)d_out, 1e-300);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_poisson_pseudo<T>, dim3((unsigned)blocks), dim3(256), 0, st, n, D, mode, (const T*)d_zeta,
+                       (const T*)d_Y, (const T*)d_kappa, (T*)d_out, sizeof(T) == 4 ? (T)1e-30f : (T)1e-300);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -312,12 +303,11 @@ extern "C" int mu_csr_densify_rows(int dtype, int64_t r0, int64_t r1, int64_t D,
   if (r1 == r0) return MU_OK;
   MU_REQUIRE(d_indptr && d_out, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_densify_rows<float>, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, r0, D, d_indptr, d_indices,
-                       (const float*)d_values, (float*)d_out);
-  else
-    hipLaunchKernelGGL(k_densify_rows<double>, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, r0, D, d_indptr, d_indices,
-                       (const double*)d_values, (double*)d_out);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_densify_rows<T>, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, r0, D, d_indptr, d_indices,
+                       (const T*)d_values, (T*)d_out);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -358,12 +348,11 @@ extern "C" int mu_mofa_jaakkola(int dtype, int64_t n, const void* d_zeta, const 
   const int64_t cap = (int64_t)mu_num_cus() * 32;
   if (blocks > cap) blocks = cap;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_jaakkola<float>, dim3((unsigned)blocks), dim3(256), 0, st, n, (const float*)d_zeta,
-                       (const float*)d_a, (const float*)d_b, (float*)d_out);
-  else
-    hipLaunchKernelGGL(k_jaakkola<double>, dim3((unsigned)blocks), dim3(256), 0, st, n, (const double*)d_zeta,
-                       (const double*)d_a, (const double*)d_b, (double*)d_out);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_jaakkola<T>, dim3((unsigned)blocks), dim3(256), 0, st, n, (const T*)d_zeta, (const T*)d_a,
+                       (const T*)d_b, (T*)d_out);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

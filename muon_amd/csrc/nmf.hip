@@ -244,20 +244,10 @@ int mu_nmf_cd_sweep_f64(int64_t rows, int k, double* d_W, int64_t ldw, const dou
   const unsigned blocks = (unsigned)nmf_blocks(rows, max_blocks);
   const int kp = nmf_kp(k);
   double* work = (double*)d_work;
-  switch (kp) {
-    case 16:
-      hipLaunchKernelGGL((k_nmf_sweep<16>), dim3(blocks), dim3(64), 0, st, rows, k, d_W, ldw, d_B, ldb, d_bscale, d_G, l1,
-                         d_oscale, d_Wout, ldo, work);
-      break;
-    case 32:
-      hipLaunchKernelGGL((k_nmf_sweep<32>), dim3(blocks), dim3(64), 0, st, rows, k, d_W, ldw, d_B, ldb, d_bscale, d_G, l1,
-                         d_oscale, d_Wout, ldo, work);
-      break;
-    default:
-      hipLaunchKernelGGL((k_nmf_sweep<64>), dim3(blocks), dim3(64), 0, st, rows, k, d_W, ldw, d_B, ldb, d_bscale, d_G, l1,
-                         d_oscale, d_Wout, ldo, work);
-      break;
-  }
+  by_width<16, 32, 64>(k, [&](auto w) {
+    hipLaunchKernelGGL((k_nmf_sweep<decltype(w)::value>), dim3(blocks), dim3(64), 0, st, rows, k, d_W, ldw, d_B, ldb,
+                       d_bscale, d_G, l1, d_oscale, d_Wout, ldo, work);
+  });
   MU_CHECK_LAUNCH();
   const int total = k * k + 1;
   hipLaunchKernelGGL(k_nmf_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, k, kp, (int)blocks,

@@ -316,24 +316,6 @@ __global__ __launch_bounds__(64 * kFitWaves) void k_prot_dsb_fit(
   }
 }
 
-template <typename T>
-int launch_fit(int64_t n, int d, const void* X, const int64_t* indptr, const int32_t* indices, const void* values,
-               double pc, const double* mean, const double* sd, const double* resp, int64_t rcs, int64_t rms,
-               double* scaled, double* bg, double* bic, int32_t* niter, hipStream_t st) {
-  const dim3 grid((unsigned)((n + kFitWaves - 1) / kFitWaves)), block(64 * kFitWaves);
-#define MU_FIT(NPL)                                                                                                    \
-  hipLaunchKernelGGL((k_prot_dsb_fit<T, NPL>), grid, block, 0, st, n, d, (const T*)X, indptr, indices, (const T*)values, \
-                     pc, mean, sd, resp, rcs, rms, scaled, bg, bic, niter)
-  if (d <= 64) MU_FIT(1);
-  else if (d <= 128) MU_FIT(2);
-  else if (d <= 256) MU_FIT(4);
-  else if (d <= 512) MU_FIT(8);
-  else MU_FIT(16);
-#undef MU_FIT
-  MU_CHECK_LAUNCH();
-  return MU_OK;
-}
-
 // what numpy's float32 arithmetic makes of the pseudocount and its logarithm
 void prot_pc(int dtype, double pc, double* pc_out, double* logpc) {
   if (dtype == MU_DTYPE_F32) {
@@ -373,12 +355,10 @@ int mu_prot_log_moments_csr(int dtype, int64_t n, int64_t d, const int64_t* d_in
   const dim3 grid((unsigned)((parts + kMomWaves - 1) / kMomWaves)), block(64 * kMomWaves);
   const size_t lds = (size_t)kMomWaves * 2 * (size_t)d * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_prot_moments_csr<float>, grid, block, lds, st, n, (int)d, d_indptr, d_indices,
-                       (const float*)d_values, pc, logpc, rpp, (double*)d_work);
-  else
-    hipLaunchKernelGGL(k_prot_moments_csr<double>, grid, block, lds, st, n, (int)d, d_indptr, d_indices,
-                       (const double*)d_values, pc, logpc, rpp, (double*)d_work);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_prot_moments_csr<decltype(t)>, grid, block, lds, st, n, (int)d, d_indptr, d_indices,
+                       (const decltype(t)*)d_values, pc, logpc, rpp, (double*)d_work);
+  });
   MU_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_prot_moments_finish, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, n, d, parts, logpc,
                      (const double*)d_work, d_mean, d_std);
@@ -398,12 +378,10 @@ int mu_prot_log_moments_dense(int dtype, int64_t n, int64_t d, const void* d_X, 
   const int64_t rpp = mom_rows_per_part(n), parts = (n + rpp - 1) / rpp;
   const dim3 grid((unsigned)parts, (unsigned)((d + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_prot_moments_dense<float>, grid, block, 0, st, n, d, (const float*)d_X, pc, logpc, rpp,
-                       (double*)d_work);
-  else
-    hipLaunchKernelGGL(k_prot_moments_dense<double>, grid, block, 0, st, n, d, (const double*)d_X, pc, logpc, rpp,
-                       (double*)d_work);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_prot_moments_dense<decltype(t)>, grid, block, 0, st, n, d, (const decltype(t)*)d_X, pc, logpc,
+                       rpp, (double*)d_work);
+  });
   MU_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_prot_moments_finish, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, n, d, parts, logpc,
                      (const double*)d_work, d_mean, d_std);
@@ -425,11 +403,17 @@ int mu_prot_dsb_fit(int dtype, int64_t n, int64_t d, const void* d_X, const int6
   double pc, logpc;
   prot_pc(dtype, pseudocount, &pc, &logpc);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    return launch_fit<float>(n, (int)d, d_X, d_indptr, d_indices, d_values, pc, d_mean, d_std, d_resp, resp_cell_stride,
-                             resp_model_stride, d_scaled, d_bgmean, d_bic, d_niter, st);
-  return launch_fit<double>(n, (int)d, d_X, d_indptr, d_indices, d_values, pc, d_mean, d_std, d_resp, resp_cell_stride,
-                            resp_model_stride, d_scaled, d_bgmean, d_bic, d_niter, st);
+  const dim3 grid((unsigned)((n + kFitWaves - 1) / kFitWaves)), block(64 * kFitWaves);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    by_width<64, 128, 256, 512, 1024>((int)d, [&](auto w) {  // NPL: proteins per lane
+      hipLaunchKernelGGL((k_prot_dsb_fit<T, decltype(w)::value / 64>), grid, block, 0, st, n, (int)d, (const T*)d_X,
+                         d_indptr, d_indices, (const T*)d_values, pc, d_mean, d_std, d_resp, resp_cell_stride,
+                         resp_model_stride, d_scaled, d_bgmean, d_bic, d_niter);
+    });
+  });
+  MU_CHECK_LAUNCH();
+  return MU_OK;
 }
 
 }  // extern "C"

@@ -376,12 +376,11 @@ int mu_group_moments(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_b
   if (d == 0) return MU_OK;
   MU_REQUIRE(d_sum && d_sumsq && d_nnz, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_group_moments<float>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
-                       n_buckets, d_indptr, d_cells, (const float*)d_values, d_labels, d_sum, d_sumsq, d_nnz);
-  else
-    hipLaunchKernelGGL(k_group_moments<double>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz,
-                       n_buckets, d_indptr, d_cells, (const double*)d_values, d_labels, d_sum, d_sumsq, d_nnz);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_group_moments<decltype(t)>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d,
+                       n_cells, nnz, n_buckets, d_indptr, d_cells, (const decltype(t)*)d_values, d_labels, d_sum, d_sumsq,
+                       d_nnz);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -395,12 +394,11 @@ int mu_rank_sums(int dtype, int64_t d, int64_t n_cells, int64_t nnz, int n_bucke
   if (d == 0) return MU_OK;
   MU_REQUIRE(d_ranksum && d_zero_rank && d_tie, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_rank_sums<float>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
-                       n_kept, d_indptr, d_cells, (const float*)d_values, d_labels, d_ranksum, d_zero_rank, d_tie);
-  else
-    hipLaunchKernelGGL(k_rank_sums<double>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells, nnz, n_buckets,
-                       n_kept, d_indptr, d_cells, (const double*)d_values, d_labels, d_ranksum, d_zero_rank, d_tie);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_rank_sums<decltype(t)>, dim3(wave_grid(d, kRankWaves, 8)), dim3(kRankThreads), 0, st, d, n_cells,
+                       nnz, n_buckets, n_kept, d_indptr, d_cells, (const decltype(t)*)d_values, d_labels, d_ranksum,
+                       d_zero_rank, d_tie);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

@@ -137,12 +137,10 @@ int mu_gene_moments(int dtype, int64_t d, int64_t nnz, const int64_t* d_indptr, 
   unsigned grid = wave_grid(d, kRnaWaves, kRnaBlocksPerCu);
   if (max_blocks > 0 && grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_gene_moments<float>, dim3(grid), dim3(kRnaThreads), 0, st, d, nnz, d_indptr,
-                       (const float*)d_values, c, with_e, d_sums, d_nnz);
-  else
-    hipLaunchKernelGGL(k_gene_moments<double>, dim3(grid), dim3(kRnaThreads), 0, st, d, nnz, d_indptr,
-                       (const double*)d_values, c, with_e, d_sums, d_nnz);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_gene_moments<decltype(t)>, dim3(grid), dim3(kRnaThreads), 0, st, d, nnz, d_indptr,
+                       (const decltype(t)*)d_values, c, with_e, d_sums, d_nnz);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -156,12 +154,11 @@ int mu_rna_value_sweep(int dtype, int64_t n, int64_t nnz, const int64_t* d_indpt
   MU_REQUIRE(d_indptr && d_in && d_out, "null pointer");
   const unsigned grid = wave_grid(n, kRnaWaves, kRnaBlocksPerCu);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_value_sweep<float>, dim3(grid), dim3(kRnaThreads), 0, st, n, nnz, d_indptr, (const float*)d_in,
-                       (float*)d_out, d_div, log_flag, log_div);
-  else
-    hipLaunchKernelGGL(k_value_sweep<double>, dim3(grid), dim3(kRnaThreads), 0, st, n, nnz, d_indptr,
-                       (const double*)d_in, (double*)d_out, d_div, log_flag, log_div);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_value_sweep<T>, dim3(grid), dim3(kRnaThreads), 0, st, n, nnz, d_indptr, (const T*)d_in,
+                       (T*)d_out, d_div, log_flag, log_div);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

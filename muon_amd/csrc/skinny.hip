@@ -362,21 +362,16 @@ int mu_skinny_tn(int dtype, int64_t n_rows, int64_t D, int64_t ldY, const void* 
   const int64_t cbs = (D + 16 * kCT - 1) / (16 * kCT);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = D * 16;
-  if (dtype == MU_DTYPE_F64) {
-    hipLaunchKernelGGL(k_skinny_tn_partial<double>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                       n_rows, D, ldY, (const double*)d_Y, (const double*)d_Z, S, (double*)d_work);
+  return by_dtype(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_skinny_tn_partial<T>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st, n_rows, D, ldY,
+                       (const T*)d_Y, (const T*)d_Z, S, (T*)d_work);
     MU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_skinny_tn_reduce<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       total, S, (const double*)d_work, (double*)d_C);
-  } else {
-    hipLaunchKernelGGL(k_skinny_tn_partial<float>, dim3((unsigned)cbs, (unsigned)S), dim3(256), 0, st,
-                       n_rows, D, ldY, (const float*)d_Y, (const float*)d_Z, S, (float*)d_work);
+    hipLaunchKernelGGL(k_skinny_tn_reduce<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S,
+                       (const T*)d_work, (T*)d_C);
     MU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_skinny_tn_reduce<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       total, S, (const float*)d_work, (float*)d_C);
-  }
-  MU_CHECK_LAUNCH();
-  return MU_OK;
+    return MU_OK;
+  });
 }
 
 }  // extern "C"

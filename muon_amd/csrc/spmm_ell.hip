@@ -363,13 +363,12 @@ static int ell16_launch(bool wide, int waves, int64_t n_pos, int64_t n_cols, con
   MU_REQUIRE(parts >= 1 && parts <= n_slabs && (parts == 1 || !accumulate), "column parts: 1 .. slabs, partial products");
   const int s_per_part = (int)((n_slabs + parts - 1) / parts);
   const unsigned ny = (unsigned)((n_slabs + s_per_part - 1) / s_per_part);
-#define MU_GO(DT)                                                                                                 \
-  hipLaunchKernelGGL((k_spmm_ell16<DT>), dim3((unsigned)wgs, ny), dim3(64 * (waves + 1)), 0, st, n_pos, n_cols,   \
-                     (int)n_slabs, waves, d_hdr, d_wave_base, (const unsigned char*)d_ent, d_perm, (const DT*)d_Q, \
-                     (DT*)d_Y, accumulate, s_per_part, y_stride)
-  if (wide) MU_GO(double);
-  else MU_GO(float);
-#undef MU_GO
+  by_index<2>(wide, [&](auto w) {
+    using DT = std::conditional_t<decltype(w)::value == 1, double, float>;
+    hipLaunchKernelGGL((k_spmm_ell16<DT>), dim3((unsigned)wgs, ny), dim3(64 * (waves + 1)), 0, st, n_pos, n_cols,
+                       (int)n_slabs, waves, d_hdr, d_wave_base, (const unsigned char*)d_ent, d_perm, (const DT*)d_Q,
+                       (DT*)d_Y, accumulate, s_per_part, y_stride);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

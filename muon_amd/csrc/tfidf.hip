@@ -892,12 +892,10 @@ int mu_tfidf_idf(int dtype, int64_t n_cols, double n_obs, const double* d_colsum
   if (n_cols == 0) return MU_OK;
   MU_REQUIRE(d_colsum && d_idf, "null pointer");
   const unsigned blocks = (unsigned)((n_cols + 255) / 256);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_idf<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_cols, n_obs,
-                       d_colsum, flags, (float*)d_idf);
-  else
-    hipLaunchKernelGGL(k_idf<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_cols, n_obs,
-                       d_colsum, flags, (double*)d_idf);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_idf<decltype(t)>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_cols, n_obs, d_colsum,
+                       flags, (decltype(t)*)d_idf);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -914,14 +912,12 @@ int mu_tfidf_scale(int dtype, int64_t n_rows, const int64_t* d_indptr, const int
   MU_REQUIRE(d_indptr && d_rowsum && d_idf && d_out, "null pointer");
   const int use_scale = !(scale == 0.0 || scale == 1.0);  // preproc.py:101
   const unsigned blocks = wave_grid(n_rows, 4, 16);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_tfidf_scale<float>, dim3(blocks), dim3(256), 0, st, n_rows, d_indptr,
-                       d_indices, (const float*)d_values, d_rowsum, (const float*)d_idf,
-                       (float)scale, use_scale, flags, (float*)d_out, d_zero_count);
-  else
-    hipLaunchKernelGGL(k_tfidf_scale<double>, dim3(blocks), dim3(256), 0, st, n_rows, d_indptr,
-                       d_indices, (const double*)d_values, d_rowsum, (const double*)d_idf, scale,
-                       use_scale, flags, (double*)d_out, d_zero_count);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_tfidf_scale<T>, dim3(blocks), dim3(256), 0, st, n_rows, d_indptr, d_indices,
+                       (const T*)d_values, d_rowsum, (const T*)d_idf, (T)scale, use_scale, flags, (T*)d_out,
+                       d_zero_count);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -1028,12 +1024,10 @@ int mu_csr_count_nonzero(int dtype, int64_t n_rows, const int64_t* d_indptr, con
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_row_nnz, "null pointer");
   const unsigned blocks = wave_grid(n_rows, 4, 16);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_count_nonzero<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       n_rows, d_indptr, (const float*)d_values, d_row_nnz);
-  else
-    hipLaunchKernelGGL(k_count_nonzero<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       n_rows, d_indptr, (const double*)d_values, d_row_nnz);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_count_nonzero<decltype(t)>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rows, d_indptr,
+                       (const decltype(t)*)d_values, d_row_nnz);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -1046,14 +1040,11 @@ int mu_csr_compact_nonzero(int dtype, int64_t n_rows, const int64_t* d_indptr,
   if (n_rows == 0) return MU_OK;
   MU_REQUIRE(d_indptr && d_new_indptr, "null pointer");
   const unsigned blocks = wave_grid(n_rows, 4, 16);
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_compact_nonzero<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       n_rows, d_indptr, d_indices, (const float*)d_values, d_new_indptr,
-                       d_new_indices, (float*)d_new_values);
-  else
-    hipLaunchKernelGGL(k_compact_nonzero<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       n_rows, d_indptr, d_indices, (const double*)d_values, d_new_indptr,
-                       d_new_indices, (double*)d_new_values);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_compact_nonzero<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rows, d_indptr,
+                       d_indices, (const T*)d_values, d_new_indptr, d_new_indices, (T*)d_new_values);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }
@@ -1083,12 +1074,10 @@ int mu_binarize_values(int dtype, int64_t nnz, void* d_values, void* stream) {
   int64_t blocks = (nnz + 255) / 256;
   const int64_t cap = (int64_t)mu_num_cus() * 16;
   if (blocks > cap) blocks = cap;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_binarize<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       nnz, (float*)d_values);
-  else
-    hipLaunchKernelGGL(k_binarize<double>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       nnz, (double*)d_values);
+  by_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(k_binarize<decltype(t)>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nnz,
+                       (decltype(t)*)d_values);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

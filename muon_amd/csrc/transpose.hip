@@ -173,14 +173,11 @@ int mu_csr_transpose(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
   MU_CHECK_LAUNCH();
   rc = mu_exclusive_scan_i64(n_cols, coltot, d_t_indptr, stream);
   if (rc) return rc;
-  if (dtype == MU_DTYPE_F32)
-    hipLaunchKernelGGL(k_transpose_fill<float>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols,
-                       S, d_indptr, d_indices, (const float*)d_values, sp, d_t_indptr, cnt,
-                       d_t_indices, (float*)d_t_values);
-  else
-    hipLaunchKernelGGL(k_transpose_fill<double>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols,
-                       S, d_indptr, d_indices, (const double*)d_values, sp, d_t_indptr, cnt,
-                       d_t_indices, (double*)d_t_values);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_transpose_fill<T>, dim3(G), dim3(kSweepThreads), 0, st, n_rows, n_cols, S, d_indptr, d_indices,
+                       (const T*)d_values, sp, d_t_indptr, cnt, d_t_indices, (T*)d_t_values);
+  });
   MU_CHECK_LAUNCH();
   return MU_OK;
 }

@@ -391,7 +391,7 @@ def test_wrapper_fits_count_likelihoods_on_the_gpu():
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
-@pytest.mark.parametrize("K,R", [(10, 5000), (16, 777), (3, 70000), (20, 1234)])
+@pytest.mark.parametrize("K,R", [(10, 5000), (16, 777), (17, 777), (3, 70000), (20, 1234)])
 def test_rowstats_kernel_matches_tensor_formulas(hip, dtype, K, R):
     """csrc/mofa_stats.hip: padded operand, transposed operand, weighted Gram, second- and first-moment
     sums of a factor / weight block in one pass, against the same formulas as tensor operations."""
@@ -428,7 +428,7 @@ def test_rowstats_kernel_matches_tensor_formulas(hip, dtype, K, R):
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.float64])
-@pytest.mark.parametrize("K,spike", [(5, True), (10, False), (20, True)])
+@pytest.mark.parametrize("K,spike", [(5, True), (10, False), (16, False), (17, True), (20, True)])
 def test_gauss_seidel_row_kernel_matches_the_tensor_loop(hip, dt, K, spike):
     """mu_mofa_gs_update (a thread per row, row-wise K x K statistics) against the per-factor tensor loop it replaced."""
     g = torch.Generator(device="cpu").manual_seed(K)
@@ -505,7 +505,9 @@ def test_poisson_passes_without_the_dense_chunk(dt, tol, K):
 
 
 @pytest.mark.parametrize("dt,tol", [(torch.float64, 1e-11), (torch.float32, 2e-5)])
-@pytest.mark.parametrize("K,ld", [(3, 4), (7, 8), (10, 12), (10, 16), (13, 16), (16, 16), (16, 20), (20, 32)])
+@pytest.mark.parametrize("K,ld", [(3, 4), (7, 8), (10, 12), (10, 16), (13, 16), (16, 16), (16, 20), (20, 32),
+                                  # both sides of every edge of the padded widths 4 | 8 | 12 | 16 | 32
+                                  (4, 4), (5, 8), (8, 8), (9, 12), (12, 12), (17, 32)])
 def test_poisson_stored_entries_ragged_rows(dt, tol, K, ld):
     """mu_mofa_poisson_sparse_ld alone (the correction over the stored entries, added to a given array) against numpy f64:
     rows of 0, 1, .. entries around every batch size of the two kernels (16 / 64 entries per step, 128 / 256 per batch),
@@ -567,7 +569,7 @@ def test_poisson_stored_entries_ragged_rows(dt, tol, K, ld):
 
 @pytest.mark.parametrize("dt,tol", [(torch.float64, 1e-13), (torch.float32, 2e-6)])
 @pytest.mark.parametrize("K,D,G,masked", [(1, 1, 1, True), (5, 700, 1, True), (10, 2000, 2, True), (10, 513, 3, False),
-                                          (20, 300, 2, True)])
+                                          (20, 300, 2, True), (16, 300, 1, True), (17, 300, 1, True)])
 def test_stats_view_residual_and_tau_finish_kernels(dt, tol, K, D, G, masked):
     """mu_mofa_stats_resid + mu_mofa_tau_finish (r06: the tau node of a dense gaussian view with missing entries in the
     general engine, two kernels for ~35 tensor launches) against the tensor expressions they replace

@@ -160,7 +160,8 @@ def _compare_fit(hip, X, pc, mean, std, resp, what):
     return z_k, bg_k, bic_k, it_k
 
 
-@pytest.mark.parametrize("d", [1, 2, 63, 64, 65, 300, 1024])
+# (both sides of every edge of the proteins-per-lane ladder: 64 | 65, 128 | 129, 256 | 257, 512 | 513)
+@pytest.mark.parametrize("d", [1, 2, 63, 64, 65, 128, 129, 256, 257, 300, 512, 513, 1024])
 def test_fit_kernel_equals_the_tensor_formulation(hip, d):
     assert hip.prot_max_proteins() == 1024
     n = 97 if d < 1024 else 33
