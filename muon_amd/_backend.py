@@ -168,6 +168,47 @@ def _n_slab_ptr(n: int, d: int) -> int:
     return n * (-(-d // 8192) + 1)
 
 
+def _sum_parts(part: torch.Tensor) -> torch.Tensor:
+    """The sum of the partial products part[0], part[1], ... in that order (fixed order: deterministic)."""
+    return part[0] if part.shape[0] == 1 else part.sum(dim=0)
+
+
+def _split_hi(values: torch.Tensor):
+    """(hi, rest) of f64 values: hi = fl32(v) and what it leaves, rest = v - hi (f64)."""
+    hi = values.to(torch.float32)
+    return hi, values - hi.to(torch.float64)
+
+
+def _split_lo(rest: torch.Tensor) -> Optional[torch.Tensor]:
+    """lo = fl32(rest) of ``_split_hi``, or None when every value was exact in f32.  Synchronises (it reads whether some
+    rest is not zero): a caller with work to queue on hi alone queues that first."""
+    return rest.to(torch.float32) if bool((rest != 0).any().item()) else None
+
+
+def _mofa_pad_width(K: int) -> int:
+    """Columns of a zero-padded moment block of the poisson passes (include/muon_amd.h): 4 / 8 / 16 / 32, and 16 for
+    9 <= K <= 12 too - 64-byte rows let the stored-entry pass read a row in one cache-line look-up (r06)."""
+    return 16 if 8 < K <= 16 else next(k for k in (4, 8, 32) if k >= K)
+
+
+def _mofa_pad(E: torch.Tensor, slot: str, K: int, ld: int, pads: Optional[dict]) -> torch.Tensor:
+    """E [rows, K] with its rows padded with zeros to ``ld`` columns (E itself where it is that already).
+    ``pads`` (a dict the caller owns, e.g. the engine of a fit): a padded buffer per (role, shape) whose columns
+    K .. ld - 1 are zeroed once - a pass copies the K columns in, one kernel instead of a fill and a copy.
+    Calls are ordered on one stream and a pass has consumed its operands when the next one overwrites them;
+    the buffers live as long as the caller (a captured iteration keeps pointing at them)."""
+    if K == ld and E.is_contiguous():
+        return E
+    key = (slot, int(E.shape[0]), ld, K, E.dtype)
+    P = pads.get(key) if pads is not None else None
+    if P is None:
+        P = torch.zeros((E.shape[0], ld), dtype=E.dtype, device=E.device)
+        if pads is not None:
+            pads[key] = P
+    P[:, :K].copy_(E)
+    return P
+
+
 def pick_block(width: int) -> int:
     for b in (16, 32, 64):
         if width <= b:
@@ -291,6 +332,22 @@ class HipBackend(OperatorSet):
         if torch.cuda.current_device() == self.device.index:
             return _NULL_CTX
         return torch.cuda.device(self.device)
+
+    def _launch(self, fn, *args) -> None:
+        """Call the stream-taking library entry ``fn`` (as in ``self.lib.mu_gram_f32``): a tensor among ``args`` goes as
+        its ``data_ptr()``, everything else (None, ints, floats, bytes, ctypes arrays, ``byref``) as it is; the raw handle
+        of the stream that is current NOW is appended, this backend's device is current around the call, and a status
+        other than 0 raises.  The one place that decides which stream and which device a launch goes to."""
+        Tensor = torch.Tensor
+        with self._dev_ctx():
+            check(fn(*[a.data_ptr() if isinstance(a, Tensor) else a for a in args], self._stream()))
+
+    def _work(self, size, floor: int = 0):
+        """(work, wb): a uint8 work buffer for the ``size`` bytes a ``*_worksize`` query answered, and that size as the
+        int the library is handed.  ``floor``: the fewest bytes allocated (a kernel that is handed a buffer of no size
+        still wants an address)."""
+        wb = int(size)
+        return self.empty((max(wb, floor),), torch.uint8), wb
 
     def empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
@@ -471,8 +528,7 @@ class HipBackend(OperatorSet):
         if n == 0 or d == 0 or X.nnz == 0 or self._slab_ptr_of(X) is not None:
             return X
         sp = self.empty((_n_slab_ptr(n, d),), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_slab_ptr(n, d, _p(X.indptr), _p(X.indices), _p(sp), self._stream()))
+        self._launch(self.lib.mu_csr_slab_ptr, n, d, X.indptr, X.indices, sp)
         X.plans = CsrPlans(CsrPlans.key_of(X), slab_ptr=sp)
         return self.with_plans(X)
 
@@ -500,30 +556,29 @@ class HipBackend(OperatorSet):
 
     def _make_xplan(self, X: DeviceCSR, K: Optional[int]) -> dict:
         """Where the rows of X go in its row stream: launch_layout of the row lengths, scanned."""
-        lens = X.indptr[1:] - X.indptr[:-1]
+        perm, inv, K, sptr = self._dealt_sptr(X.indptr[1:] - X.indptr[:-1], K)
+        return dict(perm=perm, inv=inv, K=K, sptr=sptr, row_dst=sptr[inv.long()].contiguous())
+
+    def _dealt_sptr(self, lens: torch.Tensor, K: Optional[int]):
+        """(perm, inv, K, sptr) of a row stream whose rows, ``lens`` entries long, are dealt by launch_layout: the
+        lengths scattered to their positions, scanned."""
         perm, inv, K = self.launch_layout(lens, K)
         plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
         plens[inv.long()] = lens
-        sptr = self._stream_sptr(plens, K)
-        return dict(perm=perm, inv=inv, K=K, sptr=sptr, row_dst=sptr[inv.long()].contiguous())
+        return perm, inv, K, self._stream_sptr(plens, K)
 
     def _make_tplan(self, X: DeviceCSR, K: Optional[int], sort_rows: bool) -> dict:
         """The count phase of the tile-staged transposition of X (csrc/tpack4.hip) and the layout of X^T's row stream."""
         n, d = X.shape
         col_nnz = self.empty((max(d, 1),), torch.int64)
-        wb = int(self.lib.mu_tpack4_worksize(n, d, X.nnz))
-        work = self.empty((wb,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_tpack4_count(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(col_nnz), _p(work), wb,
-                                           _p(self._slab_ptr_of(X)), self._stream()))
-            lens = col_nnz[:d]
-            if sort_rows and d > 0:
-                perm, inv, K = self.launch_layout(lens, K)
-                plens = torch.zeros((int(perm.numel()),), dtype=torch.int64, device=self.device)
-                plens[inv.long()] = lens
-            else:
-                perm, inv, K, plens = None, None, max(1, int(K or self.lib.mu_spmm_stream_k(d))), lens
-            sptr = self._stream_sptr(plens, K)
+        work, wb = self._work(self.lib.mu_tpack4_worksize(n, d, X.nnz))
+        self._launch(self.lib.mu_tpack4_count, n, d, X.nnz, X.indptr, X.indices, col_nnz, work, wb, self._slab_ptr_of(X))
+        lens = col_nnz[:d]
+        if sort_rows and d > 0:
+            perm, inv, K, sptr = self._dealt_sptr(lens, K)
+        else:
+            perm, inv, K = None, None, max(1, int(K or self.lib.mu_spmm_stream_k(d)))
+            sptr = self._stream_sptr(lens, K)
         return dict(work=work, wb=wb, perm=perm, inv=inv, K=K, sptr=sptr)
 
     @staticmethod
@@ -540,13 +595,10 @@ class HipBackend(OperatorSet):
         n, d = X.shape
         rowsum = self.empty((n,), torch.float64)
         colsum = self.empty((d,), torch.float64)
-        wb = int(self.lib.mu_csr_row_col_sums_worksize(n, d))
-        work = self.empty((wb,), torch.uint8)
+        work, wb = self._work(self.lib.mu_csr_row_col_sums_worksize(n, d))
         sp = self._slab_ptr_of(X)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_row_col_sums_sp(_dt(X.values), n, d, _p(X.indptr), _p(X.indices),
-                                                  _p(X.values), _p(rowsum), _p(colsum), _p(work), wb, _p(sp),
-                                                  self._stream()))
+        self._launch(self.lib.mu_csr_row_col_sums_sp, _dt(X.values), n, d, X.indptr, X.indices, X.values, rowsum, colsum,
+                     work, wb, sp)
         if keep_work:
             return rowsum, colsum, (work if sp is None else None)
         return rowsum, colsum
@@ -554,9 +606,7 @@ class HipBackend(OperatorSet):
     def idf(self, colsum: torch.Tensor, n_obs: float, flags: int, dtype) -> torch.Tensor:
         d = colsum.numel()
         out = self.empty((d,), dtype)
-        with self._dev_ctx():
-            check(self.lib.mu_tfidf_idf(_dt(out), d, float(n_obs), _p(colsum), flags, _p(out),
-                                        self._stream()))
+        self._launch(self.lib.mu_tfidf_idf, _dt(out), d, float(n_obs), colsum, flags, out)
         return out
 
     def can_emit_stream(self, X: DeviceCSR) -> bool:
@@ -591,15 +641,12 @@ class HipBackend(OperatorSet):
         n, d = X.shape
         sp = self._slab_ptr_of(X)
         if emit is None and (gather or sp is not None):
-            with self._dev_ctx():
-                if gather:
-                    check(self.lib.mu_tfidf_scale(_dt(X.values), n, _p(X.indptr), _p(X.indices),
-                                                  _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
-                                                  _p(out), _p(zc), self._stream()))
-                else:
-                    check(self.lib.mu_tfidf_scale_sweep_sp(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                           _p(rowsum), _p(idf), float(scale), flags, _p(out), _p(zc), _p(sp),
-                                                           self._stream()))
+            if gather:
+                self._launch(self.lib.mu_tfidf_scale, _dt(X.values), n, X.indptr, X.indices, X.values, rowsum, idf,
+                             float(scale), flags, out, zc)
+            else:
+                self._launch(self.lib.mu_tfidf_scale_sweep_sp, _dt(X.values), n, d, X.indptr, X.indices, X.values, rowsum,
+                             idf, float(scale), flags, out, zc, sp)
             return out, zc
         # the sweeps that search the slab pointers into the head of a work buffer, or find them there (`have`)
         have, wb = False, 0
@@ -611,18 +658,13 @@ class HipBackend(OperatorSet):
                 work = self.empty((wb,), torch.uint8)
             elif work.numel() != wb:
                 raise ValueError("tfidf_scale(work=): not the work buffer of a sum sweep of this matrix")
-        with self._dev_ctx():
-            if emit is not None:
-                assert X.values.dtype == torch.float32
-                check(self.lib.mu_tfidf_scale_sweep_stream(n, d, _p(X.indptr), _p(X.indices), _p(X.values), _p(rowsum),
-                                                           _p(idf), float(scale), flags, _p(out), _p(zc), _p(work), wb,
-                                                           int(have), _p(sp), _p(emit[1]), _p(emit[0].ent),
-                                                           self._stream()))
-            else:
-                check(self.lib.mu_tfidf_scale_sweep(_dt(X.values), n, d, _p(X.indptr), _p(X.indices),
-                                                    _p(X.values), _p(rowsum), _p(idf), float(scale), flags,
-                                                    _p(out), _p(zc), _p(work), wb, int(have),
-                                                    self._stream()))
+        if emit is not None:
+            assert X.values.dtype == torch.float32
+            self._launch(self.lib.mu_tfidf_scale_sweep_stream, n, d, X.indptr, X.indices, X.values, rowsum, idf,
+                         float(scale), flags, out, zc, work, wb, int(have), sp, emit[1], emit[0].ent)
+        else:
+            self._launch(self.lib.mu_tfidf_scale_sweep, _dt(X.values), n, d, X.indptr, X.indices, X.values, rowsum, idf,
+                         float(scale), flags, out, zc, work, wb, int(have))
         return out, zc
 
     def slab_ptr_from_work(self, X: DeviceCSR, work: torch.Tensor) -> torch.Tensor:
@@ -635,17 +677,13 @@ class HipBackend(OperatorSet):
         n = X.shape[0]
         row_nnz = self.empty((n,), torch.int64)
         new_indptr = self.empty((n + 1,), torch.int64)
-        with self._dev_ctx():
-            st = self._stream()
-            check(self.lib.mu_csr_count_nonzero(_dt(X.values), n, _p(X.indptr), _p(X.values),
-                                                _p(row_nnz), st))
-            check(self.lib.mu_exclusive_scan_i64(n, _p(row_nnz), _p(new_indptr), st))
-            new_nnz = int(new_indptr[-1].item())
-            new_indices = self.empty((new_nnz,), torch.int32)
-            new_values = self.empty((new_nnz,), X.values.dtype)
-            check(self.lib.mu_csr_compact_nonzero(_dt(X.values), n, _p(X.indptr), _p(X.indices),
-                                                  _p(X.values), _p(new_indptr), _p(new_indices),
-                                                  _p(new_values), st))
+        self._launch(self.lib.mu_csr_count_nonzero, _dt(X.values), n, X.indptr, X.values, row_nnz)
+        self._launch(self.lib.mu_exclusive_scan_i64, n, row_nnz, new_indptr)
+        new_nnz = int(new_indptr[-1].item())
+        new_indices = self.empty((new_nnz,), torch.int32)
+        new_values = self.empty((new_nnz,), X.values.dtype)
+        self._launch(self.lib.mu_csr_compact_nonzero, _dt(X.values), n, X.indptr, X.indices, X.values, new_indptr,
+                     new_indices, new_values)
         return DeviceCSR(new_indptr, new_indices, new_values, X.shape)
 
     # -- QC metrics and filtering (reference _core/preproc.py:675-881) ----------------
@@ -655,12 +693,9 @@ class HipBackend(OperatorSet):
         n, d = X.shape
         row_nnz, rowsum = self.empty((n,), torch.int64), self.empty((n,), torch.float64)
         col_nnz, colsum = self.empty((d,), torch.int64), self.empty((d,), torch.float64)
-        wb = int(self.lib.mu_csr_qc_worksize(n, d))
-        work = self.empty((wb,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_qc(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values), _p(row_nnz),
-                                     _p(rowsum), _p(col_nnz), _p(colsum), _p(work), wb, _p(self._slab_ptr_of(X)),
-                                     self._stream()))
+        work, wb = self._work(self.lib.mu_csr_qc_worksize(n, d))
+        self._launch(self.lib.mu_csr_qc, _dt(X.values), n, d, X.indptr, X.indices, X.values, row_nnz, rowsum, col_nnz,
+                     colsum, work, wb, self._slab_ptr_of(X))
         return row_nnz, rowsum, col_nnz, colsum
 
     def csr_submatrix(self, X: DeviceCSR, rows: torch.Tensor, col_table: torch.Tensor, n_cols: int) -> DeviceCSR:
@@ -675,18 +710,14 @@ class HipBackend(OperatorSet):
         rows, col_table = rows.contiguous(), col_table.contiguous()
         row_nnz = self.empty((k,), torch.int64)
         new_indptr = self.zeros((k + 1,), torch.int64)
-        with self._dev_ctx():
-            st = self._stream()
-            check(self.lib.mu_csr_submatrix_count(n, d, k, _p(X.indptr), _p(X.indices), _p(rows), _p(col_table),
-                                                  _p(row_nnz), st))
-            if k:
-                check(self.lib.mu_exclusive_scan_i64(k, _p(row_nnz), _p(new_indptr), st))
-            new_nnz = int(new_indptr[-1].item())
-            new_indices = self.empty((new_nnz,), torch.int32)
-            new_values = self.empty((new_nnz,), X.values.dtype)
-            check(self.lib.mu_csr_submatrix_fill(_dt(X.values), n, d, k, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                 _p(rows), _p(col_table), _p(new_indptr), _p(new_indices),
-                                                 _p(new_values), st))
+        self._launch(self.lib.mu_csr_submatrix_count, n, d, k, X.indptr, X.indices, rows, col_table, row_nnz)
+        if k:
+            self._launch(self.lib.mu_exclusive_scan_i64, k, row_nnz, new_indptr)
+        new_nnz = int(new_indptr[-1].item())
+        new_indices = self.empty((new_nnz,), torch.int32)
+        new_values = self.empty((new_nnz,), X.values.dtype)
+        self._launch(self.lib.mu_csr_submatrix_fill, _dt(X.values), n, d, k, X.indptr, X.indices, X.values, rows, col_table,
+                     new_indptr, new_indices, new_values)
         return DeviceCSR(new_indptr, new_indices, new_values, (k, int(n_cols)))
 
     # -- fragment tools (reference _atac/tools.py:746-1201; csrc/fragments.hip) ------
@@ -703,10 +734,8 @@ class HipBackend(OperatorSet):
             raise TypeError("frag_ranges: chrom_ptr int64")
         n_win = int(wchrom.numel())
         rng_lo, rng_len = self.empty((n_win,), torch.int64), self.empty((n_win,), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_frag_ranges(n_win, int(chrom_ptr.numel()) - 1, _p(wchrom), _p(wlo), _p(whi),
-                                          _p(chrom_ptr.contiguous()), _p(start), int(max_len), _p(rng_lo), _p(rng_len),
-                                          self._stream()))
+        self._launch(self.lib.mu_frag_ranges, n_win, int(chrom_ptr.numel()) - 1, wchrom, wlo, whi, chrom_ptr.contiguous(),
+                     start, int(max_len), rng_lo, rng_len)
         return rng_lo, rng_len
 
     def _frag_chunks(self, rng_len):
@@ -716,7 +745,7 @@ class HipBackend(OperatorSet):
         per = torch.div(rng_len + (chunk - 1), chunk, rounding_mode="floor")
         chunk_ptr = self.zeros((n_win + 1,), torch.int64)
         if n_win:
-            check(self.lib.mu_exclusive_scan_i64(n_win, _p(per), _p(chunk_ptr), self._stream()))
+            self._launch(self.lib.mu_exclusive_scan_i64, n_win, per, chunk_ptr)
         return chunk_ptr, int(chunk_ptr[-1].item())
 
     def frag_overlap(self, start, end, barcode, score, cell_of, n_obs: int, wlo, whi, rng_lo, rng_len, n_features: int):
@@ -724,22 +753,18 @@ class HipBackend(OperatorSet):
         n_features + window, value = score (None: 1); window order, file order inside a window."""
         self._i32(start, end, barcode, score, cell_of, wlo, whi)
         n_win, nb = int(wlo.numel()), int(cell_of.numel())
-        with self._dev_ctx():
-            st = self._stream()
-            chunk_ptr, n_chunks = self._frag_chunks(rng_len)
-            cnt = self.empty((n_chunks,), torch.int64)
-            off = self.zeros((n_chunks + 1,), torch.int64)
-            check(self.lib.mu_frag_overlap_count(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo),
-                                                 _p(whi), _p(start), _p(end), _p(barcode), _p(cell_of), nb, int(n_obs),
-                                                 _p(cnt), st))
-            if n_chunks:
-                check(self.lib.mu_exclusive_scan_i64(n_chunks, _p(cnt), _p(off), st))
-            total = int(off[-1].item())
-            keys, vals = self.empty((total,), torch.int64), self.empty((total,), torch.int32)
-            if total:
-                check(self.lib.mu_frag_overlap_emit(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo),
-                                                    _p(whi), _p(start), _p(end), _p(barcode), _p(score), _p(cell_of),
-                                                    nb, int(n_obs), int(n_features), _p(off), _p(keys), _p(vals), st))
+        chunk_ptr, n_chunks = self._frag_chunks(rng_len)
+        cnt = self.empty((n_chunks,), torch.int64)
+        off = self.zeros((n_chunks + 1,), torch.int64)
+        self._launch(self.lib.mu_frag_overlap_count, n_win, n_chunks, chunk_ptr, rng_lo, rng_len, wlo, whi, start, end,
+                     barcode, cell_of, nb, int(n_obs), cnt)
+        if n_chunks:
+            self._launch(self.lib.mu_exclusive_scan_i64, n_chunks, cnt, off)
+        total = int(off[-1].item())
+        keys, vals = self.empty((total,), torch.int64), self.empty((total,), torch.int32)
+        if total:
+            self._launch(self.lib.mu_frag_overlap_emit, n_win, n_chunks, chunk_ptr, rng_lo, rng_len, wlo, whi, start, end,
+                         barcode, score, cell_of, nb, int(n_obs), int(n_features), off, keys, vals)
         return keys, vals
 
     def frag_pileup(self, start, end, barcode, score, cell_of, n_obs: int, wlo, whi, rng_lo, rng_len, width: int):
@@ -748,11 +773,9 @@ class HipBackend(OperatorSet):
         self._i32(start, end, barcode, score, cell_of, wlo, whi)
         n_win, nb = int(wlo.numel()), int(cell_of.numel())
         diff = self.zeros((int(n_obs), int(width) + 1), torch.int32)
-        with self._dev_ctx():
-            chunk_ptr, n_chunks = self._frag_chunks(rng_len)
-            check(self.lib.mu_frag_pileup(n_win, n_chunks, _p(chunk_ptr), _p(rng_lo), _p(rng_len), _p(wlo), _p(whi),
-                                          _p(start), _p(end), _p(barcode), _p(score), _p(cell_of), nb, int(n_obs),
-                                          int(width), _p(diff), self._stream()))
+        chunk_ptr, n_chunks = self._frag_chunks(rng_len)
+        self._launch(self.lib.mu_frag_pileup, n_win, n_chunks, chunk_ptr, rng_lo, rng_len, wlo, whi, start, end, barcode,
+                     score, cell_of, nb, int(n_obs), int(width), diff)
         return diff
 
     def frag_pileup_scan(self, diff, flank_size: int, center_dist: int):
@@ -761,9 +784,7 @@ class HipBackend(OperatorSet):
         self._i32(diff)
         n, w1 = diff.shape
         sums = self.zeros((n, 2), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_frag_pileup_scan(n, w1 - 1, int(flank_size), int(center_dist), _p(diff), _p(sums),
-                                               self._stream()))
+        self._launch(self.lib.mu_frag_pileup_scan, n, w1 - 1, int(flank_size), int(center_dist), diff, sums)
         return sums
 
     def frag_length_classes(self, start, end, barcode, cell_of, n_obs: int, n_take: int, free_bound: int,
@@ -773,16 +794,12 @@ class HipBackend(OperatorSet):
         self._i32(start, end, barcode, cell_of)
         n_take = max(0, min(int(n_take), int(start.numel())))
         classes = self.zeros((int(n_obs), 2), torch.int32)
-        with self._dev_ctx():
-            check(self.lib.mu_frag_length_classes(n_take, _p(start), _p(end), _p(barcode), _p(cell_of),
-                                                  int(cell_of.numel()), int(n_obs), int(free_bound), int(mono_bound),
-                                                  _p(classes), self._stream()))
+        self._launch(self.lib.mu_frag_length_classes, n_take, start, end, barcode, cell_of, int(cell_of.numel()), int(n_obs),
+                     int(free_bound), int(mono_bound), classes)
         return classes
 
     def binarize_values(self, values: torch.Tensor) -> None:
-        with self._dev_ctx():
-            check(self.lib.mu_binarize_values(_dt(values), values.numel(), _p(values),
-                                              self._stream()))
+        self._launch(self.lib.mu_binarize_values, _dt(values), values.numel(), values)
 
     # -- LSI building blocks (reference tools.py:53 -> scipy svds) ---------------------
     @staticmethod
@@ -797,12 +814,9 @@ class HipBackend(OperatorSet):
         t_indptr = self.empty((d + 1,), torch.int64)
         t_indices = self.empty((nnz,), torch.int32)
         t_values = torch.empty_like(X.values)
-        wb = int(self.lib.mu_csr_transpose_worksize(n, d, nnz))
-        work = self.empty((wb,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_transpose(_dt(X.values), n, d, nnz, _p(X.indptr), _p(X.indices),
-                                            _p(X.values), _p(t_indptr), _p(t_indices),
-                                            _p(t_values), _p(work), wb, self._stream()))
+        work, wb = self._work(self.lib.mu_csr_transpose_worksize(n, d, nnz))
+        self._launch(self.lib.mu_csr_transpose, _dt(X.values), n, d, nnz, X.indptr, X.indices, X.values, t_indptr, t_indices,
+                     t_values, work, wb)
         return DeviceCSR(t_indptr, t_indices, t_values, (d, n))
 
     def transpose_csr(self, X: DeviceCSR) -> DeviceCSR:
@@ -815,15 +829,12 @@ class HipBackend(OperatorSet):
         t_indices = self.empty((max(X.nnz, 1),), torch.int32)[:X.nnz]
         t_values = self.empty((max(X.nnz, 1),), torch.float32)[:X.nnz]
         if self._use_tpack4(X):
-            wb = int(self.lib.mu_tpack4_worksize(n, d, X.nnz))
-            work = self.empty((wb,), torch.uint8)
-            with self._dev_ctx():
-                st = self._stream()
-                check(self.lib.mu_tpack4_count(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(col_nnz), _p(work), wb,
-                                               _p(self._slab_ptr_of(X)), st))
-                check(self.lib.mu_exclusive_scan_i64(d, _p(col_nnz), _p(t_indptr), st))
-                check(self.lib.mu_tpack4_fill_csr(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values), None, None,
-                                                  _p(t_indptr), _p(t_indices), _p(t_values), _p(work), wb, st))
+            work, wb = self._work(self.lib.mu_tpack4_worksize(n, d, X.nnz))
+            self._launch(self.lib.mu_tpack4_count, n, d, X.nnz, X.indptr, X.indices, col_nnz, work, wb,
+                         self._slab_ptr_of(X))
+            self._launch(self.lib.mu_exclusive_scan_i64, d, col_nnz, t_indptr)
+            self._launch(self.lib.mu_tpack4_fill_csr, n, d, X.nnz, X.indptr, X.indices, X.values, None, None, t_indptr,
+                         t_indices, t_values, work, wb)
             self.raise_tpack4(self._note_tpack4(work, n, d, X.nnz).item())  # (set-up / ingest paths: a synchronisation is affordable)
             return DeviceCSR(t_indptr, t_indices, t_values, (d, n))
         # (2^31 rows, a row block of 2^29 entries: the general stable transposition, csrc/transpose.hip)
@@ -836,8 +847,7 @@ class HipBackend(OperatorSet):
     def _stream_sptr(self, lens_by_pos: torch.Tensor, K: int):
         n_pos = int(lens_by_pos.numel())
         sptr = self.zeros((n_pos + 1,), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_exclusive_scan_i64(n_pos, _p(lens_by_pos), _p(sptr), self._stream()))
+        self._launch(self.lib.mu_exclusive_scan_i64, n_pos, lens_by_pos, sptr)
         # cursors are 32-bit byte offsets from the first pair of the workgroup's 64 K rows
         per_wg = 64 * K
         span = sptr[per_wg::per_wg] - sptr[:-per_wg:per_wg] if n_pos > per_wg else sptr[-1:] - sptr[:1]
@@ -855,13 +865,10 @@ class HipBackend(OperatorSet):
             perm, _inv, K = self.launch_layout(X.indptr[1:] - X.indptr[:-1], want_k)
             n_pos = int(perm.numel())
         lens = self.empty((max(n_pos, 1),), torch.int64)[:n_pos]
-        with self._dev_ctx():
-            st = self._stream()
-            check(self.lib.mu_csr_stream_len(n_pos, _p(perm), _p(X.indptr), _p(lens), st))
-            sptr = self._stream_sptr(lens, K)
-            ent = self.empty((max(X.nnz, 1),), torch.int64)
-            check(self.lib.mu_csr_stream_fill(n_pos, _p(perm), _p(X.indptr), _p(X.indices), _p(X.values),
-                                              _p(sptr), _p(ent), st))
+        self._launch(self.lib.mu_csr_stream_len, n_pos, perm, X.indptr, lens)
+        sptr = self._stream_sptr(lens, K)
+        ent = self.empty((max(X.nnz, 1),), torch.int64)
+        self._launch(self.lib.mu_csr_stream_fill, n_pos, perm, X.indptr, X.indices, X.values, sptr, ent)
         return DeviceStream(sptr, ent, (n, d), X.nnz, perm, K)
 
     def _use_tpack4(self, X: DeviceCSR) -> bool:
@@ -892,14 +899,12 @@ class HipBackend(OperatorSet):
 
     def tpack4_status(self) -> int:
         """Error word of the last fourth-generation fill (0 = fine; synchronises: tests and probes)."""
-        import ctypes as C
-
         got = self.__dict__.get("_tpack4_work")
         if got is None:
             return 0
         work, (n, d, nnz) = got
-        err = C.c_int(0)
-        check(self.lib.mu_tpack4_status(_p(work), n, d, nnz, C.byref(err)))
+        err = ctypes.c_int(0)
+        check(self.lib.mu_tpack4_status(_p(work), n, d, nnz, ctypes.byref(err)))
         return int(err.value)
 
     def transpose_stream(self, X: DeviceCSR, sort_rows: bool = True, before_fill=None,
@@ -922,23 +927,19 @@ class HipBackend(OperatorSet):
             before_fill()
         xs_ent, xs_dst = (src[0].ent, src[1]) if src is not None else (None, None)
         tp = self._tperm_of(X, cached, xs_ent, xs_dst) if (cached is not None and src is not None) else None
-        with self._dev_ctx():
-            if tp is not None and "counts" in tp:
-                # (the same with the rows' counts per tile in the plan: the flat read-in, csrc/tflat.hip)
-                cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
-                check(self.lib.mu_tflat_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
-                                             _p(tp["toff"]), _p(tp["tiles"]), _p(tp["counts"]), _p(tp["slots"]), _p(ent),
-                                             self._stream()))
-            elif tp is not None:
-                # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
-                cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
-                check(self.lib.mu_tperm_fill(n, d, X.nnz, _p(X.indptr), _p(xs_dst), _p(xs_ent), _p(tp["cdst"]), _p(cnt),
-                                             _p(tp["toff"]), _p(tp["tiles"]), _p(tp["cont"]), _p(tp["slots"]), _p(ent),
-                                             self._stream()))
-            else:
-                check(self.lib.mu_tpack4_fill_stream(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                     _p(xs_dst), _p(xs_ent), _p(plan["sptr"]), _p(plan["inv"]), _p(ent),
-                                                     _p(plan["work"]), plan["wb"], self._stream()))
+        if tp is not None and "counts" in tp:
+            # (the same with the rows' counts per tile in the plan: the flat read-in, csrc/tflat.hip)
+            cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
+            self._launch(self.lib.mu_tflat_fill, n, d, X.nnz, X.indptr, xs_dst, xs_ent, tp["cdst"], cnt, tp["toff"],
+                         tp["tiles"], tp["counts"], tp["slots"], ent)
+        elif tp is not None:
+            # (lsi's hot path: the slots and the tile schedule come from the plan, csrc/tperm.hip)
+            cnt = plan["work"][int(self.lib.mu_tpack4_cnt_offset(n, d, X.nnz)):]
+            self._launch(self.lib.mu_tperm_fill, n, d, X.nnz, X.indptr, xs_dst, xs_ent, tp["cdst"], cnt, tp["toff"],
+                         tp["tiles"], tp["cont"], tp["slots"], ent)
+        else:
+            self._launch(self.lib.mu_tpack4_fill_stream, n, d, X.nnz, X.indptr, X.indices, X.values, xs_dst, xs_ent,
+                         plan["sptr"], plan["inv"], ent, plan["work"], plan["wb"])
         err = self._note_tpack4(plan["work"], n, d, X.nnz)
         return DeviceStream(plan["sptr"], ent, (d, n), X.nnz, plan["perm"], plan["K"],
                             self._t4_prefix(plan["work"], n, d, X.nnz), err)
@@ -980,51 +981,49 @@ class HipBackend(OperatorSet):
         """The arrays of mu_tflat_plan (``flat``: tiles, counts per (tile, row), slots) or of mu_tperm_plan (tiles,
         continuation rows, slots), or None when they cannot be made: no memory, a refused launch, a row that is not
         canonical."""
-        import ctypes as C
-
         lib = self.lib
         n, d = X.shape
-        rpb, G, Ct = C.c_int64(0), C.c_int(0), C.c_int(0)
-        check(lib.mu_tpack4_geometry(n, d, X.nnz, C.byref(rpb), C.byref(G), C.byref(Ct)))
-        G, Ct = int(G.value), min(int(Ct.value), 512)
+        _rpb, G, Ct = self._t4_tiling(n, d, X.nnz)
+        Ct = min(Ct, 512)
         try:
-            with self._dev_ctx():
-                st = self._stream()
-                ntile = self.empty((G,), torch.int32)
-                if flat:
-                    err = torch.zeros((1,), dtype=torch.int32, device=self.device)
-                    check(lib.mu_tflat_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
-                                            None, _p(err), st))
-                else:
-                    check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), None, Ct, None, _p(ntile), None, None,
-                                            None, st))
-                toff = torch.zeros((G + 1,), dtype=torch.int64, device=self.device)
-                toff[1:] = torch.cumsum(ntile.long(), 0)
-                T = int(toff[-1].item())
-                tiles = self.empty((T + G,), torch.int32)
-                slots = self.empty((X.nnz,), torch.int16)
-                if flat:
-                    side = dict(counts=self.empty((512 * T,), torch.int16))
-                    check(lib.mu_tflat_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
-                                            _p(tiles), _p(side["counts"]), _p(slots), _p(err), st))
-                    if int(err.item()) != 0:
-                        raise RuntimeError("mu_tflat_plan: a row is not canonical")
-                else:
-                    side = dict(cont=self.empty((16 * T,), torch.int32))
-                    check(lib.mu_tperm_plan(n, d, X.nnz, _p(X.indptr), _p(X.indices), _p(xs_dst), Ct, _p(toff), None,
-                                            _p(tiles), _p(side["cont"]), _p(slots), st))
-                inv = plan["inv"]
-                cdst = (plan["sptr"][inv.long()] if inv is not None else plan["sptr"][:d]).contiguous()
+            ntile = self.empty((G,), torch.int32)
+            if flat:
+                err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+                self._launch(lib.mu_tflat_plan, n, d, X.nnz, X.indptr, X.indices, None, Ct, None, ntile, None, None, None,
+                             err)
+            else:
+                self._launch(lib.mu_tperm_plan, n, d, X.nnz, X.indptr, X.indices, None, Ct, None, ntile, None, None, None)
+            toff = torch.zeros((G + 1,), dtype=torch.int64, device=self.device)
+            toff[1:] = torch.cumsum(ntile.long(), 0)
+            T = int(toff[-1].item())
+            tiles = self.empty((T + G,), torch.int32)
+            slots = self.empty((X.nnz,), torch.int16)
+            if flat:
+                side = dict(counts=self.empty((512 * T,), torch.int16))
+                self._launch(lib.mu_tflat_plan, n, d, X.nnz, X.indptr, X.indices, xs_dst, Ct, toff, None, tiles,
+                             side["counts"], slots, err)
+                if int(err.item()) != 0:
+                    raise RuntimeError("mu_tflat_plan: a row is not canonical")
+            else:
+                side = dict(cont=self.empty((16 * T,), torch.int32))
+                self._launch(lib.mu_tperm_plan, n, d, X.nnz, X.indptr, X.indices, xs_dst, Ct, toff, None, tiles,
+                             side["cont"], slots)
+            inv = plan["inv"]
+            cdst = (plan["sptr"][inv.long()] if inv is not None else plan["sptr"][:d]).contiguous()
         except (RuntimeError, MemoryError):  # (torch's out-of-memory errors and a refused launch are RuntimeErrors)
             return None
         return dict(tile_cols=Ct, toff=toff, tiles=tiles, slots=slots, cdst=cdst, n_tiles=T, **side)
 
-    def _t4_geometry(self, n, d, nnz):
-        import ctypes as C
+    def _t4_tiling(self, n, d, nnz):
+        """(rows per row block, row blocks, columns of the widest tile) of the tile-staged transposition of this shape:
+        the one query of mu_tpack4_geometry."""
+        rpb, G, Ct = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib.mu_tpack4_geometry(n, d, nnz, ctypes.byref(rpb), ctypes.byref(G), ctypes.byref(Ct)))
+        return int(rpb.value), int(G.value), int(Ct.value)
 
-        rpb, G, Ct = C.c_int64(0), C.c_int(0), C.c_int(0)
-        check(self.lib.mu_tpack4_geometry(n, d, nnz, C.byref(rpb), C.byref(G), C.byref(Ct)))
-        return int(rpb.value), int(G.value)
+    def _t4_geometry(self, n, d, nnz):
+        """(rows per row block, row blocks): what the ranged products and the tests ask for."""
+        return self._t4_tiling(n, d, nnz)[:2]
 
     def _t4_prefix(self, work, n, d, nnz):
         rpb, G = self._t4_geometry(n, d, nnz)
@@ -1069,8 +1068,6 @@ class HipBackend(OperatorSet):
     def slice_stream(self, X: DeviceCSR, plan) -> dict:
         """Compact row stream of the slice's rows (mu_csr_slice_stream: range after range, rows in their own order) with
         the table of its 8192-column super-slab boundaries - the operand of X_S Q (spmm_slice)."""
-        import ctypes as C
-
         n, d = X.shape
         rg = plan["ranges"]
         n_s, nnz_s = plan["n_s"], plan["nnz_s"]
@@ -1078,11 +1075,9 @@ class HipBackend(OperatorSet):
         sptr = self.empty((n_s + 1,), torch.int64)
         ent = self.empty((max(nnz_s, 1),), torch.int64)
         rel = self.empty((S1 * max(n_s, 1),), torch.int32)
-        arr = lambda key, f=None: (C.c_int64 * len(rg))(*[(f(r) if f else r[key]) for r in rg])  # noqa: E731
-        with self._dev_ctx():
-            check(self.lib.mu_csr_slice_stream(len(rg), arr("row0"), arr(None, lambda r: r["row1"] - r["row0"]), arr("lo"),
-                                               arr("hi"), d, _p(X.indptr), _p(X.indices), _p(X.values),
-                                               _p(self._slab_ptr_of(X)), _p(sptr), _p(ent), _p(rel), self._stream()))
+        arr = lambda key, f=None: (ctypes.c_int64 * len(rg))(*[(f(r) if f else r[key]) for r in rg])  # noqa: E731
+        self._launch(self.lib.mu_csr_slice_stream, len(rg), arr("row0"), arr(None, lambda r: r["row1"] - r["row0"]),
+                     arr("lo"), arr("hi"), d, X.indptr, X.indices, X.values, self._slab_ptr_of(X), sptr, ent, rel)
         # K and the split of the column super-slabs over blockIdx.y: enough workgroups for two rounds of the chip
         n_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         K = 8
@@ -1097,26 +1092,27 @@ class HipBackend(OperatorSet):
         """Y_S = X_S Q [n_s x B] on the compact slice stream, column super-slabs split over the chip, partial products
         summed in fixed order.  B = 16 / 32 / 64; the kernel exists for 64 columns only: a narrower Q is zero-padded to
         64 and the leading B columns of the product returned (the padded ones are exact zeros)."""
-        import ctypes as C
-
         d, n_s = S["d"], S["n_s"]
         B = Q.shape[1] if Q.dim() == 2 else 0
         assert Q.shape == (d, B) and B in (16, 32, 64) and Q.dtype == torch.float32 and Q.is_contiguous()
         if B < 64:
-            Qp = self.zeros((d, 64), torch.float32)
-            Qp[:, :B] = Q
-            return self.spmm_slice(S, Qp)[:, :B].contiguous()
+            return self.spmm_slice(S, self._pad64(Q))[:, :B].contiguous()
         ns, g = S["S"], S["group"]
         ny = -(-ns // g)
         part = self.empty((ny, n_s, 64), torch.float32)
-        h = (C.c_int32 * (5 * ny))()
+        h = (ctypes.c_int32 * (5 * ny))()
         for r in range(ny):  # (the super-slabs r g .. (r + 1) g - 1 are contiguous in the columns and in every row)
             h[5 * r:5 * r + 5] = [r * g * 8192, min((r + 1) * g * 8192, d), r * g * 8192, r * g, min((r + 1) * g, ns)]
-        with self._dev_ctx():
-            check(self.lib.mu_spmm_stream_ranges_slab_f32(n_s, _p(S["sptr"]), _p(S["ent"]), None, S["K"], _p(Q), d,
-                                                          _p(part), n_s * 64, _p(S["rel"]), n_s, ny, h, 1,
-                                                          self.spmm_slab_ranged(S["K"]), self._stream()))
-        return part[0] if ny == 1 else part.sum(dim=0)
+        self._launch(self.lib.mu_spmm_stream_ranges_slab_f32, n_s, S["sptr"], S["ent"], None, S["K"], Q, d, part, n_s * 64,
+                     S["rel"], n_s, ny, h, 1, self.spmm_slab_ranged(S["K"]))
+        return _sum_parts(part)
+
+    def _pad64(self, A: torch.Tensor) -> torch.Tensor:
+        """The f32 block A [rows, B < 64] in the leading columns of a zeroed 64-column block: the one width the ranged
+        products exist for."""
+        P = self.zeros((A.shape[0], 64), torch.float32)
+        P[:, :A.shape[1]] = A
+        return P
 
     def spmm_slab_ranged(self, k_layout: int) -> int:
         """The slab width of a ranged product (B = 64, f32; the ranged entry takes the layout's K as it is and has no
@@ -1127,38 +1123,32 @@ class HipBackend(OperatorSet):
         """Z = X_S^T Y_S [d x B] on the row stream of X^T as it is: the slice's cells are <= 16 contiguous pieces of
         every row, found through the transposition's count prefixes (Xt.t4).  B = 16 / 32 / 64, a narrower Y_S
         zero-padded to the kernel's 64 columns like in spmm_slice."""
-        import ctypes as C
-
         d, n = Xt.shape
         t4, rg = Xt.t4, plan["ranges"]
         B = Ys.shape[1] if Ys.dim() == 2 else 0
         assert t4 is not None and t4["rpb"] == plan["rpb"] and Ys.shape == (plan["n_s"], B) and B in (16, 32, 64) \
             and Ys.dtype == torch.float32 and Ys.is_contiguous()
         if B < 64:
-            Yp = self.zeros((plan["n_s"], 64), torch.float32)
-            Yp[:, :B] = Ys
-            return self.spmm_slice_t(Xt, plan, Yp)[:, :B].contiguous()
+            return self.spmm_slice_t(Xt, plan, self._pad64(Ys))[:, :B].contiguous()
         Z = self.empty((d, 64), torch.float32)
-        h = (C.c_int32 * (5 * len(rg)))()
+        h = (ctypes.c_int32 * (5 * len(rg)))()
         q_off = 0
         for i, r in enumerate(rg):
             h[5 * i:5 * i + 5] = [r["row0"], r["row1"], q_off, r["g0"], r["g1"]]
             q_off += r["row1"] - r["row0"]
-        with self._dev_ctx():
-            check(self.lib.mu_spmm_stream_ranges_slab_f32(Xt.n_pos, _p(Xt.sptr), _p(Xt.ent), _p(Xt.perm), Xt.k, _p(Ys),
-                                                          plan["n_s"], _p(Z), 0, _p(t4["cnt"]), t4["stride"], len(rg), h,
-                                                          len(rg), self.spmm_slab_ranged(Xt.k), self._stream()))
+        self._launch(self.lib.mu_spmm_stream_ranges_slab_f32, Xt.n_pos, Xt.sptr, Xt.ent, Xt.perm, Xt.k, Ys, plan["n_s"], Z,
+                     0, t4["cnt"], t4["stride"], len(rg), h, len(rg), self.spmm_slab_ranged(Xt.k))
         return Z
 
     def split_streams(self, X: DeviceCSR):
         """(row streams of X, row streams of X^T) for an f64-valued CSR: see SplitStream."""
         assert X.values.dtype == torch.float64
-        hi = X.values.to(torch.float32)
-        rest = X.values - hi.to(torch.float64)
+        hi, rest = _split_hi(X.values)
         Xh = X.with_values(hi)
         s_hi, t_hi = self.stream(Xh), self.transpose_stream(Xh)
-        if bool((rest != 0).any().item()):
-            Xl = X.with_values(rest.to(torch.float32))
+        lo = _split_lo(rest)
+        if lo is not None:
+            Xl = X.with_values(lo)
             return SplitStream(s_hi, self.stream(Xl)), SplitStream(t_hi, self.transpose_stream(Xl))
         return SplitStream(s_hi, None), SplitStream(t_hi, None)
 
@@ -1210,11 +1200,11 @@ class HipBackend(OperatorSet):
         if X.values.dtype == torch.float32:
             return ell16_layout(X, waves, cols, self.slab_ptr_width, fill)
         assert wide and X.values.dtype == torch.float64
-        hi = X.values.to(torch.float32)
-        rest = X.values - hi.to(torch.float64)
+        hi, rest = _split_hi(X.values)
         e_hi = ell16_layout(X.with_values(hi), waves, cols, self.slab_ptr_width, fill)
-        if bool((rest != 0).any().item()):
-            return SplitEll(e_hi, ell16_layout(X.with_values(rest.to(torch.float32)), waves, cols, self.slab_ptr_width, fill))
+        lo = _split_lo(rest)
+        if lo is not None:
+            return SplitEll(e_hi, ell16_layout(X.with_values(lo), waves, cols, self.slab_ptr_width, fill))
         return SplitEll(e_hi, None)
 
     def ell16_pair(self, X: DeviceCSR, wide: bool = False):
@@ -1224,10 +1214,10 @@ class HipBackend(OperatorSet):
         if X.values.dtype == torch.float32:
             return self.ell16(X, wide), self.ell16(self.transpose_csr(X), wide)
         assert wide and X.values.dtype == torch.float64
-        hi = X.values.to(torch.float32)
-        rest = X.values - hi.to(torch.float64)
-        parts = [hi] + ([rest.to(torch.float32)] if bool((rest != 0).any().item()) else [])
+        hi, rest = _split_hi(X.values)
+        lo = _split_lo(rest)
         del rest
+        parts = [hi] if lo is None else [hi, lo]
         fw = [self.ell16(X.with_values(p), True) for p in parts]
         tr = [self.ell16(self.transpose_csr(X.with_values(p)), True) for p in parts]
         return SplitEll(fw[0], fw[1] if len(fw) > 1 else None), SplitEll(tr[0], tr[1] if len(tr) > 1 else None)
@@ -1238,23 +1228,19 @@ class HipBackend(OperatorSet):
         D = int(Y.shape[1])
         chunks = max(1, int(self.lib.mu_dense_col_moments_chunks(b - a, D)))
         part = self.empty((chunks, 2, D), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_dense_col_moments(_dt(Y),
-                                                int(a), int(b), D, _p(Y), chunks, _p(part), self._stream()))
+        self._launch(self.lib.mu_dense_col_moments, _dt(Y), int(a), int(b), D, Y, chunks, part)
         s = part.sum(dim=0)
         return s[0], s[1]
 
     def _ell16_fill(self, X, slab_cols, sp, perm, hdr, win_base, ent):
-        with self._dev_ctx():
-            check(self.lib.mu_ell16_fill(int(perm.numel()) // 16, X.shape[1], X.nnz, int(slab_cols), _p(X.indices), _p(X.values),
-                                         _p(sp), _p(perm), _p(hdr), _p(win_base), _p(ent), self._stream()))
+        self._launch(self.lib.mu_ell16_fill, int(perm.numel()) // 16, X.shape[1], X.nnz, int(slab_cols), X.indices, X.values,
+                     sp, perm, hdr, win_base, ent)
 
     def slab_ptr_width(self, X: DeviceCSR, width: int) -> torch.Tensor:
         """First entry of every row at or behind every multiple of ``width`` columns (+ the row's end)."""
         n, d = X.shape
         sp = self.empty((n * (-(-d // width) + 1),), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_slab_ptr_width(n, d, int(width), _p(X.indptr), _p(X.indices), _p(sp), self._stream()))
+        self._launch(self.lib.mu_csr_slab_ptr_width, n, d, int(width), X.indptr, X.indices, sp)
         return sp
 
     def spmm_ell(self, E: DeviceEll, Q: torch.Tensor, out=None, accumulate: bool = False) -> torch.Tensor:
@@ -1272,31 +1258,26 @@ class HipBackend(OperatorSet):
         # r06: an operand of a few thousand rows (one rank's shard of a sharded fit) is a few dozen workgroups that each
         # pull all of Q through their LDS - its column slabs are split over blockIdx.y, the partial products summed in
         # order (mu_spmm_ell16_parts: one part for every shape that fills a round of the chip by its rows)
-        import ctypes as C
-
-        wv, parts = C.c_int(0), C.c_int(1)
-        check(self.lib.mu_spmm_ell16_parts(n, d, int(wide), C.byref(wv), C.byref(parts)))
+        wv, parts = ctypes.c_int(0), ctypes.c_int(1)
+        check(self.lib.mu_spmm_ell16_parts(n, d, int(wide), ctypes.byref(wv), ctypes.byref(parts)))
         if parts.value > 1:
             slabs = -(-d // E.slab_cols)
             ny = -(-slabs // -(-slabs // parts.value))
             part = self.empty((ny, n, 16), Q.dtype)
             fn = self.lib.mu_spmm_ell16_parts_f64 if wide else self.lib.mu_spmm_ell16_parts_f32
-            with self._dev_ctx():
-                check(fn(wv.value, parts.value, int(E.perm.numel()), d, _p(E.hdr), _p(E.wave_base), _p(E.ent), _p(E.perm),
-                         _p(Q), _p(part), n * 16, self._stream()))
+            self._launch(fn, wv.value, parts.value, int(E.perm.numel()), d, E.hdr, E.wave_base, E.ent, E.perm, Q, part,
+                         n * 16)
             if accumulate:
                 out += part.sum(dim=0)
             else:
                 torch.sum(part, dim=0, out=out)
             return out
-        with self._dev_ctx():
-            if wide:
-                check(self.lib.mu_spmm_ell16_f64(E.waves, int(E.perm.numel()), d, _p(E.hdr), _p(E.wave_base),
-                                                 _p(E.ent), _p(E.perm), _p(Q), _p(out), int(bool(accumulate)),
-                                                 self._stream()))
-            else:
-                check(self.lib.mu_spmm_ell16_f32(E.waves, int(E.perm.numel()), d, _p(E.hdr), _p(E.wave_base),
-                                                 _p(E.ent), _p(E.perm), _p(Q), _p(out), self._stream()))
+        if wide:
+            self._launch(self.lib.mu_spmm_ell16_f64, E.waves, int(E.perm.numel()), d, E.hdr, E.wave_base, E.ent, E.perm, Q,
+                         out, int(bool(accumulate)))
+        else:
+            self._launch(self.lib.mu_spmm_ell16_f32, E.waves, int(E.perm.numel()), d, E.hdr, E.wave_base, E.ent, E.perm, Q,
+                         out)
         return out
 
     def stream_both(self, X: DeviceCSR):
@@ -1398,23 +1379,19 @@ class HipBackend(OperatorSet):
             if out is None:
                 assert not accumulate
                 out = self.empty((n, B), Q.dtype)
-            with self._dev_ctx():
-                if wide:
-                    check(self.lib.mu_spmm_stream_f64(X.n_pos, d, _p(X.sptr), _p(X.ent), _p(X.perm), X.k,
-                                                      _p(Q), B, _p(out), int(bool(accumulate)), self._stream()))
-                else:
-                    check(self.lib.mu_spmm_stream_slab_f32(X.n_pos, d, _p(X.sptr), _p(X.ent), _p(X.perm), X.k,
-                                                           _p(Q), B, _p(out), self.spmm_slab(X.k, X.n_pos, B),
-                                                           self._stream()))
+            if wide:
+                self._launch(self.lib.mu_spmm_stream_f64, X.n_pos, d, X.sptr, X.ent, X.perm, X.k, Q, B, out,
+                             int(bool(accumulate)))
+            else:
+                self._launch(self.lib.mu_spmm_stream_slab_f32, X.n_pos, d, X.sptr, X.ent, X.perm, X.k, Q, B, out,
+                             self.spmm_slab(X.k, X.n_pos, B))
             return out
         if X.values.dtype != Q.dtype:
             raise TypeError("spmm needs values and dense block of one dtype")
         if out is None:
             out = self.empty((n, B), Q.dtype)
         fn = self.lib.mu_spmm_f32 if Q.dtype == torch.float32 else self.lib.mu_spmm_f64
-        with self._dev_ctx():
-            check(fn(n, d, _p(X.indptr), _p(X.indices), _p(X.values), _p(Q), B, _p(out), 0,
-                     self._stream()))
+        self._launch(fn, n, d, X.indptr, X.indices, X.values, Q, B, out, 0)
         return out
 
     def gram(self, A: torch.Tensor):
@@ -1422,10 +1399,8 @@ class HipBackend(OperatorSet):
         assert A.dtype == torch.float32 and A.is_contiguous()
         G = self.empty((B, B), torch.float64)
         cs = self.empty((B,), torch.float64)
-        wb = int(self.lib.mu_gram_worksize(n, B))
-        work = self.empty((wb,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_gram_f32(n, B, _p(A), _p(G), _p(cs), _p(work), wb, self._stream()))
+        work, wb = self._work(self.lib.mu_gram_worksize(n, B))
+        self._launch(self.lib.mu_gram_f32, n, B, A, G, cs, work, wb)
         return G, cs
 
     def gram_cross(self, A: torch.Tensor, Bm: torch.Tensor) -> torch.Tensor:
@@ -1434,10 +1409,8 @@ class HipBackend(OperatorSet):
         assert Bm.shape == A.shape and A.dtype == torch.float32 and Bm.dtype == torch.float32
         assert A.is_contiguous() and Bm.is_contiguous()
         Cm = self.empty((B, B), torch.float64)
-        wb = int(self.lib.mu_gram_worksize(n, B))
-        work = self.empty((wb,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_gram_cross_f32(n, B, _p(A), _p(Bm), _p(Cm), _p(work), wb, self._stream()))
+        work, wb = self._work(self.lib.mu_gram_worksize(n, B))
+        self._launch(self.lib.mu_gram_cross_f32, n, B, A, Bm, Cm, work, wb)
         return Cm
 
     def apply(self, A: torch.Tensor, M: torch.Tensor, bias=None, out=None) -> torch.Tensor:
@@ -1445,8 +1418,7 @@ class HipBackend(OperatorSet):
         assert M.shape == (B, B) and M.dtype == torch.float32 and M.is_contiguous()
         if out is None:
             out = torch.empty_like(A)
-        with self._dev_ctx():
-            check(self.lib.mu_dense_apply_f32(n, B, _p(A), _p(M), _p(bias), _p(out), self._stream()))
+        self._launch(self.lib.mu_dense_apply_f32, n, B, A, M, bias, out)
         return out
 
     def project_out_block(self, Q: torch.Tensor, C: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
@@ -1454,8 +1426,7 @@ class HipBackend(OperatorSet):
         n, B = Q.shape
         assert Z.shape == Q.shape and C.shape == (B, B) and C.dtype == torch.float64 and C.is_contiguous()
         assert Q.dtype == torch.float32 and Z.dtype == torch.float32 and Z.is_contiguous() and Q.is_contiguous()
-        with self._dev_ctx():
-            check(self.lib.mu_dense_project_out_f32(n, B, _p(Q), _p(C), _p(Z), self._stream()))
+        self._launch(self.lib.mu_dense_project_out_f32, n, B, Q, C, Z)
         return Z
 
     def chol_rinv(self, G: torch.Tensor, w: int, flag: torch.Tensor) -> torch.Tensor:
@@ -1464,14 +1435,12 @@ class HipBackend(OperatorSet):
         B = G.shape[0]
         assert G.dtype == torch.float64 and G.is_contiguous() and flag.dtype == torch.int32
         M = self.empty((B, B), torch.float32)
-        with self._dev_ctx():
-            check(self.lib.mu_chol_rinv_f64(B, int(w), _p(G), _p(M), _p(flag), self._stream()))
+        self._launch(self.lib.mu_chol_rinv_f64, B, int(w), G, M, flag)
         return M
 
     def randn(self, rows: int, B: int, seed: int) -> torch.Tensor:
         out = self.empty((rows, B), torch.float32)
-        with self._dev_ctx():
-            check(self.lib.mu_randn_f32(rows * B, int(seed) & (2**64 - 1), _p(out), self._stream()))
+        self._launch(self.lib.mu_randn_f32, rows * B, int(seed) & (2**64 - 1), out)
         return out
 
     # -- MOFA+: tall-skinny products of a dense view with 16-column factor blocks ------------------
@@ -1485,11 +1454,10 @@ class HipBackend(OperatorSet):
         assert T16.shape == (D, 16) and (mixed or T16.dtype == Y.dtype) and T16.is_contiguous() and Y.stride(1) == 1
         out = self.empty((n, 16), T16.dtype)
         ld = Y.stride(0) if n > 1 else D
-        with self._dev_ctx():
-            if mixed:
-                check(self.lib.mu_skinny_nn_f64_f32(n, D, ld, _p(Y), _p(T16), _p(out), self._stream()))
-            else:
-                check(self.lib.mu_skinny_nn(_dt(Y), n, D, ld, _p(Y), _p(T16), _p(out), self._stream()))
+        if mixed:
+            self._launch(self.lib.mu_skinny_nn_f64_f32, n, D, ld, Y, T16, out)
+        else:
+            self._launch(self.lib.mu_skinny_nn, _dt(Y), n, D, ld, Y, T16, out)
         return out
 
     def skinny_tn(self, Y: torch.Tensor, Z16: torch.Tensor) -> torch.Tensor:
@@ -1498,32 +1466,24 @@ class HipBackend(OperatorSet):
         mixed = Y.dtype == torch.float32 and Z16.dtype == torch.float64
         assert Z16.shape == (n, 16) and (mixed or Z16.dtype == Y.dtype) and Z16.is_contiguous() and Y.stride(1) == 1
         out = self.empty((D, 16), Z16.dtype)
-        wb = int(self.lib.mu_skinny_tn_worksize(_dt(Z16), n, D))
-        work = self.empty((wb,), torch.uint8)
+        work, wb = self._work(self.lib.mu_skinny_tn_worksize(_dt(Z16), n, D))
         ld = Y.stride(0) if n > 1 else D
-        with self._dev_ctx():
-            if mixed:
-                check(self.lib.mu_skinny_tn_f64_f32(n, D, ld, _p(Y), _p(Z16), _p(out), _p(work), wb, self._stream()))
-            else:
-                check(self.lib.mu_skinny_tn(_dt(Y), n, D, ld, _p(Y), _p(Z16), _p(out), _p(work), wb, self._stream()))
+        if mixed:
+            self._launch(self.lib.mu_skinny_tn_f64_f32, n, D, ld, Y, Z16, out, work, wb)
+        else:
+            self._launch(self.lib.mu_skinny_tn, _dt(Y), n, D, ld, Y, Z16, out, work, wb)
         return out
 
     # -- MOFA+ coordinate updates (reference tools.py:585 -> mofapy2 node updates) -----------
     def mofa_update_w(self, B, tau, Gz, Z2, alpha, lth, l1mth, spikeslab, EW, EW2, gamma, EWh2, sig2):
         G, D, K = B.shape
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_update_w(_dt(EW), D, K, G, _p(B), _p(tau), _p(Gz), _p(Z2),
-                                            _p(alpha), _p(lth), _p(l1mth), int(bool(spikeslab)),
-                                            _p(EW), _p(EW2), _p(gamma), _p(EWh2), _p(sig2),
-                                            self._stream()))
+        self._launch(self.lib.mu_mofa_update_w, _dt(EW), D, K, G, B, tau, Gz, Z2, alpha, lth, l1mth, int(bool(spikeslab)),
+                     EW, EW2, gamma, EWh2, sig2)
 
     def mofa_update_z(self, A, pres, grp, Gw, dw2, alphaz, EZ, EZ2, sig2, corr=None):
         M, N, K = A.shape
         G = alphaz.shape[0]
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_update_z(_dt(EZ), N, K, M, G, _p(A), _p(pres), _p(grp), _p(Gw),
-                                            _p(dw2), _p(alphaz), _p(corr), _p(EZ), _p(EZ2), _p(sig2),
-                                            self._stream()))
+        self._launch(self.lib.mu_mofa_update_z, _dt(EZ), N, K, M, G, A, pres, grp, Gw, dw2, alphaz, corr, EZ, EZ2, sig2)
 
     def mofa_rowstats_work(self, K: int) -> torch.Tensor:
         return self.empty((int(self.lib.mu_mofa_rowstats_work_doubles(int(K))),), torch.float64)
@@ -1534,19 +1494,15 @@ class HipBackend(OperatorSet):
         K = E.shape[1]
         ld = int(out_pad.shape[1]) if out_pad is not None else 0
         ld_t = int(out_t.shape[1]) if out_t is not None else 0
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_rowstats(_dt(E), int(r0), int(r1), K, _p(E), _p(E2), _p(wgt), _p(aux),
-                                            int(bool(scale_out)), _p(out_pad), ld, int(col0), _p(out_t), ld_t,
-                                            _p(gram), _p(s2), _p(s1), _p(work), self._stream()))
+        self._launch(self.lib.mu_mofa_rowstats, _dt(E), int(r0), int(r1), K, E, E2, wgt, aux, int(bool(scale_out)), out_pad,
+                     ld, int(col0), out_t, ld_t, gram, s2, s1, work)
 
     def umap_strengths(self, dist, idx, target: float, mean_all: float):
         """Membership strengths of a neighbour table [n, k] (include/muon_amd.h): a thread per row."""
         n, k = dist.shape
         assert dist.dtype == torch.float64 and idx.dtype == torch.int64 and dist.is_contiguous() and idx.is_contiguous()
         out = self.empty((n, k), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_umap_strengths_f64(int(n), int(k), _p(dist), _p(idx), float(target), float(mean_all),
-                                                 _p(out), self._stream()))
+        self._launch(self.lib.mu_umap_strengths_f64, int(n), int(k), dist, idx, float(target), float(mean_all), out)
         return out
 
     def wnn_bandwidth(self, X, g_indptr, g_indices, r_indptr, r_indices, n_bw: int, bbox: float):
@@ -1554,18 +1510,14 @@ class HipBackend(OperatorSet):
         n, p = X.shape
         out = self.empty((n,), torch.float64)
         over = self.zeros((1,), torch.int32)
-        with self._dev_ctx():
-            check(self.lib.mu_wnn_bandwidth_f64(int(n), int(p), _p(X), _p(g_indptr), _p(g_indices), _p(r_indptr),
-                                                _p(r_indices), int(n_bw), float(bbox), _p(out), _p(over),
-                                                self._stream()))
+        self._launch(self.lib.mu_wnn_bandwidth_f64, int(n), int(p), X, g_indptr, g_indices, r_indptr, r_indices, int(n_bw),
+                     float(bbox), out, over)
         return out, bool(int(over.item()))
 
     def knn_filter(self, Xq, Xc, sqq, sqc, thr, self_pos, c_lo, c_hi, buf_pos, buf_d, cnt):
         """Candidates of positions [c_lo, c_hi) that beat the queries' thresholds (include/muon_amd.h)."""
-        with self._dev_ctx():
-            check(self.lib.mu_knn_filter_f64(int(Xq.shape[0]), int(c_lo), int(c_hi), int(Xq.shape[1]), _p(Xq), _p(Xc),
-                                             _p(sqq), _p(sqc), _p(thr), _p(self_pos), int(buf_pos.shape[1]),
-                                             _p(buf_pos), _p(buf_d), _p(cnt), self._stream()))
+        self._launch(self.lib.mu_knn_filter_f64, int(Xq.shape[0]), int(c_lo), int(c_hi), int(Xq.shape[1]), Xq, Xc, sqq, sqc,
+                     thr, self_pos, int(buf_pos.shape[1]), buf_pos, buf_d, cnt)
 
     def knn_merge(self, cur_d, cur_p, buf_d, buf_pos, cnt):
         """list ++ buffer -> (the kc smallest distances ascending, their positions, the new thresholds)
@@ -1573,17 +1525,15 @@ class HipBackend(OperatorSet):
         n, kc = cur_d.shape
         out_d, out_p = torch.empty_like(cur_d), torch.empty_like(cur_p)
         thr = self.empty((n,), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_knn_merge_f64(int(n), int(kc), int(buf_d.shape[1]), _p(cur_d), _p(cur_p), _p(buf_d),
-                                            _p(buf_pos), _p(cnt), _p(out_d), _p(out_p), _p(thr), self._stream()))
+        self._launch(self.lib.mu_knn_merge_f64, int(n), int(kc), int(buf_d.shape[1]), cur_d, cur_p, buf_d, buf_pos, cnt,
+                     out_d, out_p, thr)
         return out_d, out_p, thr
 
     def densify_rows(self, X: DeviceCSR, lo: int, hi: int) -> torch.Tensor:
         """Rows [lo, hi) of a device CSR as a dense chunk (include/muon_amd.h)."""
         out = self.empty((hi - lo, X.shape[1]), X.values.dtype)
-        with self._dev_ctx():
-            check(self.lib.mu_csr_densify_rows(_dt(X.values), int(lo), int(hi), int(X.shape[1]), _p(X.indptr),
-                                               _p(X.indices), _p(X.values), _p(out), self._stream()))
+        self._launch(self.lib.mu_csr_densify_rows, _dt(X.values), int(lo), int(hi), int(X.shape[1]), X.indptr, X.indices,
+                     X.values, out)
         return out
 
     # -- muon.prot.pp.dsb (csrc/prot.hip) ----------------------------------------------------------------------------
@@ -1596,16 +1546,13 @@ class HipBackend(OperatorSet):
         is (no densifying) or a dense [n, d] tensor, f32 / f64; pseudocount > 0."""
         n, d = (int(s) for s in X.shape)
         mean, std = self.empty((d,), torch.float64), self.empty((d,), torch.float64)
-        wb = int(self.lib.mu_prot_moments_worksize(n, d))
-        work = self.empty((max(wb, 8),), torch.uint8)
-        with self._dev_ctx():
-            if isinstance(X, DeviceCSR):
-                check(self.lib.mu_prot_log_moments_csr(_dt(X.values), n, d, _p(X.indptr), _p(X.indices), _p(X.values),
-                                                       float(pseudocount), _p(mean), _p(std), _p(work), wb, self._stream()))
-            else:
-                assert X.is_contiguous()
-                check(self.lib.mu_prot_log_moments_dense(_dt(X), n, d, _p(X), float(pseudocount), _p(mean), _p(std),
-                                                         _p(work), wb, self._stream()))
+        work, wb = self._work(self.lib.mu_prot_moments_worksize(n, d), floor=8)
+        if isinstance(X, DeviceCSR):
+            self._launch(self.lib.mu_prot_log_moments_csr, _dt(X.values), n, d, X.indptr, X.indices, X.values,
+                         float(pseudocount), mean, std, work, wb)
+        else:
+            assert X.is_contiguous()
+            self._launch(self.lib.mu_prot_log_moments_dense, _dt(X), n, d, X, float(pseudocount), mean, std, work, wb)
         return mean, std
 
     def prot_dsb_fit(self, X, pseudocount: float, mean, std, resp):
@@ -1625,16 +1572,13 @@ class HipBackend(OperatorSet):
         bg = self.empty((n,), torch.float64)
         bic = self.empty((n, 2), torch.float64)
         niter = self.empty((n, 2), torch.int32)
-        with self._dev_ctx():
-            if isinstance(X, DeviceCSR):
-                check(self.lib.mu_prot_dsb_fit(_dt(X.values), n, d, None, _p(X.indptr), _p(X.indices), _p(X.values),
-                                               float(pseudocount), _p(mean), _p(std), _p(resp), cs, ms, _p(scaled), _p(bg),
-                                               _p(bic), _p(niter), self._stream()))
-            else:
-                assert X.is_contiguous()
-                check(self.lib.mu_prot_dsb_fit(_dt(X), n, d, _p(X), None, None, None, float(pseudocount), _p(mean),
-                                               _p(std), _p(resp), cs, ms, _p(scaled), _p(bg), _p(bic), _p(niter),
-                                               self._stream()))
+        if isinstance(X, DeviceCSR):
+            self._launch(self.lib.mu_prot_dsb_fit, _dt(X.values), n, d, None, X.indptr, X.indices, X.values,
+                         float(pseudocount), mean, std, resp, cs, ms, scaled, bg, bic, niter)
+        else:
+            assert X.is_contiguous()
+            self._launch(self.lib.mu_prot_dsb_fit, _dt(X), n, d, X, None, None, None, float(pseudocount), mean, std, resp,
+                         cs, ms, scaled, bg, bic, niter)
         return scaled, bg, bic, niter
 
     # -- muon.tl.ica (csrc/ica.hip) ----------------------------------------------------------------------------------
@@ -1655,13 +1599,12 @@ class HipBackend(OperatorSet):
         assert Z.dim() == 2 and (Z.shape[1] == 0 or Z.stride(1) == 1)
         ld = int(Z.stride(0)) if n > 1 else int(Z.shape[1])
         A, gp = self.empty((k, k), torch.float64), self.empty((k,), torch.float64)
-        wb = int(self.lib.mu_ica_worksize(n, k, int(max_blocks))) if 1 <= k <= self.ica_max_components() else 0
-        work = self.empty((max(wb, 8),), torch.uint8)
+        work, wb = self._work(
+            self.lib.mu_ica_worksize(n, k, int(max_blocks)) if 1 <= k <= self.ica_max_components() else 0, floor=8)
         if min(int(Z.shape[1]), ld) < (k + 15) // 16 * 16:
             ld = int(Z.shape[1])  # (a view narrower than the padded width: the library refuses it by its ldz)
-        with self._dev_ctx():
-            check(self.lib.mu_ica_sweep_f64(n, k, ld, _p(Z), _p(W), self._ICA_FUN[fun], float(alpha), _p(A), _p(gp),
-                                            _p(work), wb, int(max_blocks), self._stream()))
+        self._launch(self.lib.mu_ica_sweep_f64, n, k, ld, Z, W, self._ICA_FUN[fun], float(alpha), A, gp, work, wb,
+                     int(max_blocks))
         return A, gp
 
     # -- muon.atac.pp.scopen (csrc/nmf.hip) ----------------------------------------------------------------------------
@@ -1691,12 +1634,10 @@ class HipBackend(OperatorSet):
             assert out.dtype == f64 and out.dim() == 2 and int(out.shape[0]) == rows and out.is_contiguous()
         assert oscale is None or out is not None
         gram, viol = self.empty((k, k), f64), self.empty((1,), f64)
-        wb = int(self.lib.mu_nmf_cd_worksize(rows, k, int(max_blocks))) if 1 <= k <= self.nmf_max_components() else 0
-        work = self.empty((max(wb, 8),), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_nmf_cd_sweep_f64(rows, k, _p(W), ld(W), _p(B), ld(B), _p(bscale), _p(G), float(l1),
-                                               _p(oscale), _p(out), 0 if out is None else int(out.shape[1]), _p(gram),
-                                               _p(viol), _p(work), wb, int(max_blocks), self._stream()))
+        work, wb = self._work(
+            self.lib.mu_nmf_cd_worksize(rows, k, int(max_blocks)) if 1 <= k <= self.nmf_max_components() else 0, floor=8)
+        self._launch(self.lib.mu_nmf_cd_sweep_f64, rows, k, W, ld(W), B, ld(B), bscale, G, float(l1), oscale, out,
+                     0 if out is None else int(out.shape[1]), gram, viol, work, wb, int(max_blocks))
         return gram, viol
 
     # -- muon.tl.mofa with smooth_covariate (csrc/gp.hip) --------------------------------------------------------------
@@ -1715,10 +1656,8 @@ class HipBackend(OperatorSet):
         pass over V, every sum in the order include/muon_amd.h states - two calls agree bit for bit."""
         n, ldv = self._gp_square(V, r)
         u = self.empty((n,), torch.float64)
-        wb = int(self.lib.mu_gp_project_worksize(n))
-        work = self.empty((max(wb, 8),), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_gp_project_f64(n, _p(V), ldv, _p(r), _p(u), _p(work), wb, self._stream()))
+        work, wb = self._work(self.lib.mu_gp_project_worksize(n), floor=8)
+        self._launch(self.lib.mu_gp_project_f64, n, V, ldv, r, u, work, wb)
         return u
 
     def gp_posterior(self, V, g, u):
@@ -1726,8 +1665,7 @@ class HipBackend(OperatorSet):
         diagonal of the posterior covariance of a factor on MEFISTO's eigen route.  Two calls agree bit for bit."""
         n, ldv = self._gp_square(V, g, u)
         m, dc = self.empty((n,), torch.float64), self.empty((n,), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_gp_posterior_f64(n, _p(V), ldv, _p(g), _p(u), _p(m), _p(dc), self._stream()))
+        self._launch(self.lib.mu_gp_posterior_f64, n, V, ldv, g, u, m, dc)
         return m, dc
 
     # -- muon_amd.rna.pp / muon_amd.tl.pca (csrc/rna.hip) --------------------------------------------------------------
@@ -1743,10 +1681,8 @@ class HipBackend(OperatorSet):
         assert Xt.indptr.dtype == torch.int64 and int(Xt.indptr.numel()) == d + 1 and Xt.indptr.is_contiguous()
         assert Xt.values.is_contiguous()
         sums, cnt = self.zeros((4, d), torch.float64), self.empty((d,), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_gene_moments(_dt(Xt.values), d, int(Xt.values.numel()), _p(Xt.indptr), _p(Xt.values),
-                                           float(c), int(bool(with_e)), _p(sums), _p(cnt), int(max_blocks),
-                                           self._stream()))
+        self._launch(self.lib.mu_gene_moments, _dt(Xt.values), d, int(Xt.values.numel()), Xt.indptr, Xt.values, float(c),
+                     int(bool(with_e)), sums, cnt, int(max_blocks))
         return sums, cnt
 
     def value_sweep(self, X: DeviceCSR, div=None, log: bool = False, log_div: float = 0.0, out=None):
@@ -1761,9 +1697,8 @@ class HipBackend(OperatorSet):
         if out is None:
             out = torch.empty_like(v)
         assert out.dtype == v.dtype and out.shape == v.shape and out.is_contiguous()
-        with self._dev_ctx():
-            check(self.lib.mu_rna_value_sweep(_dt(v), n, int(v.numel()), _p(X.indptr), _p(v), _p(out), _p(div),
-                                              int(bool(log)), float(log_div), self._stream()))
+        self._launch(self.lib.mu_rna_value_sweep, _dt(v), n, int(v.numel()), X.indptr, v, out, div, int(bool(log)),
+                     float(log_div))
         return out
 
     def shift_cols(self, Y: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
@@ -1771,8 +1706,7 @@ class HipBackend(OperatorSet):
         n, B = Y.shape
         assert Y.dtype == torch.float32 and Y.is_contiguous() and Y.data_ptr() % 16 == 0
         assert m.dtype == torch.float64 and tuple(m.shape) == (B,) and m.is_contiguous()
-        with self._dev_ctx():
-            check(self.lib.mu_shift_cols_f32(int(n), int(B), _p(Y), _p(m), self._stream()))
+        self._launch(self.lib.mu_shift_cols_f32, int(n), int(B), Y, m)
         return Y
 
     def scale_rows(self, s: torch.Tensor, Q: torch.Tensor, out=None) -> torch.Tensor:
@@ -1784,8 +1718,7 @@ class HipBackend(OperatorSet):
         assert Q.dtype == torch.float32 and Q.is_contiguous() and Q.data_ptr() % 16 == 0
         assert out.dtype == torch.float32 and out.shape == Q.shape and out.is_contiguous() and out.data_ptr() % 16 == 0
         assert s.dtype == torch.float32 and tuple(s.shape) == (d,) and s.is_contiguous()
-        with self._dev_ctx():
-            check(self.lib.mu_scale_rows_f32(int(d), int(B), _p(s), _p(Q), _p(out), self._stream()))
+        self._launch(self.lib.mu_scale_rows_f32, int(d), int(B), s, Q, out)
         return out
 
     # -- muon.tl.snf (csrc/snf.hip) ----------------------------------------------------------------------------------
@@ -1826,9 +1759,7 @@ class HipBackend(OperatorSet):
         if n2 != n:
             raise ValueError("out: the shape of D")
         means = self.empty((max(n, 1),), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_snf_affinity_f64(n, int(k), ldd, _p(D), ldw, _p(out), float(sigma), float(eps), _p(means),
-                                               self._stream()))
+        self._launch(self.lib.mu_snf_affinity_f64, n, int(k), ldd, D, ldw, out, float(sigma), float(eps), means)
         return out
 
     def snf_normalize(self, X, out=None):
@@ -1839,8 +1770,7 @@ class HipBackend(OperatorSet):
         if n2 != n:
             raise ValueError("out: the shape of X")
         r = self.empty((max(n, 1),), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_snf_normalize_f64(n, ldx, _p(X), ldo, _p(out), _p(r), self._stream()))
+        self._launch(self.lib.mu_snf_normalize_f64, n, ldx, X, ldo, out, r)
         return out
 
     def snf_topk(self, W, k: int):
@@ -1848,8 +1778,7 @@ class HipBackend(OperatorSet):
         n, ldw = self._snf_square(W, "W")
         idx = self.empty((n, int(k)), torch.int32)
         val = self.empty((n, int(k)), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_snf_topk_f64(n, int(k), ldw, _p(W), _p(idx), _p(val), self._stream()))
+        self._launch(self.lib.mu_snf_topk_f64, n, int(k), ldw, W, idx, val)
         return idx, val
 
     def snf_p_scale(self, indptr, cols, vals):
@@ -1860,9 +1789,7 @@ class HipBackend(OperatorSet):
         assert indptr.is_contiguous() and cols.is_contiguous() and vals.is_contiguous() and cols.numel() == vals.numel()
         n = int(indptr.numel()) - 1
         rowsum = self.empty((max(n, 1),), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_snf_p_scale_f64(n, int(vals.numel()), _p(indptr), _p(cols), _p(vals), _p(rowsum),
-                                              self._stream()))
+        self._launch(self.lib.mu_snf_p_scale_f64, n, int(vals.numel()), indptr, cols, vals, rowsum)
         return rowsum[:n]
 
     def snf_diffuse(self, P, terms, out):
@@ -1884,9 +1811,8 @@ class HipBackend(OperatorSet):
         if len(lds) > 1:
             raise ValueError("terms: one leading dimension")
         ptrs = (ctypes.c_void_p * max(len(terms), 1))(*[t.data_ptr() for t in terms])
-        with self._dev_ctx():
-            check(self.lib.mu_snf_diffuse_f64(n, len(terms), ptrs, lds.pop() if lds else max(n, 1), _p(indptr), _p(cols),
-                                              _p(vals), ldy, _p(out), self._stream()))
+        self._launch(self.lib.mu_snf_diffuse_f64, n, len(terms), ptrs, lds.pop() if lds else max(n, 1), indptr, cols, vals,
+                     ldy, out)
         return out
 
     # -- muon.atac.tl.rank_peaks_groups (csrc/rank.hip) --------------------------------------------------------------
@@ -1916,9 +1842,8 @@ class HipBackend(OperatorSet):
         B = int(n_buckets)
         s, ss = self.empty((d, B), torch.float64), self.empty((d, B), torch.float64)
         cnt = self.empty((d, B), torch.int64)
-        with self._dev_ctx():
-            check(self.lib.mu_group_moments(_dt(values), d, n, int(cells.numel()), B, _p(indptr), _p(cells), _p(values),
-                                            _p(labels), _p(s), _p(ss), _p(cnt), self._stream()))
+        self._launch(self.lib.mu_group_moments, _dt(values), d, n, int(cells.numel()), B, indptr, cells, values, labels, s,
+                     ss, cnt)
         return s, ss, cnt
 
     def rank_sums(self, Xt_sorted: DeviceCSR, labels, n_buckets: int):
@@ -1931,9 +1856,8 @@ class HipBackend(OperatorSet):
         n_kept = int((labels >= 0).sum().item())
         rs = self.empty((d, B), torch.float64)
         zr, tie = self.empty((d,), torch.float64), self.empty((d,), torch.float64)
-        with self._dev_ctx():
-            check(self.lib.mu_rank_sums(_dt(values), d, n, int(cells.numel()), B, n_kept, _p(indptr), _p(cells),
-                                        _p(values), _p(labels), _p(rs), _p(zr), _p(tie), self._stream()))
+        self._launch(self.lib.mu_rank_sums, _dt(values), d, n, int(cells.numel()), B, n_kept, indptr, cells, values, labels,
+                     rs, zr, tie)
         return rs, zr, tie
 
     # -- muon.tl.leiden / muon.tl.louvain (csrc/cluster.hip) ---------------------------------------------------------
@@ -1973,10 +1897,8 @@ class HipBackend(OperatorSet):
         if int(overflow.numel()) < 1:
             raise ValueError("overflow: at least one entry")
         h_coef = (ctypes.c_double * max(L, 1))(*[float(c) for c in coef])
-        with self._dev_ctx():
-            check(self.lib.mu_cluster_move_f64(int(verts.numel()), _p(verts), nv, int(vals.numel()), _p(indptr), _p(cols),
-                                               _p(vals), _p(labels), _p(bound), _p(size), L, _p(P), _p(K), h_coef,
-                                               1 if only_single else 0, _p(prop), _p(score), _p(overflow), self._stream()))
+        self._launch(self.lib.mu_cluster_move_f64, int(verts.numel()), verts, nv, int(vals.numel()), indptr, cols, vals,
+                     labels, bound, size, L, P, K, h_coef, 1 if only_single else 0, prop, score, overflow)
         return prop, score
 
     def cluster_segsum(self, vals, ptr):
@@ -1990,8 +1912,7 @@ class HipBackend(OperatorSet):
         out = self.empty((nseg, w), torch.float64)
         if w == 0:
             return out
-        with self._dev_ctx():
-            check(self.lib.mu_cluster_segsum_f64(n, nseg, w, _p(vals), _p(ptr), _p(out), self._stream()))
+        self._launch(self.lib.mu_cluster_segsum_f64, n, nseg, w, vals, ptr, out)
         return out
 
     # -- muon.tl.umap (csrc/umap.hip) -----------------------------------------------------------------------------------
@@ -2019,10 +1940,8 @@ class HipBackend(OperatorSet):
             raise TypeError("E: a contiguous int64 tensor")
         if cols.numel() != E.numel():
             raise ValueError("cols and E: one entry each per edge")
-        with self._dev_ctx():
-            check(self.lib.mu_umap_epoch_f64(n, int(cols.numel()), _p(indptr), _p(cols), _p(E), dim, int(epoch),
-                                             int(n_epochs), int(rate), float(a), float(b), float(gamma), float(alpha_e),
-                                             int(seed) & 0xFFFFFFFFFFFFFFFF, _p(Y_in), _p(Y_out), self._stream()))
+        self._launch(self.lib.mu_umap_epoch_f64, n, int(cols.numel()), indptr, cols, E, dim, int(epoch), int(n_epochs),
+                     int(rate), float(a), float(b), float(gamma), float(alpha_e), int(seed) & 0xFFFFFFFFFFFFFFFF, Y_in, Y_out)
         return Y_out
 
     # -- muon.atac.tl.scan_sequences (csrc/motif.hip) ----------------------------------------------------------------
@@ -2046,8 +1965,7 @@ class HipBackend(OperatorSet):
             raise TypeError("codes uint8 [total], offsets int64 [n_seq + 1], n_seq >= 1")
         codes, offsets = codes.contiguous(), offsets.contiguous()
         room = self.empty((total,), torch.uint8)
-        with self._dev_ctx():
-            check(self.lib.mu_motif_room(total, n_seq, _p(codes), _p(offsets), _p(room), self._stream()))
+        self._launch(self.lib.mu_motif_room, total, n_seq, codes, offsets, room)
         return room
 
     def motif_scan(self, codes, offsets, bank):
@@ -2069,35 +1987,28 @@ class HipBackend(OperatorSet):
         codes, offsets = codes.contiguous(), offsets.contiguous()
         n_ptiles = -(-total // self.motif_tile())
         counts = self.empty((nt * n_ptiles,), torch.int32)
-        with self._dev_ctx():
-            check(self.lib.mu_motif_count(total, n_seq, nt, _p(codes), _p(room), _p(B), _p(tl), _p(ml), _p(th),
-                                          _p(counts), self._stream()))
+        self._launch(self.lib.mu_motif_count, total, n_seq, nt, codes, room, B, tl, ml, th, counts)
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         n_hits = int(ends[-1].item()) if ends.numel() else 0
         base = (ends - counts).contiguous()
         seq, mot, pos = (self.empty((n_hits,), torch.int32) for _ in range(3))
         score = self.empty((n_hits,), torch.float64)
         if n_hits:
-            with self._dev_ctx():
-                check(self.lib.mu_motif_write(total, n_seq, nt, _p(codes), _p(room), _p(offsets), _p(B), _p(tl), _p(ml),
-                                              _p(th), _p(og), _p(counts), _p(base), n_hits, _p(seq), _p(mot), _p(pos),
-                                              _p(score), self._stream()))
+            self._launch(self.lib.mu_motif_write, total, n_seq, nt, codes, room, offsets, B, tl, ml, th, og, counts, base,
+                         n_hits, seq, mot, pos, score)
         return seq, mot, pos, score
 
     def mofa_jaakkola(self, zeta, a, b):
         """Bernoulli pseudo-data precision 2 lambda(xi), xi^2 = zeta^2 + a - b, written over ``a``."""
         assert zeta.is_contiguous() and a.is_contiguous() and b.is_contiguous() and a.shape == zeta.shape == b.shape
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_jaakkola(_dt(zeta), int(zeta.numel()), _p(zeta), _p(a), _p(b), _p(a), self._stream()))
+        self._launch(self.lib.mu_mofa_jaakkola, _dt(zeta), int(zeta.numel()), zeta, a, b, a)
         return a
 
     def mofa_poisson_pseudo(self, zeta, Y, kappa, mode: int):
         """Poisson pseudo-data (mode 0) / likelihood terms (mode 1) of a dense chunk, in place of zeta."""
         n, D = zeta.shape
         assert zeta.is_contiguous() and Y.is_contiguous() and Y.shape == zeta.shape and Y.dtype == zeta.dtype
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_poisson_pseudo(_dt(zeta), int(n), int(D), int(mode), _p(zeta), _p(Y), _p(kappa),
-                                                  _p(zeta), self._stream()))
+        self._launch(self.lib.mu_mofa_poisson_pseudo, _dt(zeta), int(n), int(D), int(mode), zeta, Y, kappa, zeta)
         return zeta
 
     mofa_poisson_lik_with_b = True  # (mode 3 of mofa_poisson_pass)
@@ -2111,38 +2022,16 @@ class HipBackend(OperatorSet):
         n_other = E_other.shape[0]
         assert E_other.shape[1] == K and E_own.dtype == E_other.dtype and 1 <= K <= 32
         assert X.shape == (n_own, n_other) and X.values.dtype == E_own.dtype
-        # rows padded with zeros to ld columns (include/muon_amd.h): the padded width 4 / 8 / 12 / 16 / 32, and 16 for
-        # 9 <= K <= 12 too - 64-byte rows let the stored-entry pass read a row in one cache-line look-up (r06)
-        ld = 16 if 8 < K <= 16 else next(k for k in (4, 8, 32) if k >= K)
-
-        def pad(E, slot):
-            if K == ld and E.is_contiguous():
-                return E
-            # `pads` (a dict the caller owns, e.g. the engine of a fit): a padded buffer per (role, shape) whose columns
-            # K .. ld - 1 are zeroed once - a pass copies the K columns in, one kernel instead of a fill and a copy.
-            # Calls are ordered on one stream and a pass has consumed its operands when the next one overwrites them;
-            # the buffers live as long as the caller (a captured iteration keeps pointing at them).
-            if pads is None:
-                P = torch.zeros((E.shape[0], ld), dtype=E.dtype, device=E.device)
-            else:
-                key = (slot, int(E.shape[0]), ld, K, E.dtype)
-                P = pads.get(key)
-                if P is None:
-                    P = pads[key] = torch.zeros((E.shape[0], ld), dtype=E.dtype, device=E.device)
-            P[:, :K].copy_(E)
-            return P
-
-        E_own, E_other = pad(E_own, "own"), pad(E_other, "other")
+        ld = _mofa_pad_width(K)
+        E_own, E_other = _mofa_pad(E_own, "own", K, ld, pads), _mofa_pad(E_other, "other", K, ld, pads)
         blk = int(self.lib.mu_mofa_poisson_blocks_for(_dt(E_own), int(mode), K, n_own, n_other))
         nb = -(-n_other // blk)
         part = self.empty((nb, n_own) if mode == 2 else (nb, n_own, K + 1 if mode == 3 else K), E_own.dtype)
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_poisson_dense_ld(_dt(E_own), int(mode), n_own, n_other, K, ld, blk, _p(E_own),
-                                                    _p(E_other), _p(kappa), _p(part), self._stream()))
-            out = part[0] if nb == 1 else part.sum(dim=0)  # (fixed order: deterministic)
-            out = out.contiguous()
-            check(self.lib.mu_mofa_poisson_sparse_ld(_dt(E_own), int(mode), n_own, K, ld, _p(X.indptr), _p(X.indices),
-                                                     _p(X.values), _p(E_own), _p(E_other), _p(out), self._stream()))
+        self._launch(self.lib.mu_mofa_poisson_dense_ld, _dt(E_own), int(mode), n_own, n_other, K, ld, blk, E_own, E_other,
+                     kappa, part)
+        out = _sum_parts(part).contiguous()
+        self._launch(self.lib.mu_mofa_poisson_sparse_ld, _dt(E_own), int(mode), n_own, K, ld, X.indptr, X.indices, X.values,
+                     E_own, E_other, out)
         return out
 
     def mofa_softplus_sweep(self, E_own, E_other, pads: Optional[dict] = None):
@@ -2151,28 +2040,13 @@ class HipBackend(OperatorSet):
         n_own, K = E_own.shape
         n_other = E_other.shape[0]
         assert E_other.shape[1] == K and E_own.dtype == E_other.dtype and 1 <= K <= 32
-        ld = 16 if 8 < K <= 16 else next(k for k in (4, 8, 32) if k >= K)
-
-        def pad(E, slot):
-            if K == ld and E.is_contiguous():
-                return E
-            key = (slot, int(E.shape[0]), ld, K, E.dtype)
-            P = pads.get(key) if pads is not None else None
-            if P is None:
-                P = torch.zeros((E.shape[0], ld), dtype=E.dtype, device=E.device)
-                if pads is not None:
-                    pads[key] = P
-            P[:, :K].copy_(E)
-            return P
-
-        E_own, E_other = pad(E_own, "own"), pad(E_other, "other")
+        ld = _mofa_pad_width(K)
+        E_own, E_other = _mofa_pad(E_own, "own", K, ld, pads), _mofa_pad(E_other, "other", K, ld, pads)
         blk = int(self.lib.mu_mofa_poisson_blocks_for(_dt(E_own), 2, K, n_own, n_other))
         nb = -(-n_other // blk)
         part = self.empty((nb, n_own), E_own.dtype)
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_poisson_dense_ld(_dt(E_own), 2, n_own, n_other, K, ld, blk, _p(E_own), _p(E_other),
-                                                    None, _p(part), self._stream()))
-            return part[0] if nb == 1 else part.sum(dim=0)
+        self._launch(self.lib.mu_mofa_poisson_dense_ld, _dt(E_own), 2, n_own, n_other, K, ld, blk, E_own, E_other, None, part)
+        return _sum_parts(part)
 
     def mofa_jaakkola_sweep(self, E_own, E2_own, E_other, E2_other):
         """The precision-weighted moment sums of a bernoulli view without anything N x D (csrc/mofa_bernoulli.hip,
@@ -2188,31 +2062,28 @@ class HipBackend(OperatorSet):
         blk = int(self.lib.mu_mofa_jaakkola_blocks(_dt(E_own), K, n_own, n_other))
         nb = -(-n_other // blk)
         part = self.empty((nb, n_own, pc), E_own.dtype)
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_pack_moments(_dt(E_own), n_other, K, ldm, _p(args[2]), _p(args[3]), _p(M), self._stream()))
-            check(self.lib.mu_mofa_jaakkola_sweep(_dt(E_own), n_own, n_other, K, blk, _p(args[0]), _p(args[1]), _p(args[2]),
-                                                  _p(args[3]), _p(M), ldm, _p(part), self._stream()))
-            packed = part[0] if nb == 1 else part.sum(dim=0)  # (fixed order: deterministic)
-            idx = self._tri_index.get((K, packed.device))
-            if idx is None:
-                pos = {}
-                for k in range(K):
-                    for l in range(k, K):
-                        pos[(k, l)] = len(pos)
-                idx = torch.tensor([pos[(min(k, l), max(k, l))] for k in range(K) for l in range(K)], dtype=torch.int64,
-                                   device=packed.device)
-                self._tri_index[(K, packed.device)] = idx
-            return packed.index_select(1, idx).view(n_own, K, K)
+        self._launch(self.lib.mu_mofa_pack_moments, _dt(E_own), n_other, K, ldm, args[2], args[3], M)
+        self._launch(self.lib.mu_mofa_jaakkola_sweep, _dt(E_own), n_own, n_other, K, blk, args[0], args[1], args[2], args[3],
+                     M, ldm, part)
+        packed = _sum_parts(part)
+        idx = self._tri_index.get((K, packed.device))
+        if idx is None:
+            pos = {}
+            for k in range(K):
+                for l in range(k, K):
+                    pos[(k, l)] = len(pos)
+            idx = torch.tensor([pos[(min(k, l), max(k, l))] for k in range(K) for l in range(K)], dtype=torch.int64,
+                               device=packed.device)
+            self._tri_index[(K, packed.device)] = idx
+        return packed.index_select(1, idx).view(n_own, K, K)
 
     def mofa_gs_update(self, Tm, b, prior, lth, l1mth, spikeslab, E, E2, gamma, Eh2, sig2):
         """Gauss-Seidel sweep over the factors of every row with row-wise K x K statistics (include/muon_amd.h);
         prior / lth / l1mth: f64 [K]."""
         n, K = E.shape
         assert Tm.is_contiguous() and b.is_contiguous() and E.is_contiguous() and E2.is_contiguous() and sig2.is_contiguous()
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_gs_update(_dt(E), int(n), int(K), _p(Tm), _p(b), _p(prior), _p(lth), _p(l1mth),
-                                             int(bool(spikeslab)), _p(E), _p(E2), _p(gamma), _p(Eh2), _p(sig2),
-                                             self._stream()))
+        self._launch(self.lib.mu_mofa_gs_update, _dt(E), int(n), int(K), Tm, b, prior, lth, l1mth, int(bool(spikeslab)), E, E2,
+                     gamma, Eh2, sig2)
 
     def mofa_elbo_work(self, K: int) -> torch.Tensor:
         return self.empty((int(self.lib.mu_mofa_elbo_work_doubles(int(K))),), torch.float64)
@@ -2221,10 +2092,8 @@ class HipBackend(OperatorSet):
         """tau / <ln tau> of one view from the sufficient statistics; adds the likelihood and tau-node
         terms to the f64 device scalar ``elbo`` (include/muon_amd.h)."""
         G, D, K = B.shape
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_tau_elbo(_dt(EW), D, K, G, _p(yy), _p(Ngm), _p(EW), _p(EW2), _p(B), _p(Gz),
-                                            _p(Z2), float(a0), float(b0), _p(tau), _p(ltau), _p(elbo),
-                                            _p(work), self._stream()))
+        self._launch(self.lib.mu_mofa_tau_elbo, _dt(EW), D, K, G, yy, Ngm, EW, EW2, B, Gz, Z2, float(a0), float(b0), tau, ltau,
+                     elbo, work)
 
     def mofa_stats_resid(self, yy, EW, EW2, B, Q, S):
         """S[d] = yy[d] - 2 <w_d> . B[d] + sum Q[d] * <w w^T>_d in f64 (include/muon_amd.h): yy, S f64 [D]; EW, EW2, B [D, K];
@@ -2233,55 +2102,41 @@ class HipBackend(OperatorSet):
         assert yy.dtype == torch.float64 and S.dtype == torch.float64 and yy.is_contiguous() and S.is_contiguous()
         assert EW.is_contiguous() and EW2.is_contiguous() and B.is_contiguous() and Q.is_contiguous()
         assert B.shape == (D, K) and Q.shape[1] == K * K and Q.shape[0] in (1, D) and B.dtype == EW.dtype == Q.dtype
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_stats_resid(_dt(EW), int(D), int(K), int(Q.shape[0]), _p(yy), _p(EW), _p(EW2), _p(B),
-                                               _p(Q), _p(S), self._stream()))
+        self._launch(self.lib.mu_mofa_stats_resid, _dt(EW), int(D), int(K), int(Q.shape[0]), yy, EW, EW2, B, Q, S)
 
     def mofa_tau_finish(self, S, Ngd, a0, b0, tau, ltau, elbo, work):
         """tau / <ln tau> from the expected squared residuals and counts of every (group, feature) (f64, same shape as
         tau); adds the likelihood and tau-node terms to the f64 device scalar ``elbo`` (include/muon_amd.h)."""
         assert S.dtype == torch.float64 and Ngd.dtype == torch.float64 and S.is_contiguous() and Ngd.is_contiguous()
         assert tau.is_contiguous() and ltau.is_contiguous() and tau.numel() == S.numel() == Ngd.numel() == ltau.numel()
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_tau_finish(_dt(tau), int(S.numel()), _p(S), _p(Ngd), float(a0), float(b0), _p(tau),
-                                              _p(ltau), _p(elbo), _p(work), self._stream()))
+        self._launch(self.lib.mu_mofa_tau_finish, _dt(tau), int(S.numel()), S, Ngd, float(a0), float(b0), tau, ltau, elbo, work)
 
     def mofa_w_elbo(self, EWh2, gamma, sig2, ard, spikeslab, a_alpha, a0, b0, th_a0, th_b0, alpha, lalpha,
                     lth, l1mth, elbo, work):
         D, K = EWh2.shape
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_w_elbo(_dt(EWh2), D, K, int(bool(ard)), int(bool(spikeslab)), _p(EWh2),
-                                          _p(gamma), _p(sig2), float(a_alpha), float(a0), float(b0),
-                                          float(th_a0), float(th_b0), _p(alpha), _p(lalpha), _p(lth),
-                                          _p(l1mth), _p(elbo), _p(work), self._stream()))
+        self._launch(self.lib.mu_mofa_w_elbo, _dt(EWh2), D, K, int(bool(ard)), int(bool(spikeslab)), EWh2, gamma, sig2,
+                     float(a_alpha), float(a0), float(b0), float(th_a0), float(th_b0), alpha, lalpha, lth, l1mth, elbo, work)
 
     def mofa_z_sums(self, EZ2, sig2, n0, n1, out, work):
         K = EZ2.shape[1]
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_z_sums(_dt(EZ2), int(n0), int(n1), K, _p(EZ2), _p(sig2), _p(out), _p(work),
-                                          self._stream()))
+        self._launch(self.lib.mu_mofa_z_sums, _dt(EZ2), int(n0), int(n1), K, EZ2, sig2, out, work)
 
     def mofa_z_elbo(self, zs, Ng, ard, a0, b0, alpha_z, lalpha_z, elbo):
         G, _two, K = zs.shape
-        with self._dev_ctx():
-            check(self.lib.mu_mofa_z_elbo(_dt(alpha_z), K, G, int(bool(ard)), _p(zs), _p(Ng), float(a0),
-                                          float(b0), _p(alpha_z), _p(lalpha_z), _p(elbo), self._stream()))
+        self._launch(self.lib.mu_mofa_z_elbo, _dt(alpha_z), K, G, int(bool(ard)), zs, Ng, float(a0), float(b0), alpha_z,
+                     lalpha_z, elbo)
 
     # -- synthetic data (bench / tests) ---------------------------------------------
     def synth_counts(self, row0: int, n_rows: int, n_cols: int, n_topics: int = 50,
                      density: float = 0.03, seed: int = 0) -> DeviceCSR:
         row_nnz = self.empty((n_rows,), torch.int64)
         indptr = self.empty((n_rows + 1,), torch.int64)
-        with self._dev_ctx():
-            st = self._stream()
-            check(self.lib.mu_synth_row_nnz(row0, n_rows, n_cols, n_topics, density, seed,
-                                            _p(row_nnz), st))
-            check(self.lib.mu_exclusive_scan_i64(n_rows, _p(row_nnz), _p(indptr), st))
-            nnz = int(indptr[-1].item())
-            indices = self.empty((nnz,), torch.int32)
-            values = self.empty((nnz,), torch.float32)
-            check(self.lib.mu_synth_fill(row0, n_rows, n_cols, n_topics, density, seed, _p(indptr),
-                                         _p(indices), _p(values), st))
+        self._launch(self.lib.mu_synth_row_nnz, row0, n_rows, n_cols, n_topics, density, seed, row_nnz)
+        self._launch(self.lib.mu_exclusive_scan_i64, n_rows, row_nnz, indptr)
+        nnz = int(indptr[-1].item())
+        indices = self.empty((nnz,), torch.int32)
+        values = self.empty((nnz,), torch.float32)
+        self._launch(self.lib.mu_synth_fill, row0, n_rows, n_cols, n_topics, density, seed, indptr, indices, values)
         # (the generator stands where ingest stands: the slab pointers of its index arrays are made here, once)
         return self.with_slab_ptr(DeviceCSR(indptr, indices, values, (n_rows, n_cols)))
 
