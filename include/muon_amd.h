@@ -963,6 +963,29 @@ int mu_gp_project_f64(int64_t n, const double* d_V, int64_t ldv, const double* d
 int mu_gp_posterior_f64(int64_t n, const double* d_V, int64_t ldv, const double* d_g, const double* d_u, double* d_m,
                         double* d_dc, void* stream);
 
+/* ---- muon_amd.rna.pp.scale: clipped z-scores of a device CSR as a sparse matrix plus one row (scanpy's scale;
+ * csrc/scale.hip, C-ABI v814) ------------------------------------------------------------------------------
+ * Row-major CSR: d_indptr int64 [n + 1], d_indices int32 [nnz], values f32 / f64 [nnz].  d_mean, d_std, d_z: f64 [d];
+ * lo <= hi are the clip range (-inf / +inf for a side that is not clipped).  One statement, all f64, no contraction:
+ * t = (x - d_mean[c]) / d_std[c];  t < lo -> lo, t > hi -> hi by comparisons (a NaN stays NaN, as with np.clip); one
+ * rounding to the storage type.
+ *   mu_scale_values: d_out[p] = T(t - d_z[c]) for every stored entry p (the kernel needs no d_indptr: an entry's result
+ *     depends on its value and its column alone).  d_out may be d_in.  A column outside [0, d) gives NaN.  With d_mean =
+ *     d_z = 0 and lo = -inf it is the scaling without centring; with d_z = clip((0 - mean) / std) it is S = C - 1 z^T.
+ *   mu_scale_dense_rows: rows [row_lo, row_hi) of the dense C into the row-major block d_out [(row_hi - row_lo) x d]:
+ *     T(d_z[j]) where nothing is stored, T(t) - computed from x, rounded once - where an entry is stored (a stored
+ *     zero gives the value of an implicit one when d_z = clip((0 - mean) / std)).  A wave per row, walked
+ *     grid-stride; fill and stored values meet in the wave's own LDS tile, in that order, and a whole segment of the
+ *     row is written out once, coalesced.  Rows are sorted by column (an unsorted row loses the entries behind a
+ *     larger column).  d_indptr is clamped to [0, nnz] and a column outside [0, d) is skipped.
+ * No atomics, every output element is written once: two calls agree byte for byte.  Arguments are checked before any
+ * HIP call. */
+int mu_scale_values(int dtype, int64_t nnz, int64_t d, const int32_t* d_indices, const void* d_in, void* d_out,
+                    const double* d_mean, const double* d_std, const double* d_z, double lo, double hi, void* stream);
+int mu_scale_dense_rows(int dtype, int64_t n, int64_t d, int64_t nnz, int64_t row_lo, int64_t row_hi,
+                        const int64_t* d_indptr, const int32_t* d_indices, const void* d_values, const double* d_mean,
+                        const double* d_std, const double* d_z, double lo, double hi, void* d_out, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

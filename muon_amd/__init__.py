@@ -26,6 +26,8 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.rna.pp.normalize_total / log1p / highly_variable_genes, muon_amd.tl.pca  <->  scanpy's, the steps with which
                              the reference's tutorials open every RNA modality: the matrix stays the device CSR, PCA is
                              lsi's block Lanczos process on the implicitly centred (and scaled) operator
+    muon_amd.rna.pp.scale    <->  scanpy's scale: the clipped z-scores are a sparse matrix plus one row; the dense X is
+                             written once by a fused pass, and tl.pca decomposes it through the sparse form, no upload
 
     muon_amd.tl.leiden / muon_amd.tl.louvain  <->  muon.tl.leiden / muon.tl.louvain  (multiplex clustering over the
                              modalities' graphs: a wave per vertex groups its neighbours' communities in an LDS table)

@@ -1721,6 +1721,45 @@ class HipBackend(OperatorSet):
         self._launch(self.lib.mu_scale_rows_f32, int(d), int(B), s, Q, out)
         return out
 
+    # -- muon_amd.rna.pp.scale (csrc/scale.hip) ------------------------------------------------------------------------
+    @staticmethod
+    def _scale_tables(X: DeviceCSR, mean, std, z):
+        d = int(X.shape[1])
+        for t in (mean, std, z):
+            assert t.dtype == torch.float64 and tuple(t.shape) == (d,) and t.is_contiguous()
+        assert X.indices.dtype == torch.int32 and X.indices.is_contiguous() and X.values.is_contiguous()
+        assert int(X.indices.numel()) == int(X.values.numel())
+        return d
+
+    def scale_values(self, X: DeviceCSR, mean, std, z, lo: float, hi: float, out=None) -> torch.Tensor:
+        """``T(clip((x - mean[c]) / std[c], lo, hi) - z[c])`` for every stored value of ``X``: f64 arithmetic, the clip
+        by comparisons, one rounding to the storage type (include/muon_amd.h).  ``mean``, ``std``, ``z``: f64 [d].
+        ``out`` may be ``X.values`` itself; returns the values tensor written."""
+        d = self._scale_tables(X, mean, std, z)
+        v = X.values
+        if out is None:
+            out = torch.empty_like(v)
+        assert out.dtype == v.dtype and out.shape == v.shape and out.is_contiguous()
+        self._launch(self.lib.mu_scale_values, _dt(v), int(v.numel()), d, X.indices, v, out, mean, std, z, float(lo),
+                     float(hi))
+        return out
+
+    def scale_dense_rows(self, X: DeviceCSR, mean, std, z, lo: float, hi: float, row_lo: int, row_hi: int,
+                         out=None) -> torch.Tensor:
+        """Rows [row_lo, row_hi) of the dense clipped scaled matrix as a ``[row_hi - row_lo, d]`` block of the storage
+        type: ``T(z[j])`` where nothing is stored, ``T(clip((x - mean[j]) / std[j], lo, hi))`` where an entry is
+        (include/muon_amd.h).  ``out``: a contiguous block of that shape to write into."""
+        d = self._scale_tables(X, mean, std, z)
+        n, row_lo, row_hi = int(X.shape[0]), int(row_lo), int(row_hi)
+        assert X.indptr.dtype == torch.int64 and int(X.indptr.numel()) == n + 1 and X.indptr.is_contiguous()
+        assert 0 <= row_lo <= row_hi <= n
+        if out is None:
+            out = self.empty((row_hi - row_lo, d), X.values.dtype)
+        assert out.dtype == X.values.dtype and tuple(out.shape) == (row_hi - row_lo, d) and out.is_contiguous()
+        self._launch(self.lib.mu_scale_dense_rows, _dt(X.values), n, d, int(X.values.numel()), row_lo, row_hi, X.indptr,
+                     X.indices, X.values, mean, std, z, float(lo), float(hi), out)
+        return out
+
     # -- muon.tl.snf (csrc/snf.hip) ----------------------------------------------------------------------------------
     def free_memory(self) -> int:
         """Bytes the device can still hand out: what the driver reports free plus what torch's allocator holds unused."""

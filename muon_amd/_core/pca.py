@@ -142,7 +142,9 @@ def pca(adata, n_comps: Optional[int] = None, *, zero_center: bool = True, scale
             scikit-learn's ``TruncatedSVD``.
     scale
             Divide every gene by its standard deviation (ddof = 1; 0 -> 1) after centring: ``sc.pp.scale`` WITHOUT
-            ``max_value`` - clipping cannot be applied implicitly, and the scaled matrix is never formed.
+            ``max_value``, and the scaled matrix is never formed.  With ``max_value`` use ``rna.pp.scale`` first: the
+            clipped scaled matrix is a sparse matrix plus one row, and the dense ``X`` it writes from a device CSR is
+            decomposed here through that sparse form, without an upload.
     svd_solver
             ``None``, ``"arpack"`` or ``"auto"``: all run the block Lanczos process; others raise
             ``NotImplementedError``.
@@ -180,6 +182,14 @@ def pca(adata, n_comps: Optional[int] = None, *, zero_center: bool = True, scale
         from .._rna.preproc import _float_csr, device_copy
 
         counts, X, be = device_copy(_float_csr(counts), backend)
+    elif zero_center:
+        # a dense matrix that rna.pp.scale wrote from a device CSR is S + 1 z^T with S still on the device: centring
+        # removes the rank-one term, so its PCA is the centred process on S
+        from .._rna.preproc import scaled_form
+
+        form = scaled_form(counts, backend)
+        if form is not None:
+            X, _z, be = form
     if X is not None:
         if mask is not None:
             from .preproc import submatrix_device

@@ -70,6 +70,8 @@ class OperatorSet:
     nmf_max_components = nmf_cd_sweep = None
     # muon_amd.rna.pp and muon_amd.tl.pca (rna.hip)
     gene_moments_max_blocks = gene_moments = value_sweep = shift_cols = scale_rows = None
+    # muon_amd.rna.pp.scale (scale.hip)
+    scale_values = scale_dense_rows = None
     # muon.atac.tl.scan_sequences (motif.hip): behind motif_scan
     motif_max_len = motif_tile = motif_group = motif_room = motif_scan = None
     # synthetic counts of the benchmark and the tests (synth.hip)

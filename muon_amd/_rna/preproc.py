@@ -1,4 +1,5 @@
-"""``muon_amd.rna.pp``: scanpy's ``normalize_total``, ``log1p`` and ``highly_variable_genes`` on the device CSR.
+"""``muon_amd.rna.pp``: scanpy's ``normalize_total``, ``log1p``, ``highly_variable_genes`` and ``scale`` on the device
+CSR.
 
 The reference opens every RNA modality with these steps (/root/reference/docs/source/omics/*.rst) and hands them to
 scanpy; signatures and slots here follow scanpy's.  Parity with scanpy itself is NOT pinned (it is not installed where
@@ -26,9 +27,13 @@ Statements (f64 arithmetic, one rounding to the storage type; integer matrices b
                     the non-NaN dispersions, a bin with fewer than two of them gets std = its mean and mean = 0;
                     dispersions_norm = (dispersions - bin mean) / bin std.  The device computes the per-gene sums, the
                     binning runs on d-vectors on the host.
+  scale             stated above ``scale`` at the end of this module: clipped z-scores as a sparse matrix plus one row
+                    (csrc/scale.hip: ``scale_values``, ``scale_dense_rows``).
 """
 from __future__ import annotations
 
+import logging
+import weakref
 from typing import Optional
 from warnings import warn
 
@@ -40,6 +45,7 @@ from scipy.sparse import csr_matrix, issparse
 from .._containers import is_anndata, is_mudata
 from .._operators import has
 
+logger = logging.getLogger("muon_amd")
 
 def _modality(data):
     if is_anndata(data):
@@ -328,3 +334,176 @@ def highly_variable_genes(data, *, n_top_genes: Optional[int] = None, min_mean: 
 
         filter_var(adata, np.asarray(hv, dtype=bool), backend=backend)
     return None
+
+
+# ---- scale ------------------------------------------------------------------------------------------------------------
+# Statement (f64 arithmetic, one rounding to the storage type).  Per gene j: mean_j and var_j (ddof = 1) from the sums of
+# x and x^2 over all n cells (``_core.pca._moments``), std_j = sqrt(var_j) with 0 -> 1.  The clip range is [-max_value,
+# max_value] with ``zero_center``, (-inf, max_value] without (scanpy >= 1.10), the infinities without ``max_value``:
+#     C_ij = clip((x_ij - mean_j) / std_j, lo, hi)              (zero_center=False: mean_j = 0 in this formula)
+# Every implicit zero of gene j therefore maps to z_j = clip((0 - mean_j) / std_j, lo, hi), and C = S + 1 z^T with
+# S_ij = C_ij - z_j on the stored entries of X and nothing anywhere else.
+_DENSE_CHUNK_BYTES = 512 << 20  # the dense result leaves the device in row chunks of at most this size
+
+
+def _clip_np(t, lo, hi):
+    """np.clip's result by comparisons (NaN fails both and stays)."""
+    t = np.where(t < lo, lo, t)
+    return np.where(t > hi, hi, t)
+
+
+def _clip_t(t, lo, hi):
+    t = torch.where(t < lo, torch.full_like(t, lo), t)
+    return torch.where(t > hi, torch.full_like(t, hi), t)
+
+
+def scale_tables(sx, sxx, n, zero_center=True, max_value=None):
+    """``(mean, std, centre, z, lo, hi)`` of the statement above from the per-gene sums of x and x^2: ``mean`` and
+    ``std`` are what ``var`` receives, ``centre`` is what is subtracted (``mean``, or zeros without ``zero_center``)."""
+    from .._core.pca import _moments
+
+    mean, var = _moments(np.asarray(sx, dtype=np.float64), np.asarray(sxx, dtype=np.float64), n, True)
+    std = np.sqrt(var)
+    std[std == 0] = 1.0
+    hi = np.inf if max_value is None else float(max_value)
+    lo = -hi if zero_center else -np.inf
+    centre = mean if zero_center else np.zeros_like(mean)
+    z = _clip_np((0.0 - centre) / std, lo, hi)
+    return mean, std, centre, z, lo, hi
+
+
+def scale_values_tensor(X, mean, std, z, lo, hi):
+    """``scale_values`` (include/muon_amd.h) as tensor operations, for operator sets without the kernel."""
+    c = X.indices.long()
+    t = _clip_t((X.values.to(torch.float64) - mean[c]) / std[c], lo, hi)
+    return (t - z[c]).to(X.values.dtype)
+
+
+def scale_dense_rows_tensor(X, mean, std, z, lo, hi, row_lo, row_hi):
+    """``scale_dense_rows`` (include/muon_amd.h) as tensor operations, for operator sets without the kernel."""
+    T, d = X.values.dtype, X.shape[1]
+    out = z.to(T).repeat(row_hi - row_lo, 1)
+    a, b = int(X.indptr[row_lo]), int(X.indptr[row_hi])
+    ln = X.indptr[row_lo + 1:row_hi + 1] - X.indptr[row_lo:row_hi]
+    row = torch.repeat_interleave(torch.arange(row_hi - row_lo, device=ln.device), ln)
+    c = X.indices[a:b].long()
+    out[row, c] = _clip_t((X.values[a:b].to(torch.float64) - mean[c]) / std[c], lo, hi).to(T)
+    return out.reshape(row_hi - row_lo, d)
+
+
+# The device form of a dense result.  A plain ndarray takes no attributes, so the forms live in a registry keyed by the
+# array's id, each with a weak reference whose callback drops the entry (and with it the device arrays) when the array
+# dies: an id is only ever looked up while its array is alive.  Validity is ``resident()``'s rule: the same backend and
+# a fingerprint over every byte of the array.
+_FORMS = {}
+
+
+def _dense_fingerprint(a):
+    from .._atac.preproc import _hash_arrays
+
+    return (a.shape, a.dtype.str, a.flags.c_contiguous) + _hash_arrays([a])
+
+
+def remember_scaled_form(a, S, z, backend):
+    """Remember ``(S, z)`` - ``a == S + 1 z^T`` rounded once - as the device form of the dense ndarray ``a``."""
+    key = id(a)
+    _FORMS[key] = (weakref.ref(a, lambda _r, key=key: _FORMS.pop(key, None)), S, z, backend, _dense_fingerprint(a))
+
+
+def scaled_form(a, backend=None):
+    """``(S, z, backend)`` remembered for the dense ndarray ``a`` if it still describes ``a``, else None.  Without a
+    ``backend`` the form's own serves.  A form whose array was edited in place is dropped."""
+    ent = _FORMS.get(id(a)) if type(a) is np.ndarray else None
+    if ent is None or ent[0]() is not a or (backend is not None and ent[3] is not backend):
+        return None
+    if ent[4] != _dense_fingerprint(a):
+        _FORMS.pop(id(a), None)
+        return None
+    return ent[1], ent[2], ent[3]
+
+
+def _scale_dense_host(m, centre, std, lo, hi):
+    """The dense statement on the host, for a dense or a sparse matrix, in row chunks of f64."""
+    n, d = m.shape
+    out = np.empty((n, d), dtype=m.dtype)
+    rows = max(1, _DENSE_CHUNK_BYTES // max(1, 8 * d))
+    for r0 in range(0, n, rows):
+        blk = m[r0:r0 + rows]
+        blk = blk.toarray() if issparse(blk) else np.asarray(blk)
+        out[r0:r0 + rows] = _clip_np((blk.astype(np.float64) - centre) / std, lo, hi).astype(m.dtype)
+    return out
+
+
+def scale(data, zero_center: bool = True, max_value: Optional[float] = None, copy: bool = False, *,
+          layer: Optional[str] = None, obsm: Optional[str] = None, mask_obs=None, comm=None, backend=None):
+    """
+    Scale every gene to unit variance and, with ``zero_center``, zero mean (scanpy's signature).
+
+    Mean and standard deviation (ddof = 1; 0 -> 1) are per gene over all cells and go to ``var["mean"]`` and
+    ``var["std"]``.  ``max_value`` clips the result: to ``[-max_value, max_value]`` with ``zero_center``, from above
+    only without it (scanpy >= 1.10's rule).  An integer matrix becomes float32 (scanpy makes it the default float
+    type).  ``obsm`` and ``mask_obs`` raise ``NotImplementedError``.  ``copy=True`` works on a copy and returns it.
+
+    ``zero_center=True`` on a sparse matrix gives a C-ordered dense ndarray of the storage type, as scanpy does.  On a
+    device route the dense matrix is written by one fused pass in row chunks that are copied to the host one by one -
+    it never exists on the device - and the sparse form ``S`` with ``result == S + 1 z^T`` stays on the device, so that
+    a following ``tl.pca`` starts without an upload.  ``zero_center=False`` keeps a sparse matrix sparse (and its
+    device copy).  See the module docstring for where it runs; a dense matrix takes the host route.
+    """
+    if obsm is not None:
+        raise NotImplementedError("scale: obsm= is not implemented")
+    if mask_obs is not None:
+        raise NotImplementedError("scale: mask_obs= is not implemented")
+    _one_rank(comm, "rna.pp.scale")
+    adata = _modality(data)
+    if copy:
+        adata = adata.copy()
+    counts = _get(adata, layer)
+    n = int(counts.shape[0])
+    X = be = None
+    if issparse(counts):
+        m, X, be = device_copy(_float_csr(counts), backend)
+    else:
+        m = np.asarray(counts)
+        if m.dtype not in (np.float32, np.float64):
+            m = m.astype(np.float32)
+    if X is not None:
+        sums, _nnz = gene_moments_device(be, X, with_e=False)
+        sx, sxx = sums[0], sums[1]
+    elif issparse(m):
+        m64 = m.astype(np.float64)
+        sx, sxx = np.asarray(m64.sum(axis=0)).reshape(-1), np.asarray(m64.multiply(m64).sum(axis=0)).reshape(-1)
+    else:
+        m64 = m.astype(np.float64)
+        sx, sxx = m64.sum(axis=0), (m64 * m64).sum(axis=0)
+    mean, std, centre, z, lo, hi = scale_tables(sx, sxx, n, zero_center, max_value)
+
+    if issparse(m) and zero_center:
+        logger.info("scale: zero-centering a sparse matrix densifies it")
+    if X is not None:
+        tabs = [be.to_device(t, np.float64) for t in (centre, std, z)]
+        values = be.scale_values if has(be, "scale_values") else scale_values_tensor
+        if zero_center:
+            d = int(X.shape[1])
+            new = np.empty((n, d), dtype=m.dtype)
+            rows = max(1, _DENSE_CHUNK_BYTES // max(1, d * new.dtype.itemsize))
+            buf = be.empty((min(rows, n), d), X.values.dtype) if n else None
+            for r0 in range(0, n, rows):
+                r1 = min(n, r0 + rows)
+                if has(be, "scale_dense_rows"):
+                    blk = be.scale_dense_rows(X, *tabs, lo, hi, r0, r1, out=buf[:r1 - r0])
+                else:
+                    blk = scale_dense_rows_tensor(X, *tabs, lo, hi, r0, r1)
+                be.to_host(blk.reshape(-1), out=new[r0:r1].reshape(-1))
+            remember_scaled_form(new, X.with_values(values(X, *tabs, lo, hi)), z, be)
+        else:
+            new = _with_values(m, X, be, values(X, *tabs, lo, hi))
+    elif issparse(m) and not zero_center:
+        v = _clip_np(m.data.astype(np.float64) / std[m.indices], lo, hi)
+        new = _with_values(m, None, None, v.astype(m.dtype))
+    else:
+        new = _scale_dense_host(m, centre, std, lo, hi)
+    _put(adata, layer, new)
+    adata.var["mean"] = mean
+    adata.var["std"] = std
+    return adata if copy else None
