@@ -24,7 +24,10 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .._containers import AnnData, is_anndata, is_mudata
+from .._backend import backend_or_default
+from .._containers import AnnData, is_mudata, modality
+from .._core.io import device_csr_from_keys
+from .._hostmatrix import host_view
 from .._operators import has
 
 _NO_FRAGMENTS = "There is no fragments file located yet. Run muon.atac.tl.locate_fragments first."
@@ -69,22 +72,6 @@ class FragmentTable:
 # -----------------------------------------------------------------------------------------------------------------
 # building the table
 # -----------------------------------------------------------------------------------------------------------------
-def _atac(data):
-    if is_anndata(data):
-        return data
-    if is_mudata(data) and "atac" in data.mod:
-        return data.mod["atac"]
-    raise TypeError("Expected AnnData or MuData object with 'atac' modality")
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
-    return backend
-
-
 def _int32(a, what):
     a = np.asarray(a)
     if a.size and (a.min() < 0 or a.max() > _I32_MAX):
@@ -93,7 +80,7 @@ def _int32(a, what):
 
 
 def make_table(chrom, start, end, barcode, score=None, *, sort=False, backend=None) -> FragmentTable:
-    backend = _backend(backend)
+    backend = backend_or_default(backend)
     chrom, barcode = np.asarray(chrom), np.asarray(barcode)
     start, end = _int32(start, "starts"), _int32(end, "ends")
     n = start.shape[0]
@@ -132,7 +119,7 @@ def fragments_from_arrays(data, chrom, start, end, barcode, score=None, *, sort=
     ``.uns["files"]["fragments"]``, where the reference keeps the path (tools.py:679).  ``score=None``: all ones.
     Rows must be grouped by contig and non-decreasing in ``start`` inside a contig, else ``ValueError``;
     ``sort=True`` sorts them stably first."""
-    adata = _atac(data)
+    adata = modality(data, "atac")
     table = make_table(chrom, start, end, barcode, score, sort=sort, backend=backend)
     _store(adata, table)
     return table
@@ -151,7 +138,7 @@ def locate_fragments(data, fragments, return_fragments: bool = False, *, sort=Fa
     """``muon.atac.tl.locate_fragments`` (tools.py:640): ``fragments`` is a ``FragmentTable`` or the path of a plain or
     gzip fragments TSV of five columns (four: score 1), which is READ here - no tabix index and no pysam are needed.
     The table goes to ``.uns["files"]["fragments"]``."""
-    adata = _atac(data)
+    adata = modality(data, "atac")
     table = fragments if isinstance(fragments, FragmentTable) else read_fragments(fragments, sort=sort, backend=backend)
     _store(adata, table)
     if return_fragments:
@@ -306,12 +293,7 @@ def _windows(table, chrom_names, lo, hi):
 # -----------------------------------------------------------------------------------------------------------------
 def get_gene_annotation_from_rna(data) -> pd.DataFrame:
     """/root/reference/muon/_rna/utils.py:7-37: Chromosome / Start / End from the ``interval`` column of the 'rna' .var."""
-    if is_anndata(data):
-        adata = data
-    elif is_mudata(data) and "rna" in data.mod:
-        adata = data.mod["rna"]
-    else:
-        raise TypeError("Expected AnnData or MuData object with 'rna' modality")
+    adata = modality(data, "rna")
     if "interval" not in adata.var.columns:
         raise ValueError(".var object does not have a column named interval")
     features = pd.DataFrame([s.replace(":", "-", 1).split("-") for s in adata.var.interval])
@@ -344,7 +326,7 @@ def count_fragments_features(data, features: Optional[pd.DataFrame] = None, stra
     when ``stranded``: a "-" feature is then extended upstream behind its end.  ``count_reads=True`` sums the fragments'
     scores (and warns, like the reference, that the default will change), ``False`` counts fragments.  A feature on a
     contig the table lacks counts nothing."""
-    adata = _atac(data)
+    adata = modality(data, "atac")
     features = _default_features(data, features)
     table = _table_of(adata)
     be = _table_backend(table, backend)
@@ -371,10 +353,6 @@ def count_fragments_features(data, features: Optional[pd.DataFrame] = None, stra
     hi = np.where(minus, f_end + extend_upstream, f_end + extend_downstream)
 
     logging.info(f"Counting fragments in {n} cells for {n_features} features...")
-    from .._core.io import device_csr_from_keys
-    from .preproc import attach_device
-    from scipy.sparse import csr_matrix
-
     wchrom, wlo, whi = _windows(table, column(chrom_col), np.floor(lo), np.ceil(hi))
     cell_of = be.to_device(cell_table(adata, table), np.int32)
     rng_lo, rng_len = window_ranges(table, wchrom, wlo, whi)
@@ -383,11 +361,7 @@ def count_fragments_features(data, features: Optional[pd.DataFrame] = None, stra
     X.values = X.values.to(getattr(torch, np.dtype(values_dtype).name))
     if has(be, "with_slab_ptr"):
         X = be.with_slab_ptr(X)
-    host = csr_matrix((be.to_host(X.values), be.to_host(X.indices), be.to_host(X.indptr)), shape=X.shape)
-    host.has_sorted_indices = True
-    host.has_canonical_format = True
-    attach_device(host, X, be)
-    return AnnData(host, obs=adata.obs, var=features)
+    return AnnData(host_view(X, be, canonical=True), obs=adata.obs, var=features)
 
 
 def _check_tss_score(region_size: int, flank_size: int = 100, center_size: int = 1001) -> int:
@@ -422,7 +396,7 @@ def tss_enrichment(data, features: Optional[pd.DataFrame] = None, extend_upstrea
     """TSS enrichment according to ENCODE guidelines (``muon.atac.tl.tss_enrichment``, tools.py:894-1106): adds
     ``tss_score`` to ``.obs`` and, with ``return_tss``, returns the AnnData of the flank-normalised pileup (cells x
     positions, f64) - without it the pileup never leaves the device.  ``features`` needs Chromosome and Start columns."""
-    adata = _atac(data)
+    adata = modality(data, "atac")
     features = _default_features(data, features)
     if features.shape[0] > n_tss:
         # Only use n_tss randomly chosen sites to make function faster
@@ -460,7 +434,7 @@ def nucleosome_signal(data, n=None, nucleosome_free_upper_bound: int = 147, mono
     """Ratio of mono-nucleosomal to nucleosome-free fragments per cell (``muon.atac.tl.nucleosome_signal``,
     tools.py:1109-1201) over the first ``n`` fragments of the table (None: 1e4 * number of cells); fragments of unknown
     barcodes use up their turn.  Adds ``nucleosome_signal`` to ``.obs``."""
-    adata = _atac(data)
+    adata = modality(data, "atac")
     table = _table_of(adata)
     be = _table_backend(table, backend)
     n = int(adata.n_obs * 1e4) if n is None else int(n)

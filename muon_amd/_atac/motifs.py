@@ -38,7 +38,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .._containers import is_anndata, is_mudata
+from .._backend import backend_or_default
+from .._containers import modality
 from .._operators import has
 
 COLUMNS = ["sequence", "motif_id", "position", "score"]
@@ -47,14 +48,6 @@ TENSOR_CHUNK = 1 << 22  # stream positions the tensor formulation scores at a ti
 _CODE = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _CODE[ord(_c)] = _CODE[ord(_c.lower())] = _i
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
 
 
 def _background(background):
@@ -240,7 +233,7 @@ def prepare_motif_scanner(matrices=None, background=4, pvalue: float = 1e-4, max
     if matrices is None:
         matrices = parse_motif_matrices(files=None, background=background, jaspar_dir=jaspar_dir)["matrices"]
     thresholds = [scan_threshold(m, background, pvalue) for m in matrices]
-    return MotifScanner(_backend(backend), matrices, thresholds, use_kernel=use_kernel, max_hits=max_hits)
+    return MotifScanner(backend_or_default(backend), matrices, thresholds, use_kernel=use_kernel, max_hits=max_hits)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -449,12 +442,7 @@ def get_sequences(data, bed: Optional[str] = None, fasta_file: Optional[str] = N
     in the order of the intervals, with ``bedtools getfasta`` semantics: start 0-based, end exclusive.  The genome is
     ``fasta_file`` (recorded in ``.uns['files']['genome']``) or the one recorded there before.
     """
-    if is_anndata(data):
-        adata = data
-    elif is_mudata(data) and "atac" in data.mod:
-        adata = data.mod["atac"]
-    else:
-        raise TypeError("Expected AnnData or MuData object with 'atac' modality")
+    adata = modality(data, "atac")
 
     if "files" not in adata.uns or "genome" not in adata.uns["files"]:
         if fasta_file is None:

@@ -25,28 +25,14 @@ import numpy as np
 import torch
 from scipy.sparse import issparse
 
-from .._containers import is_anndata, is_mudata
+from .._backend import DeviceCSR, backend_or_default
+from .._containers import modality
+from .._hostmatrix import device_copy
 from .._operators import OperatorSet, has
 
 METHODS = ("t-test", "t-test_overestim_var", "wilcoxon", "logreg")
 SORT_BUDGET_BYTES = 1 << 30  # device memory the per-row sort of X^T may hold at a time
 _SORT_BYTES_PER_ENTRY = 64   # keys, two permutations and their gathers, 8 B each
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
-
-
-def _atac(data):
-    if is_anndata(data):
-        return data
-    if is_mudata(data) and "atac" in data.mod:
-        return data.mod["atac"]
-    raise TypeError("Expected AnnData or MuData object with 'atac' modality")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -114,8 +100,6 @@ def sort_rows_by_value(Xt, budget_bytes: int = SORT_BUDGET_BYTES):
     """X^T with every row's entries sorted ascending by value (cells permuted alike; equal values keep their order):
     two stable sorts, by value and then by row, over blocks of rows that fit ``budget_bytes`` (the row ids of a block
     are made for that block and count against the budget; nothing of the size of the matrix is held but the result)."""
-    from .._backend import DeviceCSR
-
     d = Xt.shape[0]
     indptr = Xt.indptr.cpu().numpy()
     values, cells = torch.empty_like(Xt.values), torch.empty_like(Xt.indices)
@@ -138,8 +122,6 @@ def sort_rows_by_value(Xt, budget_bytes: int = SORT_BUDGET_BYTES):
 
 def _dense_transposed(backend, arr):
     """X^T of a dense matrix as a CSR of its non-zero entries (the tensor path's operand)."""
-    from .._backend import DeviceCSR
-
     t = backend.to_device(np.ascontiguousarray(np.asarray(arr).T))
     if t.dtype not in (torch.float32, torch.float64):
         t = t.to(torch.float64)
@@ -161,17 +143,9 @@ def _transposed(adata, layer, backend):
     """``(X^T as a device CSR, operator set)``; a sparse matrix leaves its device copy attached."""
     counts = adata.X if layer is None else adata.layers[layer]
     if not issparse(counts):
-        backend = _backend(backend)
+        backend = backend_or_default(backend)  # raises without a GPU: there is no CPU path in the package
         return _dense_transposed(backend, counts), _NoKernels(backend)
-    from .._core.preproc import _resident_copy
-    from .preproc import attach_device, upload_canonical
-
-    X, backend = _resident_copy(counts, backend)
-    if X is None:
-        backend = _backend(backend)
-        host, X = upload_canonical(backend, counts)
-        if host is counts:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
-            attach_device(counts, X, backend)
+    _host, X, backend = device_copy(counts, backend)
     if X.values.dtype == torch.float32 and has(backend, "transpose_csr"):
         return backend.transpose_csr(X), backend
     return backend.transpose(X), backend
@@ -224,7 +198,7 @@ def rank_genes_groups(adata, groupby: str, *, groups="all", reference: str = "re
 
     from .._comm import default_comm
 
-    adata = _atac(adata)
+    adata = modality(adata, "atac")
     if method is None:
         method = "t-test"
     if method not in METHODS:
@@ -379,7 +353,7 @@ def add_peak_annotation(data, annotation, sep: str = "\t", return_annotation: bo
     """
     import pandas as pd
 
-    adata = _atac(data)
+    adata = modality(data, "atac")
     table = annotation if isinstance(annotation, pd.DataFrame) else pd.read_csv(annotation, sep=sep)
     table = table.convert_dtypes()
     if "peak" in table.columns:
@@ -417,7 +391,7 @@ def add_genes_peaks_groups(data, add_peak_type: bool = False, add_distance: bool
     """
     import pandas as pd
 
-    adata = _atac(data)
+    adata = modality(data, "atac")
     if key not in adata.uns:
         raise KeyError(f"There is no .uns['{key}'] yet. Run rank_genes_groups first.")
     if "atac" not in adata.uns or "peak_annotation" not in adata.uns["atac"]:
@@ -460,7 +434,7 @@ def rank_peaks_groups(data, groupby: str, add_peak_type: bool = False, add_dista
     ``uns['atac']['peak_annotation']`` exists.  Without an annotation the reference raises ``KeyError`` after the
     ranking; here the ranking alone is the result.
     """
-    adata = _atac(data)
+    adata = modality(data, "atac")
     rank_genes_groups(adata, groupby, backend=backend, **kwargs)
     if "peak_annotation" in adata.uns.get("atac", {}):
         add_genes_peaks_groups(adata, add_peak_type=add_peak_type, add_distance=add_distance,

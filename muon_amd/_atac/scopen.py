@@ -46,9 +46,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .._containers import is_anndata, is_mudata
+from .._backend import backend_or_default
+from .._containers import modality
+from .._hostmatrix import canonical_csr, resident
 from .._operators import has
-from .preproc import canonical_csr, resident
 
 logger = logging.getLogger("muon_amd")
 
@@ -285,12 +286,7 @@ def scopen(data, n_components: int = 30, max_iter: int = 500, min_rho: float = 0
     the unscaled ``alpha`` of scikit-learn <= 0.24 - parity with the ``scopen`` package itself is not pinned.  See the
     module docstring.
     """
-    if is_anndata(data):
-        adata = data
-    elif is_mudata(data) and "atac" in data.mod:
-        adata = data.mod["atac"]
-    else:
-        raise TypeError("Expected AnnData or MuData object with 'atac' modality")
+    adata = modality(data, "atac")
 
     k = n_components
     if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 1:
@@ -309,11 +305,7 @@ def scopen(data, n_components: int = 30, max_iter: int = 500, min_rho: float = 0
     if isinstance(init, str) and init not in ("nndsvd", "random"):
         raise ValueError(f"init must be 'nndsvd', 'random' or a pair (W0, H0), got {init!r}")
 
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    be = backend
+    be = backend_or_default(backend)  # raises without a GPU: there is no CPU path in the package
     import torch.distributed as dist
 
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:

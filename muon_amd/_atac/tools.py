@@ -28,11 +28,12 @@ import numpy as np
 import torch
 import scipy.linalg
 
+from .._backend import DeviceCSR, backend_or_default
 from .._comm import default_comm
-from .._containers import is_anndata, is_mudata
+from .._containers import modality
+from .._hostmatrix import resident, upload_canonical
 from .._operators import has
 from .._trace import phase
-from .preproc import canonical_csr, resident, upload_canonical  # noqa: F401
 from .fragments import (FragmentTable, count_fragments_features, fragments_from_arrays,  # noqa: F401
                         locate_fragments, nucleosome_signal, tss_enrichment)
 from .rank import (add_genes_peaks_groups, add_peak_annotation, rank_genes_groups,  # noqa: F401
@@ -245,8 +246,6 @@ def _refine_f64(backend, comm, X, Xt, V0, k, n_obs, scale_embeddings, angle_goal
     k = 26, 0.16 % gap: 5 blocks, < 7e-9 / 8e-7 - the bound is a guarantee and ~100 x the truth.
     Returns U [rows, k], s [k], V [d, k] (torch f64; U scaled like the f32 tail does) and a dict for ``info``.
     Rows are sharded like X: Y = X Q is local, Z = X^T Y all-reduced, everything d x w replicated."""
-    from .._backend import DeviceCSR
-
     f64 = torch.float64
     world = getattr(comm, "world_size", 1)
 
@@ -1074,21 +1073,13 @@ def lsi(data, scale_embeddings=True, n_comps=50, *, comm=None, n_iter: Optional[
     Keyword-only extras (not in the reference): ``comm`` for row-sharded input, ``n_iter`` /
     ``tol`` / ``oversample`` / ``seed`` of the block Lanczos iteration (``lsi_device``).
     """
-    if is_anndata(data):
-        adata = data
-    elif is_mudata(data) and "atac" in data.mod:
-        adata = data.mod["atac"]
-    else:
-        raise TypeError("Expected AnnData or MuData object with 'atac' modality")
+    adata = modality(data, "atac")
 
     # In an unlikely scnenario when there are less 50 features, set n_comps to that value
     n_comps = min(n_comps, adata.X.shape[1])
 
     logger.info("Performing SVD")
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
+    backend = backend_or_default(backend)
     comm = default_comm(comm)
 
     X = adata.X

@@ -2211,3 +2211,8 @@ def get_backend():
     if _default_backend is None or _default_backend.device.index != torch.cuda.current_device():
         _default_backend = HipBackend()
     return _default_backend
+
+
+def backend_or_default(backend):
+    """``backend`` if one was passed, else the process-wide one (raises without a GPU: there is no CPU path)."""
+    return get_backend() if backend is None else backend

@@ -292,6 +292,15 @@ def is_mudata(obj) -> bool:
     return _RealMuData is not None and isinstance(obj, _RealMuData)
 
 
+def modality(data, name: str):
+    """The AnnData an operator works on: ``data`` itself, or modality ``name`` of a MuData."""
+    if is_anndata(data):
+        return data
+    if is_mudata(data) and name in data.mod:
+        return data.mod[name]
+    raise TypeError(f"Expected AnnData or MuData object with '{name}' modality")
+
+
 def view_to_actual(adata) -> None:
     """scanpy._utils.view_to_actual equivalent (reference preproc.py:84)."""
     if getattr(adata, "is_view", False):

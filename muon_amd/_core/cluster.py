@@ -71,20 +71,13 @@ import pandas as pd
 import torch
 from scipy.sparse import csr_matrix
 
+from .._backend import backend_or_default
 from .._containers import is_anndata, is_mudata
 from .._operators import has
 
 _KERNEL_METHODS = ("cluster_move", "cluster_segsum", "cluster_max_table", "cluster_max_layers")
 MAX_SWEEPS = 50
 N_CLASSES = 4
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
 
 
 class _TableOverflow(Exception):
@@ -491,7 +484,7 @@ def _cluster(data, resolution, mod_weights, random_state, key_added, neighbors_k
     if any(l[3] != n for l in layers):
         raise ValueError("every modality's graph must have one row per observation")
 
-    be = _backend(backend)
+    be = backend_or_default(backend)
     g0 = _build_graph(be, layers, lambdas, gammas, bool(directed))
     rng = np.random.default_rng(random_state)
     groups, q_final, q_single = optimise(be, g0, algorithm, rng, int(n_iterations), diagnostics)

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 from scipy import linalg
 
+from .._backend import backend_or_default
 from .._operators import has
 
 _FUNS = ("logcosh", "exp", "cube")
@@ -45,14 +46,6 @@ _FUNS = ("logcosh", "exp", "cube")
 class ConvergenceWarning(UserWarning):
     """FastICA reached ``max_iter`` (scikit-learn's warning of the same name; defined here because scikit-learn need
     not be installed where the package runs)."""
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
 
 
 def _check_random_state(seed):
@@ -152,7 +145,7 @@ def _fastica_arrays(X, n_components=None, *, random_state=None, algorithm="paral
     ``diagnostics``: a dict that receives ``n_iter``, ``components_``, ``mean_``, ``whitening_``, the last ``lim`` and
     the whole ``lim_history`` (host values)."""
     _validate(n_components, algorithm, whiten, fun, fun_args, max_iter, tol, whiten_solver)
-    be = _backend(backend)
+    be = backend_or_default(backend)
     fun_args = {} if fun_args is None else fun_args
     rs = _check_random_state(random_state)
     alpha = fun_args.get("alpha", 1.0)
@@ -283,7 +276,7 @@ def ica(data, basis="X_pca", n_components=None, *, random_state=None, scale=Fals
     rank-deficient basis this differs from scikit-learn's SVD (and warns).  See the module docstring for where each
     statement runs.
     """
-    be = _backend(backend)
+    be = backend_or_default(backend)
     X = data.obsm[basis]
     if isinstance(X, torch.Tensor):
         dt = np.dtype(np.float32) if X.dtype == torch.float32 else np.dtype(np.float64)

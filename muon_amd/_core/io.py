@@ -19,7 +19,7 @@ device CSR of this rank's cells directly:
 
 ``read_10x_arrays`` wraps the single-process case in an AnnData whose ``X`` shares the caller's arrays
 when no column is dropped and carries the device copy, so ``tfidf`` / ``lsi`` start without another
-PCIe upload (the residency mechanism of _atac/preproc.py).
+PCIe upload (the residency mechanism of _hostmatrix.py).
 """
 from __future__ import annotations
 
@@ -28,7 +28,9 @@ from typing import Mapping, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .._backend import DeviceCSR, backend_or_default
 from .._comm import default_comm
+from .._hostmatrix import host_view
 from .._operators import has
 
 
@@ -52,10 +54,7 @@ def device_csr_from_10x(matrix: Mapping, comm=None, backend=None, atac_only: boo
     as array-likes supporting slicing (numpy arrays, h5py datasets); ``feature_types`` (or
     ``matrix["features"]["feature_type"]``) selects the "Peaks" columns when ``atac_only``.
     Returns ``(DeviceCSR, kept_feature_indices or None, (r0, r1))``."""
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
+    backend = backend_or_default(backend)
     shape = np.asarray(_get(matrix, "shape")).astype(np.int64)
     n_feat, n_cells = int(shape[0]), int(shape[1])
     r0, r1 = shard_rows(n_cells, comm)
@@ -90,8 +89,6 @@ def select_columns(backend, X, mask: np.ndarray):
     """Keep the columns where ``mask`` is True (renumbered), on the device: dropped entries get a zero
     value and fall out in the compaction kernel (which drops exactly-zero entries, as scipy's SpGEMM
     does in the reference's tfidf), the survivors' columns go through a lookup table."""
-    from .._backend import DeviceCSR
-
     mask = np.asarray(mask, dtype=bool)
     newcol = np.cumsum(mask, dtype=np.int64) - 1
     newcol[~mask] = -1
@@ -123,8 +120,6 @@ def canonicalize(backend, X):
 
 
 def _sort_rows(backend, X):
-    from .._backend import DeviceCSR
-
     n, d = X.shape
     rows = torch.repeat_interleave(torch.arange(n, device=X.indices.device), X.indptr[1:] - X.indptr[:-1])
     key = rows * int(d) + X.indices.long()
@@ -156,10 +151,7 @@ def device_csr_from_coo(rows, cols, vals, shape, backend=None, values_dtype=np.f
     """Coordinate triplets (Matrix Market bodies, snap count tables: _atac/io.py:125) -> device CSR of
     ``shape`` = (n_rows, n_cols): one key sort on the device, duplicates summed.  Host arrays are uploaded; device
     tensors (the fragment counts of _atac/fragments.py) are taken where they are."""
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
+    backend = backend_or_default(backend)
     d = int(shape[1])
 
     def dev(a, dtype):
@@ -173,8 +165,6 @@ def device_csr_from_coo(rows, cols, vals, shape, backend=None, values_dtype=np.f
 
 def device_csr_from_keys(key, v, shape, sum_duplicates=True):
     """Device tensors ``key`` = row * n_cols + column (int64) and values ``v`` -> device CSR of ``shape``."""
-    from .._backend import DeviceCSR
-
     n, d = int(shape[0]), int(shape[1])
     key, order = torch.sort(key, stable=True)
     v = v[order]
@@ -193,10 +183,7 @@ def device_csr_from_keys(key, v, shape, sum_duplicates=True):
 def device_csr_from_csc(indptr, indices, data, shape, backend=None, values_dtype=np.float32):
     """Column-compressed cells x features (``indptr`` over the features) -> device CSR, transposed on
     the device (no host ``tocsr()``)."""
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
+    backend = backend_or_default(backend)
     n, d = int(shape[0]), int(shape[1])
     Xt = backend.upload_csr(indptr, indices, data, (d, n), values_dtype=values_dtype)  # CSR of X^T
     if Xt.values.dtype == torch.float32 and has(backend, "transpose_csr"):
@@ -210,28 +197,18 @@ def read_10x_arrays(matrix: Mapping, atac_only: bool = True, feature_types=None,
     already opened by the caller): AnnData (cells x features, f32 CSR like sc.read_10x_h5 yields) whose
     ``X`` carries its device copy, so that ``pp.tfidf`` / ``tl.lsi`` start without a PCIe upload."""
     import pandas as pd
-    from scipy.sparse import csr_matrix
 
-    from .._atac.preproc import attach_device
     from .._containers import AnnData
 
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
+    backend = backend_or_default(backend)
     X, keep, _ = device_csr_from_10x(matrix, None, backend, atac_only, feature_types)
-    shape = np.asarray(_get(matrix, "shape")).astype(np.int64)
+    own = {}
     if keep is None and np.asarray(matrix["data"]).dtype == np.float32 and X.canonical_as_given:
-        # the caller's arrays ARE the canonical CSR: the host view shares them (ADVICE r03: the flags below used to be
-        # set on this branch also when only the device copy had been sorted)
-        host = csr_matrix((np.asarray(matrix["data"]), np.asarray(matrix["indices"]),
-                           np.asarray(matrix["indptr"])), shape=(int(shape[1]), int(shape[0])))
-    else:  # columns dropped / values converted / rows sorted on the device: the host view is the device result
-        host = csr_matrix((backend.to_host(X.values), backend.to_host(X.indices), backend.to_host(X.indptr)),
-                          shape=X.shape)
-    host.has_sorted_indices = True
-    host.has_canonical_format = True
-    attach_device(host, X, backend)
+        # the caller's arrays ARE the canonical CSR: the host view shares them (ADVICE r03: the canonical flags used to
+        # be set on this branch also when only the device copy had been sorted).  Otherwise - columns dropped / values
+        # converted / rows sorted on the device - the host view is the device result
+        own = {k: np.asarray(matrix[k]) for k in ("data", "indices", "indptr")}
+    host = host_view(X, backend, canonical=True, **own)
     obs = pd.DataFrame(index=pd.Index([b.decode() if isinstance(b, bytes) else str(b) for b in barcodes])) \
         if barcodes is not None else None
     var = None

@@ -26,6 +26,7 @@ import torch
 from scipy.sparse import issparse
 
 from .._containers import is_anndata
+from .._hostmatrix import device_copy
 
 logger = logging.getLogger("muon_amd")
 
@@ -179,9 +180,9 @@ def pca(adata, n_comps: Optional[int] = None, *, zero_center: bool = True, scale
 
     X = be = None
     if issparse(counts):
-        from .._rna.preproc import _float_csr, device_copy
+        from .._rna.preproc import _float_csr
 
-        counts, X, be = device_copy(_float_csr(counts), backend)
+        counts, X, be = device_copy(_float_csr(counts), backend, host_route=True)
     elif zero_center:
         # a dense matrix that rna.pp.scale wrote from a device CSR is S + 1 z^T with S still on the device: centring
         # removes the rank-one term, so its PCA is the centred process on S

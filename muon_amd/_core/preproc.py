@@ -28,18 +28,13 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix, issparse
 
-from .._containers import is_anndata, is_mudata
+from .._backend import DeviceCSR, backend_or_default
+from .._comm import default_comm
+from .._containers import is_anndata, is_mudata, modality
+from .._hostmatrix import attach_device, device_copy, resident_copy
 from .._operators import has
 
 _METRICS = ("euclidean", "sqeuclidean", "cosine", "cityblock", "manhattan", "chebyshev")
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()
-    return backend
 
 
 def _choose_representation(adata, use_rep=None, n_pcs=None):
@@ -458,7 +453,7 @@ def knn(adata, n_neighbors: int = 15, use_rep: Optional[str] = None, n_pcs: Opti
     """Exact k-nearest-neighbour graph of one modality in scanpy's slots (``.obsp["distances"]`` with
     n_neighbors - 1 entries per row, ``.obsp["connectivities"]``, ``.uns["neighbors"]``): the input
     ``neighbors`` expects per modality (reference :366-373 "Run `sc.pp.neighbors` on all modalities first")."""
-    be = _backend(backend)
+    be = backend_or_default(backend)
     X = _choose_representation(adata, use_rep, n_pcs)
     X = X.toarray() if issparse(X) else np.asarray(X)
     Xd = be.to_device(np.ascontiguousarray(X, dtype=np.float64))
@@ -595,7 +590,7 @@ def neighbors(mdata, n_neighbors: Optional[int] = None, n_bandwidth_neighbors: i
     if metric not in _PAIR_METRICS + ("seuclidean", "mahalanobis"):
         # (at entry, not after the bandwidth and weight work - ADVICE r04; the message names what is offered)
         _pair_dist(torch.zeros((1, 1)), torch.zeros((1, 1)), metric)
-    be = _backend(backend)
+    be = backend_or_default(backend)
     mdata = mdata.copy() if copy else mdata
     if neighbor_keys is None:
         modalities = list(mdata.mod.keys())
@@ -779,27 +774,13 @@ def neighbors(mdata, n_neighbors: Optional[int] = None, n_bandwidth_neighbors: i
 # muon.pp.filter_obs / filter_var (reference _core/preproc.py:675-881) and the QC columns they key on
 # ---------------------------------------------------------------------------------------------------------------------
 # The step every ATAC workflow takes between reading and tfidf.  A host matrix that carries a device copy
-# (_atac.preproc.attach_device: the ingest, binarize, tfidf leave one) is subset on the host with scipy AND on the
+# (_hostmatrix.attach_device: the ingest, binarize, tfidf leave one) is subset on the host with scipy AND on the
 # device with csrc/filter.hip, and the new device copy goes with the new host matrix - the matrix does not cross PCIe
 # a second time.  A matrix without a device copy is subset on the host alone: filtering never starts using the GPU.
 
 
-def _resident_copy(m, backend):
-    """(DeviceCSR, backend) of the valid device copy attached to host matrix ``m``, else (None, backend).  Without a
-    ``backend`` argument the copy's own backend serves: no backend is constructed for a host-only matrix."""
-    from .._atac.preproc import DEVICE_ATTR, resident
-
-    ent = getattr(m, DEVICE_ATTR, None) if issparse(m) else None
-    if ent is None:
-        return None, backend
-    be = ent[1] if backend is None else backend
-    return resident(m, be), be
-
-
 def _submatrix_tensor(X, rows, table, n_cols):
     """``csr_submatrix`` as tensor operations, for operator sets without the kernel: the same three arrays."""
-    from .._backend import DeviceCSR
-
     k = int(rows.numel())
     dev = X.indptr.device
     lo = X.indptr[rows]
@@ -841,11 +822,9 @@ def _subset_matrix(m, attr, subset, backend):
     """``m[subset, :]`` (obs) or ``m[:, subset]`` (var); a CSR with a valid device copy keeps one."""
     if m is None:
         return None
-    X, be = _resident_copy(m, backend)
+    X, be = resident_copy(m, backend)  # (never device_copy: filtering does not upload)
     new = m[subset, :] if attr == "obs" else m[:, subset]
     if X is not None:
-        from .._atac.preproc import attach_device
-
         Y = submatrix_device(be, X, subset, None) if attr == "obs" else submatrix_device(be, X, None, subset)
         new.has_sorted_indices = True  # (a resident copy is canonical, and slicing keeps the stored order)
         attach_device(new, Y, be)
@@ -950,8 +929,6 @@ def filter_var(data, var, func=None, *, backend=None) -> None:
 def qc_device(backend, X, comm=None):
     """``(row_nnz, rowsum, col_nnz, colsum)`` of (this rank's row shard of) device CSR ``X`` as host arrays, the
     per-column pair summed over the ranks in ONE packed all-reduce (counts travel as f64: exact below 2^53)."""
-    from .._comm import default_comm
-
     comm = default_comm(comm)
     if has(backend, "csr_qc"):
         row_nnz, rowsum, col_nnz, colsum = backend.csr_qc(X)
@@ -988,28 +965,14 @@ def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p
     """
     import pandas as pd
 
-    from .._comm import default_comm
-
-    if is_anndata(data):
-        adata = data
-    elif is_mudata(data) and "atac" in data.mod:
-        adata = data.mod["atac"]
-    else:
-        raise TypeError("Expected AnnData or MuData object with 'atac' modality")
+    adata = modality(data, "atac")
     comm = default_comm(comm)
     counts = adata.X if layer is None else adata.layers[layer]
     if issparse(counts):
-        from .._atac.preproc import attach_device, upload_canonical
-
-        X, backend = _resident_copy(counts, backend)
-        if X is None:
-            backend = _backend(backend)
-            host, X = upload_canonical(backend, counts)
-            if host is counts:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
-                attach_device(counts, X, backend)
+        _host, X, backend = device_copy(counts, backend)
         row_nnz, rowsum, col_nnz, colsum = qc_device(backend, X, comm)
     else:
-        backend = _backend(backend)
+        backend = backend_or_default(backend)
         t = backend.to_device(np.asarray(counts)).to(torch.float64)
         nz = (t != 0).to(torch.float64)
         cnt, colsum = nz.sum(dim=0), t.sum(dim=0)

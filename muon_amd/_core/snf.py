@@ -38,18 +38,11 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix, issparse
 
+from .._backend import backend_or_default
 from .._operators import has
 
 _SQRT_2PI = float(np.sqrt(2 * np.pi))
 _KERNEL_METHODS = ("snf_affinity", "snf_normalize", "snf_topk", "snf_p_scale", "snf_diffuse")
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
 
 
 # ---- the tensor formulation: the reference's statements as torch operations ----------------------------------------------
@@ -232,7 +225,7 @@ def snf(mdata, n_neighbors: int = 20, neighbor_keys: Optional[Union[str, Dict[st
     (the reference divides by M - 1 = 0) raises ``ValueError``; a modality that a ``neighbor_keys`` dict leaves out is
     fused through its ``.uns["neighbors"]`` (the reference ends in a ``KeyError`` there).
     """
-    be = _backend(backend)
+    be = backend_or_default(backend)
     from .preproc import _choose_representation
 
     mdata = mdata.copy() if copy else mdata

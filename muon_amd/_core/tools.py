@@ -32,6 +32,7 @@ import pandas as pd
 import torch
 from scipy.sparse import csr_matrix, issparse
 
+from .._backend import backend_or_default
 from .._containers import MuData, is_anndata, is_mudata
 from .ica import ConvergenceWarning, ica  # noqa: F401  (mu.tl.ica: FastICA of an embedding on the device)
 from .pca import pca  # noqa: F401  (scanpy's pca on the device CSR: block Lanczos on the implicitly centred operator)
@@ -352,10 +353,7 @@ def mofa(
         mdata, groups_label, use_raw, use_layer, lik, use_var, use_obs
     )
 
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: no CPU fallback
+    backend = backend_or_default(backend)  # raises without a GPU: no CPU fallback
 
     logger.info("Building the model...")
     kw = dict(dtype=torch.float32 if use_float32 else torch.float64,

@@ -78,9 +78,10 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix
 
+from .._backend import backend_or_default
 from .._containers import is_anndata, is_mudata
 from .._operators import has
-from .cluster import _backend, _ptr_of_counts, _segsum
+from .cluster import _ptr_of_counts, _segsum
 
 _KERNEL_METHODS = ("umap_epoch", "umap_max_components")
 SHIFT = 16  # the schedule's fixed point: E = rint(period 2^16)
@@ -362,7 +363,7 @@ def umap(mdata, min_dist: float = 0.5, spread: float = 1.0, n_components: int = 
     if not (a > 0 and b > 0):
         raise ValueError("a and b must be positive")
 
-    be = _backend(backend)
+    be = backend_or_default(backend)
     g = _Graph(be, n, *edges(conn, n_epochs))
     seed = (int(np.random.default_rng().integers(0, 1 << 63)) if random_state is None else int(random_state)) & _M64
     Y0 = initial_positions(be, g, init_pos, int(n_components), random_state, mdata.obsm)

@@ -30,7 +30,7 @@ import pandas as pd
 import torch
 from scipy.sparse import issparse
 
-from .._backend import DeviceCSR
+from .._backend import DeviceCSR, backend_or_default
 from .._containers import is_anndata, is_mudata
 from .._operators import has
 
@@ -40,14 +40,6 @@ _MAX_ITER = 100
 _NK_EPS = 10 * np.finfo(np.float64).eps
 _LOG_2PI = float(np.log(2 * np.pi))
 _LN2 = float(np.log(2.0))
-
-
-def _backend(backend):
-    if backend is None:
-        from .._backend import get_backend
-
-        backend = get_backend()  # raises without a GPU: there is no CPU path in the package
-    return backend
 
 
 # ---- host matrix -> device ------------------------------------------------------------------------------------------
@@ -227,7 +219,7 @@ def _dsb_arrays(cells_X, empty_X, *, pseudocount=10, denoise_counts=True, ctrl_i
     ``force_tensor``: the tensor formulation even where the kernels apply (what tests compare the kernels with).
     ``diagnostics``: a dict that receives mean / std of the empty droplets and, with denoising, the background means,
     BICs and iteration counts (host arrays)."""
-    be = _backend(backend)
+    be = backend_or_default(backend)
     pc = float(pseudocount)
     Xc, Xe = _to_device(be, cells_X), _to_device(be, empty_X)
     n, d = (int(s) for s in Xc.shape)
@@ -340,7 +332,7 @@ def dsb(
         if data.mod["rna"].n_obs != data.mod["prot"].n_obs:
             raise ValueError("different numbers of cells in 'rna' and 'prot' modalities.")
 
-        be = _backend(backend)
+        be = backend_or_default(backend)
         log10umi = np.log10(_row_sums(data.mod["rna"].X, be) + 1)
         empty_idx = np.where(
             (log10umi >= min(*empty_counts_range)) & (log10umi < max(*empty_counts_range))
@@ -402,7 +394,7 @@ def dsb(
                 empty = empty[~empty.obs_names.isin(cells.obs_names)]
             else:
                 # data_raw is a MuData with 'rna' modality and empty_counts_range values are provided
-                be = _backend(backend)
+                be = backend_or_default(backend)
                 log10umi = np.log10(_row_sums(data_raw.mod["rna"].X, be) + 1)
                 names = data_raw.mod["rna"].obs_names
                 empty_droplets = names[
@@ -427,7 +419,7 @@ def dsb(
         if len(ctrl_idx) < len(isotype_controls):
             warn("Some isotype controls are not present in the data.")
 
-    be = _backend(backend) if be is None else be
+    be = backend_or_default(backend) if be is None else be
     z = _dsb_arrays(cells.X, empty.X, pseudocount=pseudocount, denoise_counts=denoise_counts, ctrl_idx=ctrl_idx,
                     scale_factor=scale_factor, quantile_clipping=quantile_clipping, quantile_clip=quantile_clip,
                     random_state=random_state, backend=be)
@@ -477,7 +469,7 @@ def clr(adata, inplace: bool = True, axis: int = 0, flavor: str = "seurat", *, b
 
     if flavor not in ("seurat", "stoeckius", "standard"):
         raise ValueError(f"Unknown flavor `{flavor}`.")
-    be = _backend(backend)
+    be = backend_or_default(backend)
     odt = _out_dtype(x)
     n_along = x.shape[axis]
     if flavor == "seurat" and issparse(x):

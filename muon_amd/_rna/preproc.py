@@ -8,7 +8,7 @@ this package is tested): every function is stated below and pinned by an indepen
 
 Where each step runs:
 
-  * a matrix that carries a device copy (``_atac.preproc.attach_device``), or any sparse matrix when ``backend=`` is
+  * a matrix that carries a device copy (``_hostmatrix.attach_device``), or any sparse matrix when ``backend=`` is
     given: on that backend.  The matrix is uploaded at most once; the result keeps the device copy attached, so
     ``normalize_total -> log1p -> highly_variable_genes -> tl.pca`` cross PCIe for results only.  The value sweep and the
     per-gene moments are kernels of csrc/rna.hip (``value_sweep``, ``gene_moments``); an operator set without them (the
@@ -42,18 +42,11 @@ import pandas as pd
 import torch
 from scipy.sparse import csr_matrix, issparse
 
-from .._containers import is_anndata, is_mudata
+from .._containers import modality
+from .._hostmatrix import _hash_arrays, device_copy, host_view
 from .._operators import has
 
 logger = logging.getLogger("muon_amd")
-
-def _modality(data):
-    if is_anndata(data):
-        return data
-    if is_mudata(data) and "rna" in data.mod:
-        return data.mod["rna"]
-    raise TypeError("Expected AnnData or MuData object with 'rna' modality")
-
 
 def _one_rank(comm, what):
     if comm is not None and getattr(comm, "world_size", 1) > 1:
@@ -61,33 +54,14 @@ def _one_rank(comm, what):
 
 
 def _float_csr(m):
-    """A sparse matrix as float CSR (integers -> float32; a float CSR comes back as it is)."""
+    """A sparse matrix as float CSR (integers -> float32; a float CSR comes back as it is).  ``device_copy`` then gives
+    the CANONICAL host matrix every result is built on: scipy's products and slices hand out unsorted rows, a stored
+    value is only a matrix entry once duplicates are summed, and ``log1p`` / ``expm1`` are not linear."""
     if m.format != "csr":
         m = m.tocsr()
     if m.dtype not in (np.float32, np.float64):
         m = m.astype(np.float32)
     return m
-
-
-def device_copy(m, backend):
-    """``(host, DeviceCSR, backend)`` for float CSR ``m``.  ``host`` is the CANONICAL host matrix every result is built
-    on - sorted column indices, duplicates summed: ``m`` itself when it is canonical, else a copy (scipy's products and
-    slices hand out unsorted rows; a stored value is only a matrix entry once duplicates are summed, and ``log1p`` /
-    ``expm1`` are not linear).  The device CSR is ``m``'s valid device copy (a resident copy is canonical); else, with a
-    ``backend``, an upload of ``host`` that stays attached to ``m`` when ``host`` is ``m``; else ``(host, None, None)`` -
-    the host route.  The device CSR always has ``host``'s index arrays."""
-    from .._atac.preproc import attach_device, canonical_csr, upload_canonical
-    from .._core.preproc import _resident_copy
-
-    X, be = _resident_copy(m, backend)
-    if X is not None:
-        return m, X, be
-    if backend is None:
-        return canonical_csr(m), None, None
-    host, X = upload_canonical(backend, m)
-    if host is m:  # (a canonicalised temporary is nobody's matrix: nothing to leave the copy with)
-        attach_device(m, X, backend)
-    return host, X, backend
 
 
 def _row_of(X):
@@ -125,12 +99,7 @@ def _with_values(m, X, be, values):
     the new matrix keeps the device copy."""
     if X is None:
         return csr_matrix((values, m.indices.copy(), m.indptr.copy()), shape=m.shape)
-    from .._atac.preproc import attach_device
-
-    new = csr_matrix((be.to_host(values), m.indices.copy(), m.indptr.copy()), shape=m.shape)
-    new.has_sorted_indices = True  # (a resident copy is canonical)
-    attach_device(new, X.with_values(values), be)
-    return new
+    return host_view(X.with_values(values), be, indices=m.indices.copy(), indptr=m.indptr.copy())
 
 
 def _get(adata, layer):
@@ -158,7 +127,7 @@ def normalize_total(data, target_sum: Optional[float] = None, *, exclude_highly_
     if exclude_highly_expressed:
         raise NotImplementedError("normalize_total: exclude_highly_expressed=True is not implemented")
     _one_rank(comm, "rna.pp.normalize_total")
-    adata = _modality(data)
+    adata = modality(data, "rna")
     if copy:
         if not inplace:
             raise ValueError("`copy=True` cannot be used with `inplace=False`.")
@@ -166,7 +135,7 @@ def normalize_total(data, target_sum: Optional[float] = None, *, exclude_highly_
     counts = _get(adata, layer)
     X = be = None
     if issparse(counts):
-        m, X, be = device_copy(_float_csr(counts), backend)
+        m, X, be = device_copy(_float_csr(counts), backend, host_route=True)
         totals = be.to_host(be.row_col_sums(X)[0]) if X is not None else \
             np.asarray(m.astype(np.float64).sum(axis=1)).reshape(-1)
     else:
@@ -200,13 +169,13 @@ def log1p(data, *, base: Optional[float] = None, layer: Optional[str] = None, co
     ``uns["log1p"] = {"base": base}`` (scanpy's signature).  An integer matrix becomes float32.
     """
     _one_rank(comm, "rna.pp.log1p")
-    adata = _modality(data)
+    adata = modality(data, "rna")
     if copy:
         adata = adata.copy()
     counts = _get(adata, layer)
     log_div = float(np.log(base)) if base is not None else 0.0
     if issparse(counts):
-        m, X, be = device_copy(_float_csr(counts), backend)
+        m, X, be = device_copy(_float_csr(counts), backend, host_route=True)
         vals = _sweep(be, X, log=True, log_div=log_div) if X is not None else _sweep_host(m, log=True, log_div=log_div)
         new = _with_values(m, X, be, vals)
     else:
@@ -297,14 +266,14 @@ def highly_variable_genes(data, *, n_top_genes: Optional[int] = None, min_mean: 
     if batch_key is not None:
         raise NotImplementedError("highly_variable_genes: batch_key is not implemented")
     _one_rank(comm, "rna.pp.highly_variable_genes")
-    adata = _modality(data)
+    adata = modality(data, "rna")
     counts = _get(adata, layer)
     n = int(counts.shape[0])
     base = (adata.uns.get("log1p") or {}).get("base")
     c = float(np.log(base)) if base is not None else 1.0
     X = None
     if issparse(counts):
-        m, X, be = device_copy(_float_csr(counts), backend)
+        m, X, be = device_copy(_float_csr(counts), backend, host_route=True)
     if X is not None:
         sums, _nnz = gene_moments_device(be, X, c=c, with_e=True)
         s1, s2 = sums[2], sums[3]
@@ -399,8 +368,6 @@ _FORMS = {}
 
 
 def _dense_fingerprint(a):
-    from .._atac.preproc import _hash_arrays
-
     return (a.shape, a.dtype.str, a.flags.c_contiguous) + _hash_arrays([a])
 
 
@@ -455,14 +422,14 @@ def scale(data, zero_center: bool = True, max_value: Optional[float] = None, cop
     if mask_obs is not None:
         raise NotImplementedError("scale: mask_obs= is not implemented")
     _one_rank(comm, "rna.pp.scale")
-    adata = _modality(data)
+    adata = modality(data, "rna")
     if copy:
         adata = adata.copy()
     counts = _get(adata, layer)
     n = int(counts.shape[0])
     X = be = None
     if issparse(counts):
-        m, X, be = device_copy(_float_csr(counts), backend)
+        m, X, be = device_copy(_float_csr(counts), backend, host_route=True)
     else:
         m = np.asarray(counts)
         if m.dtype not in (np.float32, np.float64):

@@ -277,7 +277,7 @@ def run_c3_api(be, n_cells=250_000, n_feat=200_000, density=0.03, seed=0):
     import muon_amd
     from muon_amd import AnnData
     from muon_amd import atac as ac
-    from muon_amd._atac import preproc as P
+    from muon_amd import _hostmatrix as H  # (attach_device and resident look _fingerprint up there)
 
     X = be.synth_counts(0, n_cells, n_feat, 50, density, seed)
     m = sp.csr_matrix((be.to_host(X.values).astype(np.float32), be.to_host(X.indices), be.to_host(X.indptr)),
@@ -312,7 +312,7 @@ def run_c3_api(be, n_cells=250_000, n_feat=200_000, density=0.03, seed=0):
         # it == 2: the opt-in takeover of the replaced matrix's host arrays (r06: off by default - the reference never
         # writes into the matrix it replaces and a raw-pointer holder is invisible to reference counts)
         saved = [(be, "upload_csr", timed(be, "upload_csr", "upload")), (be, "to_host", timed(be, "to_host", "download")),
-                 (P, "_fingerprint", timed(P, "_fingerprint", "fingerprint"))]
+                 (H, "_fingerprint", timed(H, "_fingerprint", "fingerprint"))]
         _sync()
         t0 = time.perf_counter()
         ac.pp.tfidf(ad, backend=be, reuse_host=(it == 2))
@@ -344,7 +344,7 @@ def run_c3_api(be, n_cells=250_000, n_feat=200_000, density=0.03, seed=0):
                                      "taken_over": bool(taken),
                                      "note": "tfidf(..., reuse_host=True): nothing else referenced the replaced matrix, the result "
                                              "took its index arrays over and was downloaded into its value array "
-                                             "(preproc._dies_with_rebinding; opt-in since r06)"},
+                                             "(_hostmatrix._dies_with_rebinding; opt-in since r06)"},
             "config": {"workload": f"c3_api: {n_cells} cells x {n_feat} peaks ({nnz} stored entries, a quarter of configs[2]) as a host "
                                    f"scipy CSR in an AnnData; tfidf writes adata.X back, lsi finds the device copy "
                                    f"(fingerprint check) and writes obsm / varm / uns"},

@@ -36,7 +36,7 @@ def child(n: int, d: int, comps: int) -> dict:
     from scipy.sparse import csr_matrix
 
     import muon_amd as mu
-    from muon_amd._atac.preproc import attach_device
+    from muon_amd._hostmatrix import attach_device
     from muon_amd._backend import get_backend
 
     be = get_backend()

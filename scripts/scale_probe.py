@@ -53,7 +53,7 @@ def child(n: int, d: int, density: float, k: int, reps: int) -> dict:
     from scipy.sparse import csr_matrix
 
     import muon_amd as mu
-    from muon_amd._atac.preproc import attach_device
+    from muon_amd._hostmatrix import attach_device
     from muon_amd._backend import get_backend
     from muon_amd._core.pca import pca_device
     from muon_amd._rna import preproc as R

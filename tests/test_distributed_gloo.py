@@ -32,7 +32,8 @@ def _worker(rank, world, port, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from muon_amd._atac.preproc import canonical_csr, tfidf_device
+        from muon_amd._atac.preproc import tfidf_device
+        from muon_amd._hostmatrix import canonical_csr
         from muon_amd._atac.tools import lsi_device
         from muon_amd._comm import TorchDistComm
         from muon_amd._core.mofa_engine import MofaEngine
@@ -126,7 +127,8 @@ def _worker(rank, world, port, q):
 @pytest.mark.timeout(300)
 def test_world_size_2_matches_single_process():
     sys.path.insert(0, ROOT)
-    from muon_amd._atac.preproc import canonical_csr, tfidf_device
+    from muon_amd._atac.preproc import tfidf_device
+    from muon_amd._hostmatrix import canonical_csr
     from muon_amd._atac.tools import lsi_device
     from muon_amd._core.mofa_engine import MofaEngine
     from oracle import lsi_oracle

@@ -14,7 +14,7 @@ import torch
 import torch.multiprocessing as mp
 
 import muon_amd as mu
-from muon_amd._atac.preproc import DEVICE_ATTR, attach_device, resident
+from muon_amd._hostmatrix import DEVICE_ATTR, attach_device, resident
 from muon_amd._core import io as mio
 from muon_amd._core.preproc import _submatrix_tensor, submatrix_device
 from muon_amd._operators import has

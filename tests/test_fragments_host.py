@@ -13,7 +13,7 @@ import muon_amd as mu
 from muon_amd import AnnData, MuData
 from muon_amd import atac as ac
 from muon_amd._atac import fragments as fr
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from tests import frag_fixture as fx
 from tests import frag_refs
 from tests.cpu_backend import CpuTestBackend

@@ -7,7 +7,7 @@ import torch
 
 import muon_amd as mu
 from muon_amd import _ffi
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from oracle import lsi_oracle
 from tests.synth import planted_topics_csr
 

@@ -11,7 +11,7 @@ import torch
 from muon_amd import AnnData
 from muon_amd import atac as ac
 from muon_amd._atac import fragments as fr
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from tests import frag_fixture as fx
 
 pytestmark = pytest.mark.gpu

@@ -117,7 +117,7 @@ def test_baseline_shape_10k_by_30k_against_the_f64_oracle(hip):
     assert angle < ANGLE
     np.testing.assert_allclose(ad.uns["lsi"]["stdev"], ref["stdev"], rtol=1e-5)
     assert lsi_oracle.max_subspace_angle(ad.obsm["X_lsi"], ref["X_lsi"]) < 5 * ANGLE
-    from muon_amd._atac.preproc import resident
+    from muon_amd._hostmatrix import resident
     _, _, _, info = lsi_device(hip, resident(ad.X, hip), n_comps=50, return_info=True)
     # (the bound is a statement at the 1e-5 ... 1e-4 level; at the f32 floor, ~1e-6, it is only indicative)
     assert info["converged"] and info["angle_bound"] < ANGLE and angle <= max(info["angle_bound"], 1e-5)

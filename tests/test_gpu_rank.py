@@ -14,7 +14,7 @@ import torch
 
 from muon_amd import atac as ac
 from muon_amd._atac import rank as R
-from muon_amd._atac.preproc import attach_device, resident, upload_canonical
+from muon_amd._hostmatrix import attach_device, resident, upload_canonical
 from tests import rank_fixture as F
 from tests import rank_refs
 

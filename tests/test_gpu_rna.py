@@ -16,7 +16,7 @@ import torch
 
 import muon_amd as mu
 from muon_amd import AnnData, rna
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from muon_amd._backend import DeviceCSR
 from tests import rna_fixture as fx
 

@@ -243,7 +243,7 @@ def test_scale_then_pca_golden(hip, name, monkeypatch):
 
 
 def test_zero_center_false_keeps_the_device_copy(hip):
-    from muon_amd._atac.preproc import resident
+    from muon_amd._hostmatrix import resident
 
     M = sr.e2e_matrix("b16_clip3")
     spy = _Spy(hip)

@@ -382,7 +382,7 @@ def test_tfidf_takes_the_replaced_matrix_over_only_when_nothing_else_sees_it(mon
     """`adata.X = tf_idf` (preproc.py:121-127) leaves the old matrix to its other owners.  When there are none, the
     result reuses its index arrays and value buffer (no 6 GB copy / first touch / release at scale); an owner -
     `layers["counts"] = adata.X`, a variable, a view of one of the arrays - keeps seeing the counts."""
-    from muon_amd._atac import preproc
+    from muon_amd import _hostmatrix
 
     monkeypatch.delenv("MUON_AMD_REUSE_HOST", raising=False)
     ref = AnnData(_big_counts())
@@ -392,7 +392,7 @@ def test_tfidf_takes_the_replaced_matrix_over_only_when_nothing_else_sees_it(mon
     ac.pp.tfidf(ref, backend=BE)          # r06: OFF by default - the reference never writes into the matrix it replaces
     assert ref.X.data.ctypes.data != where
     # the counts it compares with are measured on this interpreter and the whole decision is self-tested at first use
-    cal = preproc._calibrate_refs()
+    cal = _hostmatrix._calibrate_refs()
     assert cal["ok"] and cal["matrix2"] >= 3 and cal["attr"] >= 2
 
     ad = AnnData(_big_counts())
@@ -432,7 +432,7 @@ def test_tfidf_takes_the_replaced_matrix_over_only_when_nothing_else_sees_it(mon
     where = ad.X.data.ctypes.data
     ac.pp.tfidf(ad, backend=BE)
     assert ad.X.data.ctypes.data == where
-    monkeypatch.setitem(preproc._CALIBRATION, "ok", False)
+    monkeypatch.setitem(_hostmatrix._CALIBRATION, "ok", False)
     ad = AnnData(_big_counts())
     where = ad.X.data.ctypes.data
     ac.pp.tfidf(ad, backend=BE)

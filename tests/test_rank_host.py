@@ -11,7 +11,7 @@ from scipy import stats
 
 from muon_amd import atac as ac
 from muon_amd._atac import rank as R
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from muon_amd._backend import DeviceCSR
 from tests import rank_fixture as F
 from tests import rank_refs

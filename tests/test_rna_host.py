@@ -21,7 +21,7 @@ import scipy.sparse as sp
 
 import muon_amd as mu
 from muon_amd import AnnData, MuData, rna
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from tests import rna_fixture as fx
 from tests.cpu_backend import CpuTestBackend
 

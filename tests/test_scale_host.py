@@ -15,7 +15,7 @@ import scipy.sparse as sp
 
 import muon_amd as mu
 from muon_amd import AnnData, MuData, rna
-from muon_amd._atac.preproc import resident
+from muon_amd._hostmatrix import resident
 from muon_amd._rna import preproc as rp
 from tests import scale_refs as sr
 from tests.scale_support import CountingCpuBackend, KernelCpuBackend
