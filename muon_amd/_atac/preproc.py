@@ -20,7 +20,7 @@ from .._containers import modality, view_to_actual
 from .._ffi import TFIDF_LOG_IDF, TFIDF_LOG_TF, TFIDF_LOG_TFIDF
 from .._hostmatrix import (DEVICE_ATTR, _copy_array, _dies_with_rebinding, _is_canonical, _is_canonical_csc,
                            _reuse_host_enabled, attach_device, resident, upload_canonical)
-from .._operators import has
+from .._operators import has, transposed_csr
 
 
 def _flags(log_tf, log_idf, log_tfidf):
@@ -177,8 +177,7 @@ def tfidf(
         n_r, n_c = counts.shape
         Xc = backend.upload_csr(counts.indptr, counts.indices, counts.data, (n_c, n_r))
         # f32: the tile-staged transposition of csrc/tpack4.hip (3x the rate of the general kernel)
-        fast = counts.dtype == np.float32 and has(backend, "transpose_csr") and counts.nnz > 0
-        X = backend.transpose_csr(Xc) if fast else backend.transpose(Xc)
+        X = transposed_csr(backend, Xc)
         host = None
     else:
         host, X = upload_canonical(backend, counts)

@@ -28,7 +28,7 @@ from scipy.sparse import issparse
 from .._backend import DeviceCSR, backend_or_default
 from .._containers import modality
 from .._hostmatrix import device_copy
-from .._operators import OperatorSet, has
+from .._operators import OperatorSet, has, transposed_csr
 
 METHODS = ("t-test", "t-test_overestim_var", "wilcoxon", "logreg")
 SORT_BUDGET_BYTES = 1 << 30  # device memory the per-row sort of X^T may hold at a time
@@ -146,9 +146,7 @@ def _transposed(adata, layer, backend):
         backend = backend_or_default(backend)  # raises without a GPU: there is no CPU path in the package
         return _dense_transposed(backend, counts), _NoKernels(backend)
     _host, X, backend = device_copy(counts, backend)
-    if X.values.dtype == torch.float32 and has(backend, "transpose_csr"):
-        return backend.transpose_csr(X), backend
-    return backend.transpose(X), backend
+    return transposed_csr(backend, X), backend
 
 
 # ---------------------------------------------------------------------------------------------------------------------

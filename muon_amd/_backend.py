@@ -11,7 +11,7 @@ declared once in ``_operators.OperatorSet``.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import contextlib
 import ctypes
@@ -104,20 +104,6 @@ class DeviceStream:
 
 
 @dataclass
-class SplitStream:
-    """An f64-valued matrix as row streams: v = hi + lo with hi = fl32(v), lo = fl32(v - hi) (exact to
-    2^-48); ``lo`` is None when every value is exact in f32 (counts, f32 input).  SpMM-only, against
-    f64 dense blocks."""
-
-    hi: DeviceStream
-    lo: Optional[DeviceStream]
-
-    @property
-    def shape(self):
-        return self.hi.shape
-
-
-@dataclass
 class DeviceEll:
     """Sliced-ELL operand of the narrow-block SpMM (csrc/spmm_ell.hip, include/muon_amd.h): rows in launch order
     (``perm``: position -> row, -1 none), groups of 16 positions (one wave each), columns in slabs of 1024;
@@ -137,16 +123,21 @@ class DeviceEll:
 
 
 @dataclass
-class SplitEll:
-    """An f64-valued matrix as sliced-ELL operands for f64 blocks: v = hi + lo, hi = fl32(v), lo = fl32(v - hi);
-    ``lo`` is None when every value is exact in f32.  SpMM-only."""
+class SplitOperand:
+    """An f64-valued matrix as two operands of one layout (row streams or sliced ELL) with f32 stored values:
+    v = hi + lo with hi = fl32(v), lo = fl32(v - hi) (exact to 2^-48); ``lo`` is None when every value is exact in f32
+    (counts, f32 input).  SpMM-only, against f64 dense blocks."""
 
-    hi: DeviceEll
-    lo: Optional[DeviceEll]
+    hi: Union[DeviceStream, DeviceEll]
+    lo: Union[DeviceStream, DeviceEll, None]
 
     @property
     def shape(self):
         return self.hi.shape
+
+    @property
+    def nnz(self) -> int:
+        return self.hi.nnz
 
 
 _NULL_CTX = contextlib.nullcontext()
@@ -183,6 +174,19 @@ def _split_lo(rest: torch.Tensor) -> Optional[torch.Tensor]:
     """lo = fl32(rest) of ``_split_hi``, or None when every value was exact in f32.  Synchronises (it reads whether some
     rest is not zero): a caller with work to queue on hi alone queues that first."""
     return rest.to(torch.float32) if bool((rest != 0).any().item()) else None
+
+
+def _split_build(X: DeviceCSR, build) -> Tuple[SplitOperand, ...]:
+    """``build`` (CSR with f32 values -> tuple of operands) on the hi part of an f64-valued CSR and, when some value is
+    not exact in f32, on its lo part: one SplitOperand per operand.  The work on hi is queued before ``_split_lo``
+    synchronises."""
+    assert X.values.dtype == torch.float64
+    hi, rest = _split_hi(X.values)
+    b_hi = build(X.with_values(hi))
+    lo = _split_lo(rest)
+    del rest
+    b_lo = build(X.with_values(lo)) if lo is not None else (None,) * len(b_hi)
+    return tuple(SplitOperand(a, b) for a, b in zip(b_hi, b_lo))
 
 
 def _mofa_pad_width(K: int) -> int:
@@ -1141,16 +1145,8 @@ class HipBackend(OperatorSet):
         return Z
 
     def split_streams(self, X: DeviceCSR):
-        """(row streams of X, row streams of X^T) for an f64-valued CSR: see SplitStream."""
-        assert X.values.dtype == torch.float64
-        hi, rest = _split_hi(X.values)
-        Xh = X.with_values(hi)
-        s_hi, t_hi = self.stream(Xh), self.transpose_stream(Xh)
-        lo = _split_lo(rest)
-        if lo is not None:
-            Xl = X.with_values(lo)
-            return SplitStream(s_hi, self.stream(Xl)), SplitStream(t_hi, self.transpose_stream(Xl))
-        return SplitStream(s_hi, None), SplitStream(t_hi, None)
+        """(row streams of X, row streams of X^T) for an f64-valued CSR: see SplitOperand."""
+        return _split_build(X, lambda P: (self.stream(P), self.transpose_stream(P)))
 
     def launch_layout(self, lens: torch.Tensor, K: Optional[int] = None):
         """Where the rows go in a row stream (include/muon_amd.h): sorted by length (descending,
@@ -1190,37 +1186,38 @@ class HipBackend(OperatorSet):
         return perm, inv, K
 
     # -- sliced-ELL operand of the narrow-block SpMM (csrc/spmm_ell.hip) ---------------------------
+    def ell16_fits(self, X, wide: bool) -> bool:
+        """The sliced-ELL kernels address both dense operands with 32-bit byte offsets (64-byte rows of an f32 block,
+        128-byte rows of an f64 one): X and X^T must both stay under 4 GiB of dense rows, and neither is empty."""
+        return min(X.shape) > 0 and max(X.shape) * (128 if wide else 64) < (1 << 32)
+
     def ell16(self, X: DeviceCSR, wide: bool = False):
         """Lay a canonical CSR out for mu_spmm_ell16_f32 / _f64 (once per fit: the operand of MOFA's sparse views is
         multiplied hundreds of times).  f32 values -> DeviceEll; ``wide`` (against f64 blocks): 512-column slabs,
-        and f64 values -> SplitEll (hi + lo)."""
+        and f64 values -> SplitOperand (hi + lo)."""
+        if not self.ell16_fits(X, wide):
+            raise NotImplementedError(f"sliced ELL: a {X.shape[0]} x {X.shape[1]} operand does not fit (ell16_fits)")
         waves = int(self.lib.mu_spmm_ell16_waves(X.shape[0]))
-        cols = 512 if wide else 1024
-        fill = self._ell16_fill
+
+        def layout(P):
+            return ell16_layout(P, waves, 512 if wide else 1024, self.slab_ptr_width, self._ell16_fill)
+
         if X.values.dtype == torch.float32:
-            return ell16_layout(X, waves, cols, self.slab_ptr_width, fill)
-        assert wide and X.values.dtype == torch.float64
-        hi, rest = _split_hi(X.values)
-        e_hi = ell16_layout(X.with_values(hi), waves, cols, self.slab_ptr_width, fill)
-        lo = _split_lo(rest)
-        if lo is not None:
-            return SplitEll(e_hi, ell16_layout(X.with_values(lo), waves, cols, self.slab_ptr_width, fill))
-        return SplitEll(e_hi, None)
+            return layout(X)
+        assert wide
+        return _split_build(X, lambda P: (layout(P),))[0]
 
     def ell16_pair(self, X: DeviceCSR, wide: bool = False):
         """(layout of X, layout of X^T) - both operands of a fit.  The transposed CSR comes from the tile-staged
         transposition (f32 values; an f64-valued matrix is transposed as its hi and lo parts, the second only when
         some value is not exact in f32) instead of the general kernel behind `transpose`."""
+        def pair(P):
+            return self.ell16(P, wide), self.ell16(self.transpose_csr(P), wide)
+
         if X.values.dtype == torch.float32:
-            return self.ell16(X, wide), self.ell16(self.transpose_csr(X), wide)
-        assert wide and X.values.dtype == torch.float64
-        hi, rest = _split_hi(X.values)
-        lo = _split_lo(rest)
-        del rest
-        parts = [hi] if lo is None else [hi, lo]
-        fw = [self.ell16(X.with_values(p), True) for p in parts]
-        tr = [self.ell16(self.transpose_csr(X.with_values(p)), True) for p in parts]
-        return SplitEll(fw[0], fw[1] if len(fw) > 1 else None), SplitEll(tr[0], tr[1] if len(tr) > 1 else None)
+            return pair(X)
+        assert wide
+        return _split_build(X, pair)
 
     def col_moments(self, Y: torch.Tensor, a: int, b: int):
         """(sum, sum of squares) per column over rows a .. b-1 of a dense row-major f32 / f64 block: f64 sums, one pass."""
@@ -1357,16 +1354,11 @@ class HipBackend(OperatorSet):
         n, d = X.shape
         B = Q.shape[1]
         assert Q.shape[0] == d and Q.dtype in (torch.float32, torch.float64) and Q.is_contiguous()
-        if isinstance(X, SplitStream):
-            # f64 values as two f32 streams: X Q = X_hi Q + X_lo Q, accumulated in f64
-            out = self.spmm(X.hi, Q, out=out)
+        if isinstance(X, SplitOperand):
+            # f64 values as two f32 operands: X Q = X_hi Q + X_lo Q, accumulated in f64
+            out = self.spmm(X.hi, Q, out=out, accumulate=accumulate)
             if X.lo is not None:
                 self.spmm(X.lo, Q, out=out, accumulate=True)
-            return out
-        if isinstance(X, SplitEll):
-            out = self.spmm_ell(X.hi, Q, out=out, accumulate=accumulate)
-            if X.lo is not None:
-                self.spmm_ell(X.lo, Q, out=out, accumulate=True)
             return out
         if isinstance(X, DeviceEll):
             return self.spmm_ell(X, Q, out=out, accumulate=accumulate)

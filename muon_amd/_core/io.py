@@ -31,7 +31,7 @@ import torch
 from .._backend import DeviceCSR, backend_or_default
 from .._comm import default_comm
 from .._hostmatrix import host_view
-from .._operators import has
+from .._operators import has, transposed_csr
 
 
 def shard_rows(n_rows: int, comm=None) -> Tuple[int, int]:
@@ -186,9 +186,7 @@ def device_csr_from_csc(indptr, indices, data, shape, backend=None, values_dtype
     backend = backend_or_default(backend)
     n, d = int(shape[0]), int(shape[1])
     Xt = backend.upload_csr(indptr, indices, data, (d, n), values_dtype=values_dtype)  # CSR of X^T
-    if Xt.values.dtype == torch.float32 and has(backend, "transpose_csr"):
-        return backend.transpose_csr(Xt)
-    return backend.transpose(Xt)
+    return transposed_csr(backend, Xt)
 
 
 def read_10x_arrays(matrix: Mapping, atac_only: bool = True, feature_types=None, barcodes=None,

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .._comm import default_comm
+from .._operators import has
 
 A0 = 1e-14
 B0 = 1e-14
@@ -26,11 +27,24 @@ TOL = {"fast": 5e-4, "medium": 5e-5, "slow": 5e-6}
 LN_THETA0 = float(torch.digamma(torch.tensor(1.0, dtype=torch.float64)) - torch.digamma(torch.tensor(2.0, dtype=torch.float64)))
 
 
-def _can_ell16(be, X, wide: bool) -> bool:
-    """The sliced-ELL kernels address both dense operands with 32-bit byte offsets (64-byte rows of an f32 block, 128-byte
-    rows of an f64 one): X and X^T must both stay under 4 GiB of dense rows, else the row-stream path is taken."""
-    row = 128 if wide else 64
-    return max(X.shape) * row < (1 << 32)
+def sparse_operands(be, X, width: int, dtype):
+    """``(Xs, Xt)``: the operands of X Q and X^T Y for a sparse view X (a device CSR with values of ``dtype``) that a fit
+    multiplies hundreds of times by dense blocks of ``dtype``, ``width`` (16 / 32 / 64) columns wide.  Laid out once, by
+    the first rung that ``be`` and the shape allow:
+      1. width 16: sliced ELL (csrc/spmm_ell.hip) - no per-row protocol is left in the product; X^T through the
+         tile-staged transposition; f64: f32 stored values, hi + lo where some value is not exact in f32
+      2. f32: row streams in both directions
+      3. f64, width <= 32: the same row streams with f32 stored values, hi + lo
+      4. the CSR itself and its general transpose"""
+    wide = dtype == torch.float64
+    if width == 16 and has(be, "ell16_pair", "ell16_fits") and be.ell16_fits(X, wide=wide):
+        return be.ell16_pair(X, wide=wide)
+    if dtype == torch.float32 and has(be, "can_stream") and be.can_stream(X, 16):
+        Xt = be.transpose_stream(X)
+        return be.stream(X), Xt
+    if wide and has(be, "split_streams") and width <= 32 and min(X.shape) > 0:
+        return be.split_streams(X)
+    return X, be.transpose(X)
 
 
 @dataclass(slots=True)

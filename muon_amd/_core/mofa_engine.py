@@ -39,7 +39,7 @@ import torch
 from scipy.sparse import issparse
 
 from .._operators import has
-from .mofa_common import A0, B0, TH_A0, TH_B0, TOL, MofaDriver, _can_ell16  # noqa: F401  (the constants: importable from here)
+from .mofa_common import A0, B0, TH_A0, TH_B0, TOL, MofaDriver, sparse_operands  # noqa: F401  (the constants: importable from here)
 
 
 def _pad_block(w: int) -> int:
@@ -324,35 +324,9 @@ class MofaEngine(MofaDriver):
             for g, (a, b) in enumerate(self.gslice):
                 if b > a:
                     torch.addcmul(src[a:b], V.pres[a:b, None], mu[g][None, :], value=-1.0, out=V.Y[a:b])
-        elif (self.T == torch.float32 and has(be, "ell16") and _pad_block(self.G * self.K) == 16
-              and V.X.shape[0] > 0 and V.X.shape[1] > 0 and _can_ell16(be, V.X, wide=False)):
-            # f32, factor blocks of <= 16 columns: the operand of both directions never changes during a fit - laid
-            # out once as sliced ELL (csrc/spmm_ell.hip): no per-row protocol is left in the product
-            # (the transposed operand through the tile-staged transposition, csrc/tpack4.hip: 3 ms where the general
-            #  kernel behind `transpose` took 14)
-            V.Xt = be.ell16(be.transpose_csr(V.X) if has(be, "transpose_csr") else be.transpose(V.X))
-            V.Xs = be.ell16(V.X)
-        elif self.T == torch.float32 and has(be, "can_stream") and be.can_stream(V.X, 16):
-            # f32: both directions read row streams, built once
-            V.Xt = be.transpose_stream(V.X)
-            V.Xs = be.stream(V.X)
-        elif (self.T == torch.float64 and has(be, "ell16") and _pad_block(self.G * self.K) == 16
-              and V.X.shape[0] > 0 and V.X.shape[1] > 0 and _can_ell16(be, V.X, wide=True)):
-            # f64 (the reference's default precision), factor blocks of <= 16 columns: the same static layout with
-            # f32 stored values - one operand when the data is exact in f32, hi + lo otherwise - against f64 blocks
-            if has(be, "ell16_pair"):
-                V.Xs, V.Xt = be.ell16_pair(V.X, wide=True)
-            else:
-                V.Xt = be.ell16(be.transpose(V.X), wide=True)
-                V.Xs = be.ell16(V.X, wide=True)
-        elif (self.T == torch.float64 and has(be, "split_streams") and _pad_block(self.G * self.K) <= 32
-              and V.X.shape[0] > 0 and V.X.shape[1] > 0):
-            # f64 (the reference's default precision): the same row streams with f32 stored values -
-            # one stream when the data is exact in f32, hi + lo otherwise - against f64 blocks
-            V.Xs, V.Xt = be.split_streams(V.X)
         else:
-            V.Xt = be.transpose(V.X)
-            V.Xs = V.X
+            # the operands of both directions never change during a fit: laid out once
+            V.Xs, V.Xt = sparse_operands(be, V.X, _pad_block(self.G * self.K), self.T)
         return V
 
     def _init_state(self, z0):

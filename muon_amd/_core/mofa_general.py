@@ -36,7 +36,7 @@ import torch
 from scipy.sparse import issparse
 
 from .._operators import has
-from .mofa_common import A0, B0, LN_THETA0, TH_A0, TH_B0, MofaDriver, _can_ell16
+from .mofa_common import A0, B0, LN_THETA0, TH_A0, TH_B0, MofaDriver
 
 LIKELIHOODS = ("gaussian", "poisson", "bernoulli")
 
@@ -220,11 +220,10 @@ class GeneralMofaEngine(MofaDriver):
             V.Xt = be.transpose(V.X)
         # the three sparse products of a fused bernoulli view multiply by one 16-column block each: the sliced-ELL layout
         # of MofaEngine's sparse views (csrc/spmm_ell.hip: 0.24 -> ~0.08 ms per product at 3e7 entries), laid out once
-        if V.fusedb and has(be, "ell16"):
-            wide = T == torch.float64
-            if min(V.X.shape) > 0 and _can_ell16(be, V.X, wide):
-                # (f64 values go in as hi + lo parts, the second only when some value is not exact in f32)
-                V.Xe, V.Xte = be.ell16(V.X, wide=wide), be.ell16(V.Xt, wide=wide)
+        wide = T == torch.float64
+        if V.fusedb and has(be, "ell16", "ell16_fits") and be.ell16_fits(V.X, wide):
+            # (f64 values go in as hi + lo parts, the second only when some value is not exact in f32)
+            V.Xe, V.Xte = be.ell16(V.X, wide=wide), be.ell16(V.Xt, wide=wide)
         if lik == "gaussian" and V.kind == "dense":
             # the centred / scaled / masked values are a constant of the fit: made once, in place (r04 recomputed them in
             # every chunk pass - three tensor passes over the view, six times per iteration).  Same operations in the

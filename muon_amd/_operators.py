@@ -10,6 +10,7 @@ tensor formulation.  Nothing here computes anything.
 wrapper that forwards through ``__getattr__`` (bench.py's timer, the tests' call counters), one that hides an operator
 by raising ``AttributeError`` for it, and a plain class that only defines what it implements.
 """
+import torch
 
 
 class OperatorSet:
@@ -37,8 +38,8 @@ class OperatorSet:
     raise_tpack4 = tpack4_status = launch_layout = spmm_slab = None
     # the cell slice of lsi's warm start (spmm_win.hip); behind slice_plan: the rest
     slice_plan = slice_stream = spmm_slice = spmm_slice_t = spmm_slab_ranged = None
-    # sliced-ELL operands of the narrow-block SpMM (spmm_ell.hip)
-    ell16 = ell16_pair = spmm_ell = None
+    # sliced-ELL operands of the narrow-block SpMM (spmm_ell.hip); ell16_fits(X, wide): whether its 32-bit offsets reach
+    ell16_fits = ell16 = ell16_pair = spmm_ell = None
     # block orthogonalisation on the device (dense.hip); kernel switches (runtime.hip)
     chol_rinv = tune = tune_keys = None
     # neighbour search and WNN (knn.hip, wnn.hip)
@@ -90,3 +91,11 @@ def has(ops, *names) -> bool:
         if getattr(ops, n, None) is None:
             return False
     return True
+
+
+def transposed_csr(be, X):
+    """X^T as a device CSR: the tile-staged transposition (``transpose_csr``: f32 values) where ``be`` has it and X
+    has stored entries, else the general ``transpose``.  A dispatch, like ``has``: the operators compute."""
+    if X.values.dtype == torch.float32 and X.nnz > 0 and has(be, "transpose_csr"):
+        return be.transpose_csr(X)
+    return be.transpose(X)

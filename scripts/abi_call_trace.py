@@ -14,8 +14,9 @@ of an entry whose prototype ends in `void* stream` as `stream`.  The record is J
 is free) are left out and named.  A host refactor leaves every remaining segment identical.  Exit status 1 otherwise.
 
 Usage: python scripts/abi_call_trace.py record CHECKOUT OUT.json [--repeat N] [pytest arguments ...]
-       python scripts/abi_call_trace.py compare [--stable-from PARENT.json] A.json B.json
+       python scripts/abi_call_trace.py compare [--unordered] [--stable-from PARENT.json] A.json B.json
 """
+import collections
 import ctypes
 import json
 import os
@@ -127,7 +128,7 @@ def _segments(run):
     return dict({"smoke()": run["smoke"]}, **run["tests"])
 
 
-def compare(paths, stable_from):
+def compare(paths, stable_from, unordered=False):
     def load(p):
         with open(p) as f:
             return [_segments(r) for r in json.load(f)["runs"]]
@@ -139,26 +140,36 @@ def compare(paths, stable_from):
     runs = [r for p in paths for r in load(p)]
     names = list(runs[0])
     missing = sorted(set().union(*map(set, runs)) - set(names)) + [k for k in names if any(k not in r for r in runs)]
-    bad = []
+    bad, reordered = [], []
     for k in names:
         if k in unstable or k in missing:
             continue
         first = runs[0][k]
         for r in runs[1:]:
-            if r[k] != first:
+            if r[k] != first and unordered and sorted(r[k]) == sorted(first):
+                if k not in reordered:
+                    reordered.append(k)
+            elif r[k] != first:
                 at = next((i for i, (a, b) in enumerate(zip(first, r[k])) if a != b), min(len(first), len(r[k])))
-                bad.append((k, at, first[at] if at < len(first) else None, r[k][at] if at < len(r[k]) else None))
+                ca, cb = collections.Counter(first), collections.Counter(r[k])
+                only = (ca - cb, cb - ca)
+                bad.append((k, at, first[at] if at < len(first) else None, r[k][at] if at < len(r[k]) else None, only))
                 break
     compared = [k for k in names if k not in unstable and k not in missing]
     print(f"{len(runs)} runs, {len(names)} segments, {sum(len(runs[0][k]) for k in compared)} calls compared in "
           f"{len(compared)} segments; unstable in {stable_from or '-'}: {len(unstable)}; not in every run: {len(missing)}; "
-          f"different: {len(bad)}")
+          f"different: {len(bad)}" + (f"; same calls in another order: {len(reordered)}" if unordered else ""))
     for k in sorted(unstable):
         print(f"  unstable by itself, left out: {k}")
     for k in missing:
         print(f"  not in every run: {k}")
-    for k, at, a, b in bad:
+    for k in reordered:
+        print(f"  same calls in another order: {k}")
+    for k, at, a, b, only in bad:
         print(f"  different: {k}\n    call {at}: {a}\n         vs: {b}")
+        if unordered:
+            for side, c in zip(("first", "other"), only):
+                print(f"    only in the {side} run: {sorted(c.elements())}")
     return 1 if bad or missing else 0
 
 
@@ -170,10 +181,12 @@ def main():
             repeat, rest = int(rest[1]), rest[2:]
         sys.exit(record(argv[1], argv[2], repeat, rest))
     if len(argv) >= 3 and argv[0] == "compare":
-        stable = None
+        stable, unordered = None, argv[1] == "--unordered"
+        if unordered:
+            del argv[1]
         if argv[1] == "--stable-from":
             stable, argv = argv[2], argv[:1] + argv[3:]
-        sys.exit(compare(argv[1:], stable))
+        sys.exit(compare(argv[1:], stable, unordered))
     sys.exit(__doc__)
 
 
