@@ -986,6 +986,25 @@ int mu_scale_dense_rows(int dtype, int64_t n, int64_t d, int64_t nnz, int64_t ro
                         const int64_t* d_indptr, const int32_t* d_indices, const void* d_values, const double* d_mean,
                         const double* d_std, const double* d_z, double lo, double hi, void* d_out, void* stream);
 
+/* ---- muon_amd.pp.qc_metrics(qc_vars=, percent_top=): per-row sums of a device CSR (scanpy's calculate_qc_metrics;
+ * csrc/qc.hip, C-ABI v815) ---------------------------------------------------------------------------------
+ * Row-major CSR: d_indptr int64 [n_rows + 1], d_indices int32 [nnz], values f32 / f64 [nnz]; d_indptr is clamped to
+ * [0, nnz].  A wave per row, walked grid-stride; results are f64; no float atomics and a fixed order of every sum: two
+ * calls agree byte for byte.  Arguments are checked before any HIP call.
+ *   mu_csr_row_masked_sums: d_flags uint32 [n_cols], bit q set when the column belongs to mask q; 1 <= n_masks <= 32;
+ *     d_out[i * n_masks + q] = sum of row i's stored values whose column has bit q set (bit 31 is an ordinary bit; a
+ *     column outside [0, n_cols) belongs to no mask).  One read of the row serves every mask.
+ *   mu_csr_row_top_sums: h_ns is a HOST array of n_tops values, 1 <= n_tops <= 8, strictly ascending, each in
+ *     1 .. n_cols; d_out[i * n_tops + j] = sum of the min(h_ns[j], len_i) largest stored values of row i (only stored
+ *     entries are looked at: rows shorter than n are padded with zeros).  A radix select over order-preserving integer
+ *     keys finds the n-th largest value t for every n in the same passes, then sum(v > t) + (n - count(v > t)) * t; no
+ *     limit on the row length.  A row that stores a NaN terminates and writes something. */
+int mu_csr_row_masked_sums(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
+                           const int32_t* d_indices, const void* d_values, const uint32_t* d_flags, int n_masks,
+                           double* d_out, void* stream);
+int mu_csr_row_top_sums(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
+                        const void* d_values, int n_tops, const int64_t* h_ns, double* d_out, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -10,6 +10,10 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.prot.pp.dsb     <->  muon.prot.pp.dsb    (protein normalisation ahead of neighbors on CITE-seq data)
     muon_amd.prot.pp.clr     <->  muon.prot.pp.clr
     muon_amd.pp.filter_obs   <->  muon.pp.filter_obs  (filter_var alike; pp.qc_metrics: scanpy's QC columns they key on)
+    muon_amd.pp.qc_metrics(qc_vars=, percent_top=)  <->  scanpy's calculate_qc_metrics: pct_counts_mt and
+                             pct_counts_in_top_{n}_genes from the resident CSR (a masked sum and a radix select per row)
+    muon_amd.pp.intersect_obs  <->  muon.pp.intersect_obs  (the cells all modalities share; device copies go along)
+    muon_amd.pp.sample_obs   <->  muon.pp.sample_obs  (the reference's draws under one np.random.seed; host only)
     muon_amd.atac.tl.count_fragments_features / tss_enrichment / nucleosome_signal  <->  muon.atac.tl.* (the fragment
                              tools: gene-activity counts and the two QC columns, over a fragment table on the device;
                              atac.tl.locate_fragments reads the TSV, atac.tl.fragments_from_arrays takes its columns)
@@ -42,7 +46,8 @@ from . import prot  # noqa: F401
 from . import rna  # noqa: F401
 from ._core import tools as tl  # noqa: F401
 from ._core import preproc as pp  # noqa: F401  (mu.pp.neighbors - weighted nearest neighbours -, mu.pp.l2norm,
-#   mu.pp.filter_obs / filter_var on the resident device copy, qc_metrics: the columns they key on)
+#   mu.pp.filter_obs / filter_var / intersect_obs on the resident device copy, qc_metrics: the columns they key on,
+#   mu.pp.sample_obs)
 from ._core import io  # noqa: F401  (arrays of 10x / mtx / snap files -> row-sharded device CSR)
 
 __version__ = "0.1.0"

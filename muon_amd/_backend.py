@@ -702,6 +702,27 @@ class HipBackend(OperatorSet):
                      colsum, work, wb, self._slab_ptr_of(X))
         return row_nnz, rowsum, col_nnz, colsum
 
+    def row_masked_sums(self, X: DeviceCSR, flags: torch.Tensor, M: int) -> torch.Tensor:
+        """f64 [n, M]: per row of X the sum of the stored values whose column has bit q of ``flags`` (int32 [d], read as
+        32 unsigned bits; 1 <= M <= 32) set, q < M; one read of the row serves every mask (csrc/qc.hip)."""
+        n, d = X.shape
+        if flags.dtype != torch.int32 or int(flags.numel()) != d or not 1 <= int(M) <= 32:
+            raise TypeError("row_masked_sums: flags int32[n_cols of X], 1 <= M <= 32")
+        out = self.empty((n, int(M)), torch.float64)
+        self._launch(self.lib.mu_csr_row_masked_sums, _dt(X.values), n, d, int(X.values.numel()), X.indptr, X.indices,
+                     X.values, flags.contiguous(), int(M), out)
+        return out
+
+    def row_top_sums(self, X: DeviceCSR, ns) -> torch.Tensor:
+        """f64 [n, len(ns)]: per row of X the sum of its min(n, stored entries) largest stored values, for the strictly
+        ascending ``ns`` (1 to 8 of them, each in 1 .. n_cols); rows of any length (csrc/qc.hip)."""
+        n, d = X.shape
+        ns = [int(v) for v in ns]
+        out = self.empty((n, len(ns)), torch.float64)
+        self._launch(self.lib.mu_csr_row_top_sums, _dt(X.values), n, d, int(X.values.numel()), X.indptr, X.values, len(ns),
+                     (ctypes.c_int64 * max(len(ns), 1))(*ns), out)
+        return out
+
     def csr_submatrix(self, X: DeviceCSR, rows: torch.Tensor, col_table: torch.Tensor, n_cols: int) -> DeviceCSR:
         """Rows ``rows`` (int64, ascending: new row -> old row) and the columns ``col_table`` keeps (int32[d]: old ->
         new column, -1 dropped; ``n_cols`` of them) of X: stored order inside the rows, explicit zeros kept, values bit

@@ -771,7 +771,7 @@ def neighbors(mdata, n_neighbors: Optional[int] = None, n_bandwidth_neighbors: i
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# muon.pp.filter_obs / filter_var (reference _core/preproc.py:675-881) and the QC columns they key on
+# muon.pp.filter_obs / filter_var / intersect_obs / sample_obs (reference _core/preproc.py:646-931) and the QC columns they key on
 # ---------------------------------------------------------------------------------------------------------------------
 # The step every ATAC workflow takes between reading and tfidf.  A host matrix that carries a device copy
 # (_hostmatrix.attach_device: the ingest, binarize, tfidf leave one) is subset on the host with scipy AND on the
@@ -946,31 +946,151 @@ def qc_device(backend, X, comm=None):
     return tuple(backend.to_host(t) for t in (row_nnz, rowsum, col_nnz, colsum))
 
 
-def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p: bool = True, comm=None, backend=None):
+# ---- per-row sums behind qc_vars / percent_top (csrc/qc.hip) -------------------------------------------
+_TOP_PER_LAUNCH, _MASKS_PER_LAUNCH = 8, 32  # what one launch of mu_csr_row_top_sums / mu_csr_row_masked_sums takes
+
+
+def masked_sums_tensor(X, flags, M):
+    """``row_masked_sums`` as tensor operations, for operator sets without the kernel: one ``index_add_`` over the
+    entries' row numbers per mask.  f64 [n, M]."""
+    n = X.shape[0]
+    dev = X.indptr.device
+    row_of = torch.repeat_interleave(torch.arange(n, device=dev), X.indptr[1:] - X.indptr[:-1])
+    f = flags[X.indices.long()]
+    v = X.values.to(torch.float64)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    out = torch.zeros((int(M), n), dtype=torch.float64, device=dev)
+    for q in range(int(M)):
+        out[q].index_add_(0, row_of, torch.where(((f >> q) & 1) != 0, v, zero))  # (>> of int32 is arithmetic: & 1 undoes it)
+    return out.T.contiguous()
+
+
+def top_sums_tensor(X, ns, max_cells=1 << 25):
+    """``row_top_sums`` as tensor operations: a segmented sort (by value, descending, then stably by row) and a
+    segmented cumulative sum - the first ``max(ns)`` sorted values of every row laid out as a zero-padded dense block of
+    rows, summed along the row, so a row's sum never sees another row's values.  Row blocks of ``max_cells`` cells."""
+    n = X.shape[0]
+    dev = X.indptr.device
+    ns = [int(v) for v in ns]
+    width = max(ns)
+    pick = torch.as_tensor([v - 1 for v in ns], device=dev)
+    out = torch.zeros((n, len(ns)), dtype=torch.float64, device=dev)
+    step = max(1, max_cells // width)
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        ptr = X.indptr[r0:r1 + 1]
+        lo, hi = int(ptr[0]), int(ptr[-1])
+        v = X.values[lo:hi].to(torch.float64)
+        row_of = torch.repeat_interleave(torch.arange(r1 - r0, device=dev), ptr[1:] - ptr[:-1])
+        o = torch.argsort(v, descending=True, stable=True)
+        o = o[torch.argsort(row_of[o], stable=True)]
+        rank = torch.arange(hi - lo, device=dev) - (ptr[:-1] - lo)[row_of]
+        keep = rank < width
+        block = torch.zeros((r1 - r0, width), dtype=torch.float64, device=dev)
+        block[row_of[keep], rank[keep]] = v[o][keep]
+        out[r0:r1] = torch.cumsum(block, dim=1)[:, pick]
+    return out
+
+
+def _mask_words(masks):
+    """bool [Q, d] -> [(int32 [d] flag words, masks in them)], one per group of 32 masks: bit b of a group's word is set
+    where mask 32 g + b holds the column (the words are uint32 bit patterns; torch carries them as int32)"""
+    words = []
+    for g in range(0, len(masks), _MASKS_PER_LAUNCH):
+        w = np.zeros(masks.shape[1], dtype=np.uint32)
+        for b, m in enumerate(masks[g:g + _MASKS_PER_LAUNCH]):
+            w |= m.astype(np.uint32) << np.uint32(b)
+        words.append((w.view(np.int32), min(_MASKS_PER_LAUNCH, len(masks) - g)))
+    return words
+
+
+def qc_row_sums_device(backend, X, masks, ns):
+    """``(masked [n, Q], top [n, len(ns)])`` f64 host arrays of device CSR ``X``: per row the sums of the stored values
+    inside each of the Q boolean column masks and the sums of the n largest stored values (``ns`` strictly ascending).
+    More than 32 masks / 8 values of n go as several launches.  Operator sets without the kernels get the tensor
+    formulations."""
+    n = X.shape[0]
+    masked, top = np.zeros((n, len(masks))), np.zeros((n, len(ns)))
+    for g, (words, M) in enumerate(_mask_words(masks) if len(masks) else []):
+        flags = backend.to_device(words, np.int32)
+        got = backend.row_masked_sums(X, flags, M) if has(backend, "row_masked_sums") else masked_sums_tensor(X, flags, M)
+        masked[:, g * _MASKS_PER_LAUNCH:g * _MASKS_PER_LAUNCH + M] = backend.to_host(got)
+    for g in range(0, len(ns), _TOP_PER_LAUNCH):
+        part = ns[g:g + _TOP_PER_LAUNCH]
+        got = backend.row_top_sums(X, part) if has(backend, "row_top_sums") else top_sums_tensor(X, part)
+        top[:, g:g + len(part)] = backend.to_host(got)
+    return masked, top
+
+
+def _qc_vars_masks(adata, qc_vars):
+    names = [qc_vars] if isinstance(qc_vars, str) else list(qc_vars)
+    masks = np.zeros((len(names), adata.shape[1]), dtype=bool)
+    for i, q in enumerate(names):
+        if q not in adata.var.columns:
+            raise ValueError(f"qc_vars: '{q}' is not a column of .var")
+        if adata.var[q].dtypes.name != "bool":
+            raise ValueError(f"qc_vars: .var['{q}'] is not boolean")
+        masks[i] = adata.var[q].values
+    return names, masks
+
+
+def _percent_top_list(percent_top, n_vars):
+    ns = sorted({int(v) for v in ([] if percent_top is None else percent_top)})
+    if ns and (ns[0] < 1 or ns[-1] > n_vars):
+        raise IndexError("Positions outside range of features.")
+    return ns
+
+
+def qc_metrics(data, *, qc_vars=(), percent_top=None, layer: Optional[str] = None, inplace: bool = True,
+               log1p: bool = True, comm=None, backend=None):
     """
     The per-cell and per-feature columns of scanpy's ``calculate_qc_metrics`` that the reference's tutorials filter
-    on (``mu.pp.filter_var(atac, "n_cells_by_counts", lambda x: x >= 10)``), computed on the device copy of the matrix.
+    on (``mu.pp.filter_var(atac, "n_cells_by_counts", lambda x: x >= 10)``, ``mu.pp.filter_obs(rna, "pct_counts_mt",
+    lambda x: x < 20)``), computed on the device copy of the matrix.
 
     ``obs``: ``n_genes_by_counts``, ``total_counts``; ``var``: ``n_cells_by_counts``, ``mean_counts``,
     ``pct_dropout_by_counts``, ``total_counts``; with ``log1p`` also ``log1p_n_genes_by_counts``,
     ``log1p_total_counts`` and ``log1p_mean_counts``.  ``inplace=False`` returns the two DataFrames instead.
 
+    percent_top
+            Values of n: ``obs`` gets ``pct_counts_in_top_{n}_genes`` = 100 * (sum of the n largest stored values of the
+            row) / ``total_counts`` for each n of ``sorted(percent_top)``.  Default None: no such column.  scanpy's own
+            default ``(50, 100, 200, 500)`` is deliberately NOT taken over - every existing call returns what it
+            returned before.  An n below 1 or above ``n_vars`` raises ``IndexError("Positions outside range of
+            features.")`` (scanpy's check, quoted from memory).
+    qc_vars
+            A name or a sequence of names of boolean columns of ``.var`` (``rna.var["mt"]``); anything else raises
+            ``ValueError`` naming the column.  For each q, after the percent_top columns: ``total_counts_{q}``,
+            ``log1p_total_counts_{q}`` (with ``log1p``) and ``pct_counts_{q}`` = 100 * ``total_counts_{q}`` /
+            ``total_counts``.
+    A row whose total is zero gets NaN (0 / 0) in every pct column, as in scanpy.  scanpy is not installed where this
+    package is tested: parity with scanpy itself is not pinned, the columns are pinned against their NumPy statements
+    (tests/qc_refs.py).
+
     One deliberate difference from scanpy, which counts with ``getnnz``: an explicitly stored zero is NOT counted as a
     detected feature / cell (NaN is).  Totals are f64 whatever the matrix's dtype.
 
     A sparse matrix is swept where it is resident; otherwise it is uploaded once and the copy stays attached, so the
-    ``filter_*`` / ``tfidf`` / ``lsi`` calls that follow start from it.  With ``comm`` every rank holds a row shard, as
-    in ``tfidf``: the per-feature counts and sums are summed over the ranks and ``n_obs`` is the global count.
-    ``percent_top`` and ``qc_vars`` are not implemented.
+    ``filter_*`` / ``tfidf`` / ``lsi`` calls that follow start from it.  The two new quantities are one kernel each over
+    the resident CSR (csrc/qc.hip: a masked sum per qc variable in one read of the row, a radix select for all n at
+    once); the top sums look at the stored entries only, which on count matrices is the dense answer.  A dense matrix
+    uses tensor operations (``topk``, masked ``sum``).  With ``comm`` every rank holds a row shard, as in ``tfidf``:
+    the per-feature counts and sums are summed over the ranks and ``n_obs`` is the global count; the new columns are
+    per row of the rank's shard, nothing more is communicated.
     """
     import pandas as pd
 
     adata = modality(data, "atac")
     comm = default_comm(comm)
     counts = adata.X if layer is None else adata.layers[layer]
+    q_names, masks = _qc_vars_masks(adata, qc_vars)
+    ns = _percent_top_list(percent_top, adata.shape[1])
+    masked = top = None
     if issparse(counts):
         _host, X, backend = device_copy(counts, backend)
         row_nnz, rowsum, col_nnz, colsum = qc_device(backend, X, comm)
+        if q_names or ns:
+            masked, top = qc_row_sums_device(backend, X, masks, ns)
     else:
         backend = backend_or_default(backend)
         t = backend.to_device(np.asarray(counts)).to(torch.float64)
@@ -980,6 +1100,11 @@ def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p
             comm.all_reduce_sum(cnt, colsum)
         row_nnz, rowsum, col_nnz, colsum = (backend.to_host(x) for x in (nz.sum(dim=1).to(torch.int64), t.sum(dim=1),
                                                                          cnt.to(torch.int64), colsum))
+        if q_names:
+            masked = np.stack([backend.to_host(t[:, torch.as_tensor(m, device=t.device)].sum(dim=1)) for m in masks], axis=1)
+        if ns:
+            best = torch.cumsum(torch.topk(t, ns[-1], dim=1).values, dim=1)
+            top = backend.to_host(best[:, torch.as_tensor([v - 1 for v in ns], device=t.device)])
     n_obs = float(comm.sum_scalar(adata.shape[0]))
 
     obs = pd.DataFrame(index=adata.obs_names)
@@ -989,6 +1114,14 @@ def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p
     obs["total_counts"] = rowsum
     if log1p:
         obs["log1p_total_counts"] = np.log1p(rowsum)
+    with np.errstate(divide="ignore", invalid="ignore"):  # (a row without counts: 0 / 0 = NaN, as scanpy leaves it)
+        for j, n in enumerate(ns):
+            obs[f"pct_counts_in_top_{n}_genes"] = 100.0 * top[:, j] / rowsum
+        for j, q in enumerate(q_names):
+            obs[f"total_counts_{q}"] = masked[:, j]
+            if log1p:
+                obs[f"log1p_total_counts_{q}"] = np.log1p(masked[:, j])
+            obs[f"pct_counts_{q}"] = 100.0 * masked[:, j] / rowsum
     var = pd.DataFrame(index=adata.var_names)
     var["n_cells_by_counts"] = col_nnz.astype(np.int64)
     var["mean_counts"] = colsum / n_obs
@@ -1004,3 +1137,56 @@ def qc_metrics(data, *, layer: Optional[str] = None, inplace: bool = True, log1p
         adata.obs[c] = obs[c].values
     for c in var.columns:
         adata.var[c] = var[c].values
+
+
+def intersect_obs(mdata, *, backend=None) -> None:
+    """
+    Subset observations (samples or cells) in-place, taking the observations present in all modalities
+    (reference _core/preproc.py:646-669): the common ``obs_names`` of the modalities, ``filter_obs`` on each modality -
+    every modality keeps its own order - and ``mdata.update_obs()``.
+
+    A modality whose matrix carries a device copy keeps one (``filter_obs`` subsets it on the device), so ``tfidf`` /
+    ``tl.pca`` after it start without an upload.  A modality that already holds exactly the common cells is left
+    untouched: no submatrix launch, the same device copy object.
+    """
+    import warnings
+    from functools import reduce
+
+    if getattr(mdata, "isbacked", False):
+        warnings.warn("MuData object is backed. It might be required to re-read the object with `backed=False` to make "
+                      "the intersection work.")
+    common_obs = reduce(np.intersect1d, [m.obs_names for m in mdata.mod.values()])
+    for mod in mdata.mod.values():
+        if len(common_obs) == mod.n_obs and bool(mod.obs_names.isin(common_obs).all()):
+            continue
+        filter_obs(mod, common_obs, backend=backend)
+    mdata.update_obs()
+
+
+def sample_obs(data, frac: float = 0.1, groupby: Optional[str] = None, min_n: Optional[int] = None):
+    """
+    Return an object with some of the observations (subsampling; reference _core/preproc.py:887-931): ``frac`` of them,
+    at least ``min_n``; with ``groupby`` (a categorical column of .obs) per category, in the categories' order.
+
+    The draws are the reference's ``np.random.choice(..., replace=False)`` calls in the reference's order, so under one
+    ``np.random.seed`` the same cells are drawn.  Returns ``data[...]``, a view.  Host only: the view is a new object
+    and carries no device copy.
+    """
+    pick = (lambda idx: data[idx]) if is_anndata(data) else (lambda idx: data[data.obs_names.values[idx]])
+    if groupby is None:
+        new_n = np.ceil(data.n_obs * frac).astype(int)
+        if min_n is not None and new_n < min_n:
+            new_n = min_n
+        return pick(np.random.choice(np.arange(data.n_obs), size=new_n, replace=False))
+    if groupby not in data.obs:
+        raise ValueError(f"{groupby} is not in .obs")
+    if data.obs[groupby].dtype != "category":
+        raise TypeError(f".obs['{groupby}'] is not categorical")
+    chosen = []
+    for cat in data.obs[groupby].cat.categories:
+        names = data.obs_names.values[np.asarray(data.obs[groupby] == cat)]
+        new_n = np.ceil(len(names) * frac).astype(int)
+        if min_n is not None and new_n < min_n:
+            new_n = min_n
+        chosen.append(np.random.choice(names, size=new_n, replace=False))
+    return data[np.concatenate(chosen)]

@@ -30,6 +30,8 @@ class OperatorSet:
     can_emit_stream = stream_layout = None
     # QC metrics and filtering (filter.hip)
     csr_qc = csr_submatrix = None
+    # per-row sums of qc_metrics' qc_vars / percent_top (qc.hip)
+    row_masked_sums = row_top_sums = None
     # fragment tools (fragments.hip)
     frag_ranges = frag_overlap = frag_pileup = frag_pileup_scan = frag_length_classes = None
     # transposition and row streams (transpose.hip, tpack4.hip, tperm.hip, tflat.hip, spmm_win.hip); behind can_stream: stream,

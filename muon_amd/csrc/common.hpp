@@ -188,6 +188,12 @@ static_assert(by_width<64, 128, 256, 512, 1024>(0, self) == 64 && by_width<64, 1
               by_width<64, 128, 256, 512, 1024>(257, self) == 512 && by_width<64, 128, 256, 512, 1024>(512, self) == 512 &&
               by_width<64, 128, 256, 512, 1024>(513, self) == 1024 && by_width<64, 128, 256, 512, 1024>(1024, self) == 1024 &&
               by_width<64, 128, 256, 512, 1024>(1025, self) == 1024);
+static_assert(by_width<1, 8, 32>(0, self) == 1 && by_width<1, 8, 32>(1, self) == 1 && by_width<1, 8, 32>(2, self) == 8 &&
+              by_width<1, 8, 32>(8, self) == 8 && by_width<1, 8, 32>(9, self) == 32 && by_width<1, 8, 32>(32, self) == 32 &&
+              by_width<1, 8, 32>(33, self) == 32);
+static_assert(by_width<1, 2, 4, 8>(0, self) == 1 && by_width<1, 2, 4, 8>(1, self) == 1 && by_width<1, 2, 4, 8>(2, self) == 2 &&
+              by_width<1, 2, 4, 8>(3, self) == 4 && by_width<1, 2, 4, 8>(4, self) == 4 && by_width<1, 2, 4, 8>(5, self) == 8 &&
+              by_width<1, 2, 4, 8>(8, self) == 8 && by_width<1, 2, 4, 8>(9, self) == 8);
 static_assert(by_index<2>(false, self) == 0 && by_index<2>(true, self) == 1 && by_index<2>(-1, self) == 1 &&
               by_index<2>(7, self) == 1);
 static_assert(by_index<3>(0, self) == 0 && by_index<3>(1, self) == 1 && by_index<3>(2, self) == 2 &&
