@@ -1005,6 +1005,50 @@ int mu_csr_row_masked_sums(int dtype, int64_t n_rows, int64_t n_cols, int64_t nn
 int mu_csr_row_top_sums(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* d_indptr,
                         const void* d_values, int n_tops, const int64_t* h_ns, double* d_out, void* stream);
 
+/* ---- muon_amd.pp.harmony_integrate: the cell-long steps of Harmony's k-means rounds (csrc/harmony.hip, C-ABI v816;
+ * the statement is muon_amd/_core/harmony.py and DESIGN.md 9.17) ---------------------------------------------------------
+ * All arithmetic f64 on the matrix cores.  1 <= K <= mu_harmony_max_clusters() = 128, 1 <= d <= mu_harmony_max_dims() =
+ * 64, 1 <= B, n_seg <= mu_harmony_max_levels() = 64; kp and dp are K and d rounded up to a multiple of 16.  d_idx is an
+ * optional int64 list of row numbers (NULL: the rows are 0, 1, ...); a row number outside [0, n) contributes nothing and
+ * is not written, a level code outside [0, B) is clamped: no address leaves the operands whatever the arrays hold.  No
+ * float atomics: two calls agree byte for byte.  Arguments are checked before any HIP call.
+ *   mu_harmony_gram_f64: d_out[s] = R_s^T Z_s, row-major [n_seg][kp][dp], over the rows d_idx[h_seg_ptr[s]] ..
+ *     d_idx[h_seg_ptr[s + 1] - 1] (without d_idx: the rows h_seg_ptr[s] .. h_seg_ptr[s + 1] - 1) of d_R [n][ldr >= K]
+ *     and d_Z [n][ldz >= d].  h_seg_ptr is a HOST array of n_seg + 1 offsets into the m entries of the list, ascending
+ *     within [0, m]; an empty segment gives zeros.  Columns of R at or past K and of Z at or past d are masked by index
+ *     (NaN there does no harm); the padding of d_out is zero.  Partial sums go to ceil(rows / 64) slots per segment, at
+ *     most 512 / n_seg, in d_work (mu_harmony_gram_worksize bytes); a second kernel adds them in slot order.
+ *   mu_harmony_assign_f64: for the nb cells c = d_idx[0 .. nb) with g = d_codes[c]:
+ *       D_k = 2 (1 - Zc_c . Y_k);  t_k = -D_k / sigma_k;  w_k = exp(t_k - max_k t_k) * F[k][g];  R[c][k] = w_k / sum_k w_k
+ *     for k < K and R[c][k] = 0 for K <= k < kp (ldr >= kp); no contraction.  d_Zc [n][ldz >= d], d_Y [K][d], d_sigma
+ *     [K], d_F [K][B] row-major, d_codes int32 [n].  Rows of d_R that the list does not name are not touched.
+ *   mu_harmony_objective_f64: d_out[0 .. 2] = the three terms of the objective over all n cells c and k < K, with r =
+ *     R[c][k], D as above and g = d_codes[c]:  sum r D,  sum sigma_k r log r (0 log 0 := 0),  sum sigma_k r G[k][g]; d_G
+ *     [K][B] row-major, d_R [n][ldr >= K] (columns at or past K are masked by index), one read of R.  Every workgroup
+ *     (min(ceil(n / 64), 512): a function of n) leaves three partial sums in d_work (mu_harmony_objective_worksize
+ *     bytes), a second kernel adds them in order; no contraction.
+ *   mu_harmony_correct_f64: the cells are sorted by level, level g owns the rows h_seg_ptr[g] .. h_seg_ptr[g + 1] - 1
+ *     (a HOST array of B + 1 ascending offsets from 0 to n).  d_Zcorr[c] = d_Z[c] - R[c][:K] W[g] with d_W [B][K][d]
+ *     row-major, and d_Zc[c] = d_Zcorr[c] / |d_Zcorr[c]|_2, in one pass; both outputs [n][ldo >= d], columns at or past d
+ *     are not written. */
+int mu_harmony_max_clusters(void);
+int mu_harmony_max_dims(void);
+int mu_harmony_max_levels(void);
+size_t mu_harmony_gram_worksize(int64_t m, int n_seg, int K, int d);
+int mu_harmony_gram_f64(int64_t n, int64_t m, int K, int d, const double* d_R, int64_t ldr, const double* d_Z,
+                        int64_t ldz, const int64_t* d_idx, int n_seg, const int64_t* h_seg_ptr, double* d_out,
+                        void* d_work, size_t work_bytes, void* stream);
+int mu_harmony_assign_f64(int64_t n, int K, int d, int B, int64_t nb, const double* d_Zc, int64_t ldz,
+                          const double* d_Y, const double* d_sigma, const double* d_F, const int32_t* d_codes,
+                          const int64_t* d_idx, double* d_R, int64_t ldr, void* stream);
+size_t mu_harmony_objective_worksize(int64_t n);
+int mu_harmony_objective_f64(int64_t n, int K, int d, int B, const double* d_Zc, int64_t ldz, const double* d_Y,
+                             const double* d_R, int64_t ldr, const double* d_sigma, const double* d_G,
+                             const int32_t* d_codes, double* d_out, void* d_work, size_t work_bytes, void* stream);
+int mu_harmony_correct_f64(int64_t n, int K, int d, int B, const double* d_Z, int64_t ldz, const double* d_R,
+                           int64_t ldr, const double* d_W, const int64_t* h_seg_ptr, double* d_Zcorr, double* d_Zc,
+                           int64_t ldo, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -18,6 +18,8 @@ Drop-in namespaces for the three hot-path entry points of the reference
                              tools: gene-activity counts and the two QC columns, over a fragment table on the device;
                              atac.tl.locate_fragments reads the TSV, atac.tl.fragments_from_arrays takes its columns)
     muon_amd.tl.ica          <->  muon.tl.ica         (FastICA of X_pca / X_lsi / X_mofa: one fused sweep per iteration)
+    muon_amd.pp.harmony_integrate  <->  scanpy.external.pp.harmony_integrate  (Harmony batch correction of X_pca / X_lsi:
+                             the k-means rounds and the correction on f64 matrix-core kernels; the package's own statement)
     muon_amd.tl.snf          <->  muon.tl.snf         (similarity network fusion: P S P^T as two sparse-dense passes)
     muon_amd.atac.tl.rank_peaks_groups  <->  muon.atac.tl.rank_peaks_groups  (scanpy's rank_genes_groups on the device
                              copy of the peak matrix, then add_genes_peaks_groups; atac.tl.add_peak_annotation alike)

@@ -1620,6 +1620,123 @@ class HipBackend(OperatorSet):
                      int(max_blocks))
         return A, gp
 
+    # -- muon_amd.pp.harmony_integrate (csrc/harmony.hip) --------------------------------------------------------------
+    def harmony_limits(self) -> dict:
+        """The most clusters, basis columns and levels (= segments of a gram) the kernels take; everything else is the
+        tensor formulation."""
+        return {"clusters": int(self.lib.mu_harmony_max_clusters()), "dims": int(self.lib.mu_harmony_max_dims()),
+                "levels": int(self.lib.mu_harmony_max_levels())}
+
+    @staticmethod
+    def _harmony_idx(idx, n: int, checked: bool):
+        """The optional int64 list of row numbers; unless the caller has ``checked`` it, it is checked here, on the
+        host, before any launch."""
+        if idx is None:
+            return None
+        if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+            raise TypeError("idx: a contiguous int64 tensor of row numbers")
+        if not checked and int(idx.numel()) and not (0 <= int(idx.min()) and int(idx.max()) < n):
+            raise IndexError(f"idx: a row number outside [0, {n})")
+        return idx
+
+    def harmony_gram(self, R, Z, seg_ptr, K: Optional[int] = None, idx=None, checked: bool = False):
+        """``out[s] = R_s[:, :K]^T Z_s`` for every row segment (include/muon_amd.h): f64 [n_seg, kp, dp], kp and dp K
+        and Z's width rounded up to 16, the padding zero.  ``seg_ptr``: HOST offsets (a sequence of n_seg + 1 ascending
+        ints) into the rows, or into ``idx`` (int64 row numbers on the device) where given.  R [n, >= K] and Z [n, d]
+        f64 with unit column stride; columns of R at or past K are masked by index.  Two calls agree byte for byte."""
+        f64 = torch.float64
+        if R.dtype != f64 or Z.dtype != f64 or R.dim() != 2 or Z.dim() != 2 or int(R.shape[0]) != int(Z.shape[0]):
+            raise TypeError("R [n, >= K] and Z [n, d]: float64 tensors with the same number of rows")
+        n, d = int(Z.shape[0]), int(Z.shape[1])
+        K = int(R.shape[1]) if K is None else int(K)
+        if (n > 1 and (R.stride(1) != 1 or Z.stride(1) != 1)) or K > int(R.shape[1]):
+            raise TypeError("R and Z: unit column stride, K columns of R at the least")
+        idx = self._harmony_idx(idx, n, checked)
+        m = n if idx is None else int(idx.numel())
+        seg = [int(v) for v in seg_ptr]
+        n_seg = len(seg) - 1
+        lim = self.harmony_limits()
+        inside = 1 <= K <= lim["clusters"] and 1 <= d <= lim["dims"] and 1 <= n_seg <= lim["levels"]
+        h_seg = (ctypes.c_int64 * max(len(seg), 1))(*seg)
+        kp, dp = (K + 15) // 16 * 16, (d + 15) // 16 * 16
+        out = self.empty((max(n_seg, 0), kp, dp), f64)
+        work, wb = self._work(self.lib.mu_harmony_gram_worksize(m, n_seg, K, d) if inside else 0, floor=8)
+        ldr = int(R.stride(0)) if n > 1 else int(R.shape[1])
+        ldz = int(Z.stride(0)) if n > 1 else d
+        self._launch(self.lib.mu_harmony_gram_f64, n, m, K, d, R, ldr, Z, ldz, idx, n_seg, h_seg, out, work, wb)
+        return out
+
+    def harmony_assign(self, Zc, Y, sigma, F, codes, R, idx=None, checked: bool = False) -> None:
+        """The soft assignment of the cells ``idx`` (None: all), IN PLACE in R [n, >= kp] (include/muon_amd.h):
+        ``R[c, :K] = rownormalise_L1(exp(-D / sigma - rowmax) * F[:, codes[c]])`` with ``D = 2 (1 - Zc Y^T)``, the columns
+        K .. kp - 1 zero, every other row untouched.  Zc [n, d], Y [K, d], sigma [K], F [K, B] f64; codes int32 [n]."""
+        f64 = torch.float64
+        for t in (Zc, Y, sigma, F, R):
+            if t.dtype != f64:
+                raise TypeError("Zc, Y, sigma, F and R: float64 tensors")
+        n, d, K = int(Zc.shape[0]), int(Zc.shape[1]), int(Y.shape[0])
+        if (tuple(Y.shape) != (K, d) or tuple(sigma.shape) != (K,) or F.dim() != 2 or int(F.shape[0]) != K
+                or not (Y.is_contiguous() and sigma.is_contiguous() and F.is_contiguous())):
+            raise TypeError("Y [K, d], sigma [K] and F [K, B]: contiguous")
+        if codes.dtype != torch.int32 or tuple(codes.shape) != (n,) or not codes.is_contiguous():
+            raise TypeError("codes: a contiguous int32 tensor, one level per cell")
+        if R.dim() != 2 or int(R.shape[0]) != n or (n > 1 and (R.stride(1) != 1 or Zc.stride(1) != 1)):
+            raise TypeError("R [n, >= K rounded up to 16] and Zc [n, d]: unit column stride")
+        B = int(F.shape[1])
+        idx = self._harmony_idx(idx, n, checked)
+        nb = n if idx is None else int(idx.numel())
+        ldr = int(R.stride(0)) if n > 1 else int(R.shape[1])
+        if int(R.shape[1]) < (K + 15) // 16 * 16:
+            ldr = int(R.shape[1])  # (narrower than the padded width: the library refuses it by its ldr)
+        ldz = int(Zc.stride(0)) if n > 1 else d
+        self._launch(self.lib.mu_harmony_assign_f64, n, K, d, B, nb, Zc, ldz, Y, sigma, F, codes, idx, R, ldr)
+
+    def harmony_objective(self, Zc, Y, R, sigma, G, codes):
+        """The three terms of Harmony's objective (include/muon_amd.h) as an f64 tensor [3]: ``sum(R D)``,
+        ``sum(sigma_k R log R)`` with 0 log 0 = 0 and ``sum(sigma_k R_ik G[k, codes[i]])``, ``D = 2 (1 - Zc Y^T)``, over
+        the first K = Y's rows columns of R [n, >= K]; one read of R.  Two calls agree byte for byte."""
+        f64 = torch.float64
+        for t in (Zc, Y, R, sigma, G):
+            if t.dtype != f64:
+                raise TypeError("Zc, Y, R, sigma and G: float64 tensors")
+        n, d, K = int(Zc.shape[0]), int(Zc.shape[1]), int(Y.shape[0])
+        if (tuple(Y.shape) != (K, d) or tuple(sigma.shape) != (K,) or G.dim() != 2 or int(G.shape[0]) != K
+                or not (Y.is_contiguous() and sigma.is_contiguous() and G.is_contiguous())):
+            raise TypeError("Y [K, d], sigma [K] and G [K, B]: contiguous")
+        if codes.dtype != torch.int32 or tuple(codes.shape) != (n,) or not codes.is_contiguous():
+            raise TypeError("codes: a contiguous int32 tensor, one level per cell")
+        if R.dim() != 2 or int(R.shape[0]) != n or int(R.shape[1]) < K or (n > 1 and (R.stride(1) != 1 or Zc.stride(1) != 1)):
+            raise TypeError("R [n, >= K] and Zc [n, d]: unit column stride")
+        out = self.empty((3,), f64)
+        work, wb = self._work(self.lib.mu_harmony_objective_worksize(n), floor=8)
+        ldr = int(R.stride(0)) if n > 1 else int(R.shape[1])
+        ldz = int(Zc.stride(0)) if n > 1 else d
+        self._launch(self.lib.mu_harmony_objective_f64, n, K, d, int(G.shape[1]), Zc, ldz, Y, R, ldr, sigma, G, codes, out,
+                     work, wb)
+        return out
+
+    def harmony_correct(self, Z, R, W, seg_ptr):
+        """Harmony's correction for cells sorted by level (include/muon_amd.h): returns ``(Zcorr, Zc)`` [n, d] f64 with
+        ``Zcorr[c] = Z[c] - R[c, :K] @ W[g]`` for the cells c of level g, rows ``seg_ptr[g] .. seg_ptr[g + 1] - 1`` (HOST
+        offsets, B + 1 ascending ints from 0 to n), and ``Zc`` its rows divided by their 2-norms.  W [B, K, d]."""
+        f64 = torch.float64
+        if Z.dtype != f64 or R.dtype != f64 or W.dtype != f64 or Z.dim() != 2 or R.dim() != 2 or W.dim() != 3:
+            raise TypeError("Z [n, d], R [n, >= K] and W [B, K, d]: float64 tensors")
+        n, d = int(Z.shape[0]), int(Z.shape[1])
+        B, K = int(W.shape[0]), int(W.shape[1])
+        if (int(W.shape[2]) != d or not W.is_contiguous() or int(R.shape[0]) != n or int(R.shape[1]) < K
+                or (n > 1 and (R.stride(1) != 1 or Z.stride(1) != 1))):
+            raise TypeError("W [B, K, d] contiguous; R and Z: n rows, unit column stride, K columns of R at the least")
+        seg = [int(v) for v in seg_ptr]
+        if len(seg) != B + 1:
+            raise ValueError(f"seg_ptr: {B + 1} offsets for {B} levels, got {len(seg)}")
+        h_seg = (ctypes.c_int64 * (B + 1))(*seg)
+        Zcorr, Zc = self.empty((n, d), f64), self.empty((n, d), f64)
+        ldr = int(R.stride(0)) if n > 1 else int(R.shape[1])
+        ldz = int(Z.stride(0)) if n > 1 else d
+        self._launch(self.lib.mu_harmony_correct_f64, n, K, d, B, Z, ldz, R, ldr, W, h_seg, Zcorr, Zc, d)
+        return Zcorr, Zc
+
     # -- muon.atac.pp.scopen (csrc/nmf.hip) ----------------------------------------------------------------------------
     def nmf_max_components(self) -> int:
         """The most components the fused coordinate-descent sweep takes (more: the tensor formulation)."""

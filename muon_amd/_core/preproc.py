@@ -33,6 +33,7 @@ from .._comm import default_comm
 from .._containers import is_anndata, is_mudata, modality
 from .._hostmatrix import attach_device, device_copy, resident_copy
 from .._operators import has
+from .harmony import harmony_integrate  # noqa: F401  (muon_amd.pp.harmony_integrate)
 
 _METRICS = ("euclidean", "sqeuclidean", "cosine", "cityblock", "manhattan", "chebyshev")
 

@@ -77,6 +77,8 @@ class OperatorSet:
     scale_values = scale_dense_rows = None
     # muon.atac.tl.scan_sequences (motif.hip): behind motif_scan
     motif_max_len = motif_tile = motif_group = motif_room = motif_scan = None
+    # muon_amd.pp.harmony_integrate (harmony.hip): asked for together
+    harmony_limits = harmony_gram = harmony_assign = harmony_objective = harmony_correct = None
     # synthetic counts of the benchmark and the tests (synth.hip)
     synth_counts = None
 

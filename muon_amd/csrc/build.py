@@ -11,7 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["runtime.hip", "tfidf.hip", "transpose.hip", "spmm.hip", "spmm_win.hip", "spmm_narrow.hip", "spmm_ell.hip", "tpack4.hip", "tperm.hip", "tflat.hip", "dense.hip", "skinny.hip", "synth.hip", "mofa.hip", "mofa_elbo.hip", "mofa_stats.hip", "mofa_poisson.hip", "mofa_bernoulli.hip", "knn.hip", "wnn.hip", "prot.hip", "filter.hip", "fragments.hip", "ica.hip", "rank.hip", "snf.hip", "motif.hip", "cluster.hip", "umap.hip", "nmf.hip", "rna.hip", "gp.hip", "scale.hip", "qc.hip"]
+SOURCES = ["runtime.hip", "tfidf.hip", "transpose.hip", "spmm.hip", "spmm_win.hip", "spmm_narrow.hip", "spmm_ell.hip", "tpack4.hip", "tperm.hip", "tflat.hip", "dense.hip", "skinny.hip", "synth.hip", "mofa.hip", "mofa_elbo.hip", "mofa_stats.hip", "mofa_poisson.hip", "mofa_bernoulli.hip", "knn.hip", "wnn.hip", "prot.hip", "filter.hip", "fragments.hip", "ica.hip", "rank.hip", "snf.hip", "motif.hip", "cluster.hip", "umap.hip", "nmf.hip", "rna.hip", "gp.hip", "scale.hip", "qc.hip", "harmony.hip"]
 HEADERS = ["common.hpp", "sweep.hpp", os.path.join(ROOT, "include", "muon_amd.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in VGPRs.  The default (AGPR form) kept the accumulators of these files'
 # loops in VGPRs BETWEEN the steps and copied them to AGPRs and back around the MFMAs of every step (k_skinny_tn: 64
@@ -32,7 +32,10 @@ EXTRA = {"skinny.hip": _VGPR_FORM, "dense.hip": _VGPR_FORM, "knn.hip": _VGPR_FOR
          # scale.hip: (x - mean) / std, the clip and one rounding are bit-equal to the NumPy statement: no contraction
          "scale.hip": ["-ffp-contract=off"],
          # qc.hip: sum(v > t) + (n - count) * t as the header states it: the product is rounded before the sum
-         "qc.hip": ["-ffp-contract=off"]}
+         "qc.hip": ["-ffp-contract=off"],
+         # harmony.hip: the exponent -D / sigma - max and the weight exp(.) * F are the statement's roundings (with exact
+         # distances the kernel's weights are the NumPy statement's up to libm's exp); accumulators in VGPRs as in ica.hip
+         "harmony.hip": ["-ffp-contract=off"] + _VGPR_FORM}
 LIB = os.path.join(HERE, "libmuon_amd.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
