@@ -1049,6 +1049,31 @@ int mu_harmony_correct_f64(int64_t n, int K, int d, int B, const double* d_Z, in
                            int64_t ldr, const double* d_W, const int64_t* h_seg_ptr, double* d_Zcorr, double* d_Zc,
                            int64_t ldo, void* stream);
 
+/* ---- muon_amd.pp.scrublet: synthetic doublets and the merge of a search with a large k (csrc/scrublet.hip, C-ABI v817;
+ * the statement is muon_amd/_core/scrublet.py and DESIGN.md 9.18) ----------------------------------------------------------
+ * Simulated row s is the sum of the rows d_parents[2 s] and d_parents[2 s + 1] (int64 [n_sim][2]) of a CANONICAL CSR
+ * (columns ascending, no duplicates; int64 row pointers, f32 values, indices of index_bytes = 4 or 8 bytes): every
+ * column stored in either parent is a stored entry of the result (explicit zeros included, nothing pruned), columns
+ * ascending, a column stored in both carries the f32 sum, every other entry its value bit for bit; a pair (a, a) gives
+ * the row doubled.  A parent outside [0, n_rows) gives an empty row.
+ *   1. mu_csr_pair_rows_count: d_new_row_nnz[s] = len(a) + len(b) - (columns stored in both)
+ *   2. the caller scans it into new_indptr (mu_exclusive_scan_i64) and allocates new_indices / new_values
+ *   3. mu_csr_pair_rows_fill: the entries, each at a slot computed in closed form; a row never writes outside
+ *      new_indptr[s] .. new_indptr[s + 1].  One wave per simulated row, no atomics, no row-length limit: two calls agree
+ *      byte for byte. */
+int mu_csr_pair_rows_count(int index_bytes, int64_t n_rows, int64_t n_sim, const int64_t* d_indptr,
+                           const void* d_indices, const int64_t* d_parents, int64_t* d_new_row_nnz, void* stream);
+int mu_csr_pair_rows_fill(int index_bytes, int64_t n_rows, int64_t n_sim, const int64_t* d_indptr, const void* d_indices,
+                          const float* d_values, const int64_t* d_parents, const int64_t* d_new_indptr,
+                          void* d_new_indices, float* d_new_values, void* stream);
+/* mu_knn_merge_f64's contract for kc + cap <= mu_knn_merge_wide_max() = 8192 (callable below 1024 too): one workgroup
+ * per query, the pairs sorted in LDS by (distance, position) - the same total order, so both merges return identical
+ * arrays at every shape both accept.  cnt[q] is clamped to [0, cap] and not written; not in place. */
+int mu_knn_merge_wide_max(void);
+int mu_knn_merge_wide_f64(int64_t n_q, int kc, int cap, const double* d_cur_d, const int64_t* d_cur_p,
+                          const double* d_buf_d, const int32_t* d_buf_pos, const int32_t* d_cnt, double* d_out_d,
+                          int64_t* d_out_p, double* d_thr, void* stream);
+
 /* ---- synthetic planted-topic counts (bench / tests only) ------ */
 /* Pass 1: nnz of every row for rows [row0, row0+n_rows) of the global matrix.
  * Pass 2 (after scanning the counts into indptr): fills indices / values (f32 counts).*/

@@ -20,7 +20,11 @@ Drop-in namespaces for the three hot-path entry points of the reference
     muon_amd.tl.ica          <->  muon.tl.ica         (FastICA of X_pca / X_lsi / X_mofa: one fused sweep per iteration)
     muon_amd.pp.harmony_integrate  <->  scanpy.external.pp.harmony_integrate  (Harmony batch correction of X_pca / X_lsi:
                              the k-means rounds and the correction on f64 matrix-core kernels; the package's own statement)
-    muon_amd.tl.snf          <->  muon.tl.snf         (similarity network fusion: P S P^T as two sparse-dense passes)
+    muon_amd.pp.scrublet / scrublet_simulate_doublets  <->  scanpy.pp.scrublet / scrublet_simulate_doublets  (doublet
+                             detection on the resident raw counts, before normalize_total: a sparse row-pair merge, the
+                             projection of the simulated rows as one SpMM, a search with k in the hundreds whose per-panel
+                             merge is a workgroup-wide sort; the package's own statement, parity with scanpy not pinned)
+    muon_amd.tl.snf          <->  muon.tl.snf        (similarity network fusion: P S P^T as two sparse-dense passes)
     muon_amd.atac.tl.rank_peaks_groups  <->  muon.atac.tl.rank_peaks_groups  (scanpy's rank_genes_groups on the device
                              copy of the peak matrix, then add_genes_peaks_groups; atac.tl.add_peak_annotation alike)
     muon_amd.atac.tl.scan_sequences  <->  muon.atac.tl.scan_sequences  (every window of every peak sequence against a

@@ -1542,6 +1542,44 @@ class HipBackend(OperatorSet):
                      out_d, out_p, thr)
         return out_d, out_p, thr
 
+    def knn_merge_wide_max(self) -> int:
+        """The largest kc + cap ``knn_merge_wide`` takes."""
+        return int(self.lib.mu_knn_merge_wide_max())
+
+    def knn_merge_wide(self, cur_d, cur_p, buf_d, buf_pos, cnt):
+        """``knn_merge`` for kc + cap up to ``knn_merge_wide_max()``: a workgroup per query (csrc/scrublet.hip,
+        include/muon_amd.h mu_knn_merge_wide_f64); identical arrays where both take the shape."""
+        n, kc = cur_d.shape
+        out_d, out_p = torch.empty_like(cur_d), torch.empty_like(cur_p)
+        thr = self.empty((n,), torch.float64)
+        self._launch(self.lib.mu_knn_merge_wide_f64, int(n), int(kc), int(buf_d.shape[1]), cur_d, cur_p, buf_d, buf_pos,
+                     cnt, out_d, out_p, thr)
+        return out_d, out_p, thr
+
+    def csr_pair_rows(self, X: DeviceCSR, parents: torch.Tensor) -> DeviceCSR:
+        """Row s of the result = row parents[s, 0] + row parents[s, 1] of the canonical device CSR ``X`` (f32 values;
+        indices int32, or int64 and then the result's are too; ``parents`` int64 [n_sim, 2] on the device): the union
+        of the two patterns, columns ascending, nothing pruned, the f32 sum where both store the column
+        (csrc/scrublet.hip).  Index arrays of its own, so none of X's derived tables."""
+        n, d = X.shape
+        if (parents.dtype != torch.int64 or parents.dim() != 2 or parents.shape[1] != 2
+                or X.values.dtype != torch.float32 or X.indices.dtype not in (torch.int32, torch.int64)):
+            raise TypeError("csr_pair_rows: f32 values, int32 or int64 indices, parents int64 [n_sim, 2]")
+        parents = parents.contiguous()
+        k = int(parents.shape[0])
+        ib = 8 if X.indices.dtype == torch.int64 else 4
+        row_nnz = self.empty((k,), torch.int64)
+        new_indptr = self.zeros((k + 1,), torch.int64)
+        self._launch(self.lib.mu_csr_pair_rows_count, ib, n, k, X.indptr, X.indices, parents, row_nnz)
+        if k:
+            self._launch(self.lib.mu_exclusive_scan_i64, k, row_nnz, new_indptr)
+        new_nnz = int(new_indptr[-1].item())
+        new_indices = self.empty((new_nnz,), X.indices.dtype)
+        new_values = self.empty((new_nnz,), torch.float32)
+        self._launch(self.lib.mu_csr_pair_rows_fill, ib, n, k, X.indptr, X.indices, X.values, parents, new_indptr,
+                     new_indices, new_values)
+        return DeviceCSR(new_indptr, new_indices, new_values, (k, int(d)))
+
     def densify_rows(self, X: DeviceCSR, lo: int, hi: int) -> torch.Tensor:
         """Rows [lo, hi) of a device CSR as a dense chunk (include/muon_amd.h)."""
         out = self.empty((hi - lo, X.shape[1]), X.values.dtype)

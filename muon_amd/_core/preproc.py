@@ -34,6 +34,7 @@ from .._containers import is_anndata, is_mudata, modality
 from .._hostmatrix import attach_device, device_copy, resident_copy
 from .._operators import has
 from .harmony import harmony_integrate  # noqa: F401  (muon_amd.pp.harmony_integrate)
+from .scrublet import scrublet, scrublet_simulate_doublets  # noqa: F401  (muon_amd.pp.scrublet)
 
 _METRICS = ("euclidean", "sqeuclidean", "cosine", "cityblock", "manhattan", "chebyshev")
 
@@ -245,16 +246,26 @@ def _cell_dist(X: torch.Tensor, ri: torch.Tensor, ci: torch.Tensor, ok: torch.Te
     return out
 
 
-def _candidates_filtered(be, Xn: torch.Tensor, sq: torch.Tensor, kc: int, chunk_elems: int, cap: Optional[int] = None) -> torch.Tensor:
+def _candidates_filtered(be, Xn: torch.Tensor, sq: torch.Tensor, kc: int, chunk_elems: int, cap: Optional[int] = None,
+                         queries: Optional[tuple] = None) -> torch.Tensor:
     """kc nearest candidates per row (GEMM-form squared distances) WITHOUT the n x n distance panels: the
     rows are walked as candidates in a random order, in panels of doubling size.  The first panel is searched
     densely and leaves every query its kc-th smallest distance so far as a threshold; for each later panel the
     HIP filter kernel (csrc/knn.hip: distances on the f64 matrix cores, compared in registers) appends the
     candidates that beat the threshold - about kc per query and panel, because a panel doubles what the query
     has seen - and a top-k over [list ++ buffer] (4 kc wide instead of n) updates list and threshold.  A
-    buffer that overflowed (ties, duplicated rows) has its rows redone densely."""
+    buffer that overflowed (ties, duplicated rows) has its rows redone densely.
+
+    ``queries = (lo, hi)``: only the rows lo .. hi - 1 are queries (every row stays a candidate, in the same order
+    whatever the block) and the result has hi - lo rows: the per-query buffers are (hi - lo) x cap x 12 bytes, and a
+    caller with many rows and a large kc (``scrublet``) walks them in blocks.  None: all rows.
+
+    The merge of list and buffer is ``knn_merge`` (a wave per query) where kc + cap <= 1024, ``knn_merge_wide`` (a
+    workgroup per query, csrc/scrublet.hip) up to its limit, else the tensor formulation."""
     n, p = Xn.shape
     dev = Xn.device
+    q_lo, q_hi = (0, n) if queries is None else (int(queries[0]), int(queries[1]))
+    nq = q_hi - q_lo
     p_pad = (p + 3) // 4 * 4
     g = torch.Generator(device=dev)
     g.manual_seed(0)
@@ -266,40 +277,45 @@ def _candidates_filtered(be, Xn: torch.Tensor, sq: torch.Tensor, kc: int, chunk_
     Xc = Xq[perm].contiguous()
     sq = sq.contiguous()
     sqc = sq[perm].contiguous()
-    self_pos = inv.to(torch.int32).contiguous()
-    ar = torch.arange(n, device=dev)
+    ar = torch.arange(q_lo, q_hi, device=dev)  # the queries' row numbers
 
     def dense(rows, c0, c1):
-        """squared distances of `rows` (tensor of row numbers, or None: all) to positions [c0, c1), self = inf"""
-        q = Xq if rows is None else Xq[rows]
-        D = (sq if rows is None else sq[rows])[:, None] + sqc[None, c0:c1] - 2.0 * (q @ Xc[c0:c1].T)
-        sp = inv if rows is None else inv[rows]
+        """squared distances of `rows` (tensor of row numbers) to positions [c0, c1), self = inf"""
+        D = sq[rows][:, None] + sqc[None, c0:c1] - 2.0 * (Xq[rows] @ Xc[c0:c1].T)
+        sp = inv[rows]
         hit = (sp >= c0) & (sp < c1)
         r = torch.nonzero(hit)[:, 0]
         D[r, sp[r] - c0] = float("inf")
         return D
 
     p0 = min(n, max(2048, 4 * kc))
-    cur_d = torch.empty((n, kc), dtype=torch.float64, device=dev)
-    cur_p = torch.empty((n, kc), dtype=torch.int64, device=dev)
-    rows = max(1, min(n, chunk_elems // p0))
-    for lo in range(0, n, rows):
-        hi = min(n, lo + rows)
+    cur_d = torch.empty((nq, kc), dtype=torch.float64, device=dev)
+    cur_p = torch.empty((nq, kc), dtype=torch.int64, device=dev)
+    rows = max(1, min(nq, chunk_elems // p0))
+    for lo in range(0, nq, rows):
+        hi = min(nq, lo + rows)
         t = torch.topk(dense(ar[lo:hi], 0, p0), kc, dim=1, largest=False)
         cur_d[lo:hi], cur_p[lo:hi] = t.values, t.indices
     cap = int(cap) if cap else 3 * kc + 64
-    buf_pos = torch.empty((n, cap), dtype=torch.int32, device=dev)
-    buf_d = torch.empty((n, cap), dtype=torch.float64, device=dev)
-    cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+    Xq_b, sq_b = Xq[q_lo:q_hi], sq[q_lo:q_hi]  # (contiguous row ranges; all rows: the arrays themselves)
+    self_pos = inv[q_lo:q_hi].to(torch.int32).contiguous()
+    buf_pos = torch.empty((nq, cap), dtype=torch.int32, device=dev)
+    buf_d = torch.empty((nq, cap), dtype=torch.float64, device=dev)
+    cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
     slot = torch.arange(cap, device=dev)[None, :]
     c_lo = p0
-    fused = has(be, "knn_merge") and kc + cap <= 1024
+    merge = None
+    if has(be, "knn_merge") and kc + cap <= 1024:
+        merge = be.knn_merge    # a wave per query (csrc/knn.hip)
+    elif has(be, "knn_merge_wide", "knn_merge_wide_max") and kc + cap <= be.knn_merge_wide_max():
+        merge = be.knn_merge_wide  # a workgroup per query (csrc/scrublet.hip)
+    fused = merge is not None
     thr = cur_d.amax(dim=1).contiguous()
     while c_lo < n:
         c_hi = min(n, 2 * c_lo)
-        be.knn_filter(Xq, Xc, sq, sqc, thr, self_pos, c_lo, c_hi, buf_pos, buf_d, cnt)
-        if fused:  # list ++ buffer -> the kc smallest and the new threshold, a wave per query (csrc/knn.hip)
-            new_d, new_p, thr = be.knn_merge(cur_d.contiguous(), cur_p.contiguous(), buf_d, buf_pos, cnt)
+        be.knn_filter(Xq_b, Xc, sq_b, sqc, thr, self_pos, c_lo, c_hi, buf_pos, buf_d, cnt)
+        if fused:  # list ++ buffer -> the kc smallest and the new threshold
+            new_d, new_p, thr = merge(cur_d.contiguous(), cur_p.contiguous(), buf_d, buf_pos, cnt)
         else:
             valid = slot < cnt[:, None]
             d_all = torch.cat([cur_d, torch.where(valid, buf_d, torch.full_like(buf_d, float("inf")))], dim=1)
@@ -310,7 +326,7 @@ def _candidates_filtered(be, Xn: torch.Tensor, sq: torch.Tensor, kc: int, chunk_
         if over.numel():  # (rare) more candidates than the buffer holds: those rows again, densely, over all seen
             for lo in range(0, over.numel(), max(1, chunk_elems // c_hi)):
                 r = over[lo:lo + max(1, chunk_elems // c_hi)]
-                t = torch.topk(dense(r, 0, c_hi), kc, dim=1, largest=False)
+                t = torch.topk(dense(ar[r], 0, c_hi), kc, dim=1, largest=False)
                 new_d[r], new_p[r] = t.values, t.indices
             thr = new_d.amax(dim=1).contiguous()
         elif not fused:

@@ -79,6 +79,9 @@ class OperatorSet:
     motif_max_len = motif_tile = motif_group = motif_room = motif_scan = None
     # muon_amd.pp.harmony_integrate (harmony.hip): asked for together
     harmony_limits = harmony_gram = harmony_assign = harmony_objective = harmony_correct = None
+    # muon_amd.pp.scrublet (scrublet.hip): the sum of two canonical CSR rows per simulated doublet (f32 values, int32 or
+    # int64 indices, rows of any length), and knn_merge past its 1024 pairs: kc + cap <= knn_merge_wide_max()
+    csr_pair_rows = knn_merge_wide_max = knn_merge_wide = None
     # synthetic counts of the benchmark and the tests (synth.hip)
     synth_counts = None
 

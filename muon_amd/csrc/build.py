@@ -11,7 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["runtime.hip", "tfidf.hip", "transpose.hip", "spmm.hip", "spmm_win.hip", "spmm_narrow.hip", "spmm_ell.hip", "tpack4.hip", "tperm.hip", "tflat.hip", "dense.hip", "skinny.hip", "synth.hip", "mofa.hip", "mofa_elbo.hip", "mofa_stats.hip", "mofa_poisson.hip", "mofa_bernoulli.hip", "knn.hip", "wnn.hip", "prot.hip", "filter.hip", "fragments.hip", "ica.hip", "rank.hip", "snf.hip", "motif.hip", "cluster.hip", "umap.hip", "nmf.hip", "rna.hip", "gp.hip", "scale.hip", "qc.hip", "harmony.hip"]
+SOURCES = ["runtime.hip", "tfidf.hip", "transpose.hip", "spmm.hip", "spmm_win.hip", "spmm_narrow.hip", "spmm_ell.hip", "tpack4.hip", "tperm.hip", "tflat.hip", "dense.hip", "skinny.hip", "synth.hip", "mofa.hip", "mofa_elbo.hip", "mofa_stats.hip", "mofa_poisson.hip", "mofa_bernoulli.hip", "knn.hip", "wnn.hip", "prot.hip", "filter.hip", "fragments.hip", "ica.hip", "rank.hip", "snf.hip", "motif.hip", "cluster.hip", "umap.hip", "nmf.hip", "rna.hip", "gp.hip", "scale.hip", "qc.hip", "harmony.hip", "scrublet.hip"]
 HEADERS = ["common.hpp", "sweep.hpp", os.path.join(ROOT, "include", "muon_amd.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in VGPRs.  The default (AGPR form) kept the accumulators of these files'
 # loops in VGPRs BETWEEN the steps and copied them to AGPRs and back around the MFMAs of every step (k_skinny_tn: 64

@@ -50,7 +50,7 @@ static int tune_find(const char* key) {
 
 extern "C" {
 
-int mu_version(void) { return 816; }  // 816: mu_harmony_gram_f64, mu_harmony_gram_worksize, mu_harmony_assign_f64, mu_harmony_objective_f64, mu_harmony_objective_worksize, mu_harmony_correct_f64, mu_harmony_max_clusters / _dims / _levels (csrc/harmony.hip: muon_amd.pp.harmony_integrate); 815: mu_csr_row_masked_sums, mu_csr_row_top_sums (csrc/qc.hip); 814: mu_scale_values, mu_scale_dense_rows (csrc/scale.hip); 812: mu_tune_count, mu_tune_name, mu_tune_default (the tune keys declared once, common.hpp: MU_TUNE_KEYS); the keys ell_mode, tfidf_wide, tfidf_abl, tn_pipe, nn_fast_off, tpack4_m, scale_stream_off, tpack4_abl, tpack4_late retired with their kernel variants;  // 811: mu_gene_moments, mu_gene_moments_max_blocks, mu_rna_value_sweep, mu_shift_cols_f32, mu_scale_rows_f32 (csrc/rna.hip: muon_amd.rna.pp, muon_amd.tl.pca);  // 810: mu_nmf_cd_sweep_f64, mu_nmf_cd_worksize, mu_nmf_max_components (csrc/nmf.hip: muon.atac.pp.scopen);  // 809: mu_tflat_plan, mu_tflat_fill, mu_tflat_fill_phases, mu_tflat_rounds (csrc/tflat.hip: the flat read-in of the table-driven fill), tune key tperm_flat;  // 808: mu_tperm_fill_phases (csrc/tperm.hip: the phase-accounting instance of the table-driven fill);  // 807: mu_umap_epoch_f64, mu_umap_max_components (csrc/umap.hip: muon.tl.umap);  // 806: mu_cluster_* (csrc/cluster.hip: muon.tl.leiden / muon.tl.louvain);  // 805: mu_motif_* (csrc/motif.hip: muon.atac.tl.scan_sequences);  // 804: mu_snf_* (csrc/snf.hip: muon.tl.snf);  // 803: mu_spmm_stream_slab_f32, mu_spmm_stream_ranges_slab_f32, mu_spmm_stream_slab_ok (csrc/spmm_win.hip: 320-column Q slabs), tune key spmm_slab;  // 802: mu_group_moments, mu_rank_sums (csrc/rank.hip: muon.atac.tl.rank_peaks_groups);  // 801: mu_ica_* (csrc/ica.hip: muon.tl.ica);  // 800: mu_frag_* (csrc/fragments.hip: muon.atac.tl fragment tools; mu_csr_qc / mu_csr_submatrix_* of csrc/filter.hip came in between);  // 700: mu_prot_* (csrc/prot.hip: muon.prot.pp.dsb);  // r06 (601): mu_mofa_poisson_blocks_for, mu_mofa_poisson_dense_ld / _sparse_ld (row stride of the factor blocks);  // r06: mu_spmm_stream_ranges_f32, mu_csr_slice_stream, mu_tpack4_cnt_offset / _err_offset added; the matrix-core SpMM experiment (mu_cells_*, mu_dense_to_f16, mu_spmm_cells_f32, mu_probe_*) and the third-generation transposition (mu_csr_tpack_*) removed (archived: scripts/probes/spmm_mfma.hip, tpack_v3.hip);  // r05: mu_tfidf_scale_sweep_stream, mu_tpack4_* (the transposition on the row stream);  // r04: matrix-core SpMM (mu_cells_*, mu_dense_to_f16, mu_spmm_cells_f32, probes);  // r03: mu_mofa_rowstats, mu_mofa_gs_update, mu_mofa_poisson_pseudo, mu_mofa_jaakkola, mu_csr_densify_rows, mu_knn_filter_f64, mu_wnn_bandwidth_f64, mu_umap_strengths_f64 added, mu_mofa_update_z takes d_corr, mu_spmm_ws_* removed
+int mu_version(void) { return 817; }  // 817: mu_harmony_gram_f64, mu_harmony_gram_worksize, mu_harmony_assign_f64, mu_harmony_objective_f64, mu_harmony_objective_worksize, mu_harmony_correct_f64, mu_harmony_max_clusters / _dims / _levels (csrc/harmony.hip: muon_amd.pp.harmony_integrate); 815: mu_csr_row_masked_sums, mu_csr_row_top_sums (csrc/qc.hip); 814: mu_scale_values, mu_scale_dense_rows (csrc/scale.hip); 812: mu_tune_count, mu_tune_name, mu_tune_default (the tune keys declared once, common.hpp: MU_TUNE_KEYS); the keys ell_mode, tfidf_wide, tfidf_abl, tn_pipe, nn_fast_off, tpack4_m, scale_stream_off, tpack4_abl, tpack4_late retired with their kernel variants;  // 811: mu_gene_moments, mu_gene_moments_max_blocks, mu_rna_value_sweep, mu_shift_cols_f32, mu_scale_rows_f32 (csrc/rna.hip: muon_amd.rna.pp, muon_amd.tl.pca);  // 810: mu_nmf_cd_sweep_f64, mu_nmf_cd_worksize, mu_nmf_max_components (csrc/nmf.hip: muon.atac.pp.scopen);  // 809: mu_tflat_plan, mu_tflat_fill, mu_tflat_fill_phases, mu_tflat_rounds (csrc/tflat.hip: the flat read-in of the table-driven fill), tune key tperm_flat;  // 808: mu_tperm_fill_phases (csrc/tperm.hip: the phase-accounting instance of the table-driven fill);  // 807: mu_umap_epoch_f64, mu_umap_max_components (csrc/umap.hip: muon.tl.umap);  // 806: mu_cluster_* (csrc/cluster.hip: muon.tl.leiden / muon.tl.louvain);  // 805: mu_motif_* (csrc/motif.hip: muon.atac.tl.scan_sequences);  // 804: mu_snf_* (csrc/snf.hip: muon.tl.snf);  // 803: mu_spmm_stream_slab_f32, mu_spmm_stream_ranges_slab_f32, mu_spmm_stream_slab_ok (csrc/spmm_win.hip: 320-column Q slabs), tune key spmm_slab;  // 802: mu_group_moments, mu_rank_sums (csrc/rank.hip: muon.atac.tl.rank_peaks_groups);  // 801: mu_ica_* (csrc/ica.hip: muon.tl.ica);  // 800: mu_frag_* (csrc/fragments.hip: muon.atac.tl fragment tools; mu_csr_qc / mu_csr_submatrix_* of csrc/filter.hip came in between);  // 700: mu_prot_* (csrc/prot.hip: muon.prot.pp.dsb);  // r06 (601): mu_mofa_poisson_blocks_for, mu_mofa_poisson_dense_ld / _sparse_ld (row stride of the factor blocks);  // r06: mu_spmm_stream_ranges_f32, mu_csr_slice_stream, mu_tpack4_cnt_offset / _err_offset added; the matrix-core SpMM experiment (mu_cells_*, mu_dense_to_f16, mu_spmm_cells_f32, mu_probe_*) and the third-generation transposition (mu_csr_tpack_*) removed (archived: scripts/probes/spmm_mfma.hip, tpack_v3.hip);  // r05: mu_tfidf_scale_sweep_stream, mu_tpack4_* (the transposition on the row stream);  // r04: matrix-core SpMM (mu_cells_*, mu_dense_to_f16, mu_spmm_cells_f32, probes);  // r03: mu_mofa_rowstats, mu_mofa_gs_update, mu_mofa_poisson_pseudo, mu_mofa_jaakkola, mu_csr_densify_rows, mu_knn_filter_f64, mu_wnn_bandwidth_f64, mu_umap_strengths_f64 added, mu_mofa_update_z takes d_corr, mu_spmm_ws_* removed
 
 int mu_tune_set(const char* key, int value) {
   MU_REQUIRE(key, "null key");
